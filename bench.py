@@ -13,15 +13,23 @@ launches the N ranks itself as child processes BEFORE making any GPU call, and r
 JSON line.  Default for N > 1 is STRONG scaling -- config 4 as BASELINE words it: ONE 256 x 2048
 batch whose rows are split over the ranks exactly as the reference's loader slices them
 (train_gpt.py:795-805) -- `--scaling weak` runs the full batch on every rank instead.  The path
-has no data-path collective; the only RCCL traffic is the all-reduce of the int64[4] byte
-statistics (and of the timings) after the timed region.
+has no data-path collective; the only RCCL traffic is the all-reduce of the timings (and, with
+`--full`, of the int64[4] byte statistics) after the timed region.
 
 Prints ONE JSON line (rank 0).  `roofline.achieved` = algorithmic bytes per launch / average
 launch duration measured with HIP events on the launch stream over the timed region (per rank;
-the slowest rank's duration is used); `cpu_baseline` = the CPU oracle (a C/OpenMP port of the
-reference path) timed on this host on a bounded sample; `extra` (N = 1) = the same kernel where
-caches cannot help: uniform ids, a token table larger than the Infinity Cache, the 65 536-token
-shard each GPU sees at 8-way strong scaling.
+the slowest rank's duration is used).
+
+A plain run sets up, warms up, times `--steps` steps and prints the line.  Everything else it
+can measure runs only with `--full`, after the timed region: the per-launch distribution, a
+device-copy bandwidth, the byte-statistics pass, the backward record (default workload),
+`cpu_baseline` = the CPU oracle (a C/OpenMP port of the reference path) timed on this host on a
+bounded sample, and `extra` (N = 1) = the same kernel where caches cannot help: uniform ids, a
+token table larger than the Infinity Cache, the 65 536-token shard each GPU sees at 8-way strong
+scaling.
+
+`--dump-outputs DIR` writes what the last timed step computed (rank 0) as DIR/x.npy, float32:
+the whole output when it fits in DUMP_BYTES, otherwise a fixed, seeded sample of its rows.
 """
 from __future__ import annotations
 
@@ -65,6 +73,7 @@ WORKLOADS = {
     "prodl": (64, 1024, 50257, 16, 1024, 48, 458, "concat_linear", 256),  # experiments100_000steps.sh dims (K = 1024)
 }
 F32_MFMA_PEAK_TFLOPS = 157.3  # dense fp32 matrix peak, MI355X_MICROARCH.md
+DUMP_BYTES = 48 << 20         # --dump-outputs budget: 16 384 rows of d_model 768 in fp32
 # sources whose change invalidates the committed PMC traffic figure of the fused SUM kernel
 TRAFFIC_SOURCES = ("mixture-of-tokenizers_amd/csrc/mot_embed.hip", "mixture-of-tokenizers_amd/csrc/mot_wave.hpp",
                    "mixture-of-tokenizers_amd/csrc/mot_mix.hpp", "mixture-of-tokenizers_amd/csrc/mot_tile.hpp")   # what the fused kernel is compiled from
@@ -91,8 +100,15 @@ def parse(argv=None):
                          "256x2048 batch sharded over the GPUs, train_gpt.py:795-805); weak: every rank runs the full batch")
     ap.add_argument("--dtype", default="f32", choices=["f32", "bf16"], help="table/output element type (compute is fp32)")
     ap.add_argument("--backward", action="store_true", help="also time the backward launch (sum workloads) and report it")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary records (uniform ids, table > Infinity Cache, 65 536-token shard)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beyond the headline: per-launch distribution, device-copy "
+                         "bandwidth, byte statistics, and (default workload, one GPU) the backward, secondary and CPU-baseline records")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output to DIR/x.npy (float32; a seeded sample of rows beyond DUMP_BYTES)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="with --full: skip the secondary records (uniform ids, table > Infinity Cache, 65 536-token shard) and the "
+                         "default backward record")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend of the N-rank run: nccl (= RCCL over xGMI, the real thing) or gloo (collectives on CPU "
@@ -103,6 +119,8 @@ def parse(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous / aggregation only: gloo on the CPU, no GPU call, no kernel (CPU tests of the N-rank path)")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.scaling is None:
         args.scaling = "strong" if args.gpus > 1 else "weak"
     return args
@@ -305,6 +323,21 @@ def timed_launches(step, n, warm=5):
     return e0.elapsed_time(e1) / n
 
 
+def dump_outputs(out, directory):
+    """`out` (.., d) as DIR/x.npy in float32: whole when it fits in DUMP_BYTES, else the rows at a fixed set of positions
+    (RandomState(0) draw without replacement, ascending), so two builds run with the same arguments compare row for row."""
+    x = out.reshape(-1, out.shape[-1])
+    keep = DUMP_BYTES // (x.shape[1] * 4)
+    if x.shape[0] > keep:
+        idx = np.sort(np.random.RandomState(0).choice(x.shape[0], keep, replace=False))
+        x = x.index_select(0, torch.from_numpy(idx).to(x.device))
+    else:
+        x = out
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / "x.npy", x.float().cpu().numpy())
+
+
 def extra_records(mot, device, dtype, steps, warmup):
     """The headline kernel where caches cannot carry it (N = 1 only, outside the timed region): each record is the same
     fused SUM launch with its own algorithmic bytes / HIP-event time."""
@@ -462,7 +495,7 @@ def main(argv=None):
 
     # one bound descriptor per variant: a step is exactly one mot_embed_mix_fwd call on the current stream
     plan = mot.embed_mix_plan(toks, inp["tok_table"], inp["byte_table"], **kwf)
-    plan_cnt = None if mode == "mean" else mot.embed_mix_plan(toks, inp["tok_table"], inp["byte_table"], counters=counters, **kwf)
+    plan_cnt = None if mode == "mean" or not args.full else mot.embed_mix_plan(toks, inp["tok_table"], inp["byte_table"], counters=counters, **kwf)
 
     def step():
         plan()
@@ -485,29 +518,32 @@ def main(argv=None):
     barrier()
     elapsed = time.perf_counter() - t0
     kernel_ms = ev0.elapsed_time(ev1) / args.steps          # HIP events on the launch stream
-    # per-launch distribution (median and p10/p90), outside the timed region: 64 individually evented launches
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(64)]
-    for a, b in evs:
-        a.record(); step(); b.record()
-    torch.cuda.synchronize()
-    lat = sorted(a.elapsed_time(b) * 1e3 for a, b in evs)
-    launch_us = {"p10": lat[6], "p50": lat[32], "p90": lat[57]}
-    # what a plain device copy of the same volume reaches on this GPU ("also report against a measured
-    # device-copy bandwidth"): read + write of out-sized buffers, outside the timed region
-    copy_gbs = None
-    if rank == 0:
-        src = torch.empty(out.numel() * out.element_size() // 4, dtype=torch.float32, device=device).normal_()
-        dst = torch.empty_like(src)
-        dst.copy_(src); torch.cuda.synchronize()
-        c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        c0.record()
-        for _ in range(10):
-            dst.copy_(src)
-        c1.record(); torch.cuda.synchronize()
-        copy_gbs = 2 * src.numel() * 4 * 10 / (c0.elapsed_time(c1) * 1e-3) / 1e9
-        del src, dst
-    if plan_cnt is not None:
-        plan_cnt()                                          # statistics pass, outside the timed region
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)                # before anything else writes `out`
+    launch_us = copy_gbs = None
+    if args.full:
+        # per-launch distribution (median and p10/p90), outside the timed region: 64 individually evented launches
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(64)]
+        for a, b in evs:
+            a.record(); step(); b.record()
+        torch.cuda.synchronize()
+        lat = sorted(a.elapsed_time(b) * 1e3 for a, b in evs)
+        launch_us = {"p10": lat[6], "p50": lat[32], "p90": lat[57]}
+        # what a plain device copy of the same volume reaches on this GPU ("also report against a measured
+        # device-copy bandwidth"): read + write of out-sized buffers, outside the timed region
+        if rank == 0:
+            src = torch.empty(out.numel() * out.element_size() // 4, dtype=torch.float32, device=device).normal_()
+            dst = torch.empty_like(src)
+            dst.copy_(src); torch.cuda.synchronize()
+            c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            c0.record()
+            for _ in range(10):
+                dst.copy_(src)
+            c1.record(); torch.cuda.synchronize()
+            copy_gbs = 2 * src.numel() * 4 * 10 / (c0.elapsed_time(c1) * 1e-3) / 1e9
+            del src, dst
+        if plan_cnt is not None:
+            plan_cnt()                                      # statistics pass, outside the timed region
     torch.cuda.synchronize()
     mot.check_status()
 
@@ -517,8 +553,9 @@ def main(argv=None):
         import torch.distributed as dist
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-        counters = counters.to(cdev)
-        dist.all_reduce(counters, op=dist.ReduceOp.SUM)     # the path's only collective: <= 64 B over RCCL/xGMI
+        if args.full:
+            counters = counters.to(cdev)
+            dist.all_reduce(counters, op=dist.ReduceOp.SUM)     # the path's only collective: <= 64 B over RCCL/xGMI
         kall = torch.zeros(world, dtype=torch.float64, device=cdev)
         kall[rank] = kernel_ms
         dist.all_reduce(kall, op=dist.ReduceOp.SUM)
@@ -572,9 +609,10 @@ def main(argv=None):
             **({"rehearsal": True, "rehearsal_note": "all ranks on cuda:0, collectives over gloo: NOT a multi-GPU measurement"}
                if args.one_device else {}),
             "library": mot.build_info(),
-            "byte_stats": {"tokens": c[0], "slots": c[1], "pads_before": c[2], "pads_after": c[3],
-                           "mean_valid_per_token": (c[1] - c[2]) / max(c[0], 1),
-                           "pulled_fill": (c[2] - c[3]) / max(c[1], 1)},
+            **({"byte_stats": {"tokens": c[0], "slots": c[1], "pads_before": c[2], "pads_after": c[3],
+                               "mean_valid_per_token": (c[1] - c[2]) / max(c[0], 1),
+                               "pulled_fill": (c[2] - c[3]) / max(c[1], 1)}}
+               if args.full else {}),
         }
         if mode == "concat_linear":   # dense contraction: priced against the fp32 matrix peak, not HBM
             K = WORKLOADS[wl][8] + bpt * Db
@@ -590,9 +628,10 @@ def main(argv=None):
                                           ("gemm_rows_bt_kernel" if args.dtype == "f32" else "gemm_rows_bf16_kernel") +
                                           " + rows_rms_inplace (whole call)"),
                                "kernel_ms": kernel_ms, "flop_per_token": 2 * K * D, "tokens_per_launch": tokens_per_step}
-        # the backward record: on request, and with the headline line itself (one GPU, default workload, secondary records not
-        # switched off) so that the driver's own run carries it
-        want_bwd = args.backward or (world == 1 and wl == "c4" and args.ids == "fused" and not args.uniform_ids and not args.no_extra)
+        # the backward record: on request, and with a --full line of the headline itself (one GPU, default workload, secondary
+        # records not switched off)
+        want_bwd = args.backward or (args.full and world == 1 and wl == "c4" and args.ids == "fused" and not args.uniform_ids
+                                     and not args.no_extra)
         if want_bwd and mode == "sum":
             from mixture_of_tokenizers_amd import data_creation as dc
             F = mot.functional
@@ -631,11 +670,11 @@ def main(argv=None):
                                        "token row is read and its gradient row flushed (fp32 atomic row-add) once per run, byte-table "
                                        "gradient in 64-bit fixed point in LDS; backward_grouping_itself_ms = the same call without a given "
                                        "order; hbm_read counts the algorithmic grad_out row + token row per position"}
-        if world == 1 and mode == "sum" and wl == "c4" and args.ids == "fused" and not args.uniform_ids and not args.no_extra:
+        if args.full and world == 1 and mode == "sum" and wl == "c4" and args.ids == "fused" and not args.uniform_ids and not args.no_extra:
             del plan, plan_cnt, out
             torch.cuda.empty_cache()
             res["extra"] = extra_records(mot, device, args.dtype, args.steps, args.warmup)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             res["cpu_baseline"] = cpu_baseline(wl, inp, args.cpu_seconds)
         print(json.dumps(res), flush=True)
     if use_dist:

@@ -351,3 +351,36 @@ def test_bench_rank_slices_are_rows_of_the_one_global_batch():
             np.testing.assert_array_equal(np.concatenate([p["toks"] for p in parts]), whole["toks"])
             if "chars" in whole:
                 np.testing.assert_array_equal(np.concatenate([p["chars"] for p in parts]), whole["chars"])
+
+
+def test_bench_plain_and_full_options_and_output_dump(tmp_path):
+    """bench.py's argument contract (--full off by default, --steps at least 1) and dump_outputs(): the whole output when it fits
+    in DUMP_BYTES, else DUMP_BYTES worth of rows at RandomState(0)-drawn ascending positions, always float32."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_for_dump", REPO / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", str(tmp_path)])
+    assert a.full is True and a.dump_outputs == str(tmp_path)
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+    small = torch.randn(2, 5, 8, dtype=torch.bfloat16)
+    bench.dump_outputs(small, tmp_path / "small")
+    got = np.load(tmp_path / "small" / "x.npy")
+    assert got.dtype == np.float32 and got.shape == (2, 5, 8)
+    np.testing.assert_array_equal(got, small.float().numpy())
+
+    D = 1024
+    keep = bench.DUMP_BYTES // (D * 4)
+    big = torch.arange(3 * keep, dtype=torch.float32)[:, None].expand(3 * keep, D).reshape(3, keep, D)
+    for name in ("big1", "big2"):
+        bench.dump_outputs(big, tmp_path / name)
+    got = np.load(tmp_path / "big1" / "x.npy")
+    assert got.dtype == np.float32 and got.shape == (keep, D) and got.nbytes <= 64 << 20
+    rows = got[:, 0].astype(np.int64)
+    assert (got == rows[:, None]).all() and (np.diff(rows) > 0).all() and rows.max() < 3 * keep
+    np.testing.assert_array_equal(rows, np.sort(np.random.RandomState(0).choice(3 * keep, keep, replace=False)))
+    np.testing.assert_array_equal(np.load(tmp_path / "big2" / "x.npy"), got)

@@ -21,6 +21,6 @@ run c5_sq "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INS
 cd "$root"
 for t in b4_fetch b4_write b4_sq b4_tcc c5_fetch c5_write c5_tcc c5_sq; do echo "== $t"; python3 tools/pmc_summary.py "$out/$t" 2>&1 | grep -v "zero_i32\|rows_rnorm" ; done > "$out/summary.txt"
 for t in b4_kt c5_kt; do echo "== $t"; f=$(find "$out/$t" -name "*_kernel_stats.csv" | head -1); [ -n "$f" ] && head -12 "$f"; done >> "$out/summary.txt"
-python3 bench.py --workload c4 --backward --no-cpu-baseline --no-extra > "$out/bench_c4_bwd.json" 2> "$out/bench_c4_bwd.err"
-python3 bench.py --workload c5 --steps 20 --warmup 3 --no-cpu-baseline --no-extra > "$out/bench_c5.json" 2> "$out/bench_c5.err"
+python3 bench.py --full --workload c4 --backward --no-cpu-baseline --no-extra > "$out/bench_c4_bwd.json" 2> "$out/bench_c4_bwd.err"
+python3 bench.py --full --workload c5 --steps 20 --warmup 3 --no-cpu-baseline --no-extra > "$out/bench_c5.json" 2> "$out/bench_c5.err"
 tail -c 1500 "$out/summary.txt"
