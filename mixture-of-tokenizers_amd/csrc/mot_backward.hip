@@ -2310,6 +2310,10 @@ __global__ __launch_bounds__(kTnThreads) void gemm_tn_bf16_kernel(const __bf16 *
 // A, B: 16-byte aligned, lda / ldb / M / Kc multiples of 8
 int launch_gemm_tn_bf16(const __bf16 *A_, int lda, int M, const __bf16 *B_, int ldb, int Kc, int64_t rows, float *C, int ldc, hipStream_t stream) {
     if (M <= 0 || Kc <= 0 || rows <= 0) return MOT_OK;
+    // (the kernel loads whole 16-byte pieces and guards a piece by its first column only)
+    if ((lda & 7) || (ldb & 7) || (M & 7) || (Kc & 7) || ((uintptr_t)A_ & 15) || ((uintptr_t)B_ & 15))
+        return set_error(MOT_EUNSUPPORTED, "gemm_tn_bf16: rows must be 16-byte aligned, lda / ldb / M / Kc multiples of 8 (lda %d, ldb %d, M %d, Kc %d)", lda,
+                         ldb, M, Kc);
     const int tiles = ((M + 127) / 128) * ((Kc + 127) / 128);
     // contraction slices: two workgroups per CU (80 KB of LDS each), a multiple of 8 for the XCD mapping, few enough to keep the
     // atomic volume (slices x M x Kc x 4 bytes) small

@@ -335,6 +335,16 @@ int launch_gemm_rows_f32_256(const float *A_, int lda, int64_t n, const float *B
     return check_launch("gemm_rows_256_kernel");
 }
 
+// bf16 operands: the 256 x 256 LDS-DMA kernel takes the shape (Nc % 256, R % 32, 512 rows and more, rows 16-byte aligned); false: the
+// 128 x 128 kernel above
+bool gemm_rows_bf16_256_usable(const void *A_, int lda, int64_t n, const void *B_, int ldb, int R, int Nc) {
+    bool ok = (Nc % 256) == 0 && (R % 32) == 0 && n >= 512 && !(lda & 7) && !(ldb & 7) && !(((uintptr_t)A_ | (uintptr_t)B_) & 15) &&
+              (int64_t)256 * (lda > ldb ? lda : ldb) * 2 < 0x7fffffffLL;
+#ifdef MOT_DEV_ABLATION
+    if (getenv("MOT_GEMM16_OLD")) ok = false;
+#endif
+    return ok;
+}
 int launch_gemm_rows_bf16(const void *A_, int lda, int64_t n, const void *B_, int ldb, int R, int Nc, void *C, int ldc, bool out_bf16,
                           const void *bias, hipStream_t stream, bool accumulate, const float *addend) {
     if (n <= 0 || Nc <= 0) return MOT_OK;
@@ -342,11 +352,7 @@ int launch_gemm_rows_bf16(const void *A_, int lda, int64_t n, const void *B_, in
     if (accumulate) addend = (const float *)C;
     if ((R & 7) || (lda & 7) || (ldb & 7) || ((uintptr_t)A_ & 15) || ((uintptr_t)B_ & 15))
         return set_error(MOT_EUNSUPPORTED, "gemm_rows_bf16: rows must be 16-byte aligned multiples of 8 elements (R %d, lda %d, ldb %d)", R, lda, ldb);
-    bool big = (Nc % 256) == 0 && (R % 32) == 0 && n >= 512 && (int64_t)256 * (lda > ldb ? lda : ldb) * 2 < 0x7fffffffLL;
-#ifdef MOT_DEV_ABLATION
-    if (getenv("MOT_GEMM16_OLD")) big = false;
-#endif
-    if (big) {   // 256 x 256 blocks by LDS-DMA
+    if (gemm_rows_bf16_256_usable(A_, lda, n, B_, ldb, R, Nc)) {   // 256 x 256 blocks by LDS-DMA
         const int64_t gx2 = (n + 255) / 256, blocks2 = (gx2 + 7) / 8 * 8 * (Nc / 256);
         if (blocks2 > 0x7fffffffLL) return set_error(MOT_EUNSUPPORTED, "gemm_rows_bf16: too many rows");
         const size_t lds = (size_t)kG2NS * (256 + 256) * 64;

@@ -35,6 +35,22 @@ def test_product_does_not_import_the_oracle():
             assert "oracle" not in src.read_text().lower(), src
 
 
+def test_product_never_loads_the_probe():
+    """tests/native/libmot_probe.so (the test-only entry points to the matrix-product launchers) stays out of the product:
+    nothing in the package or its sources names it, include/mot.h declares none of it, and importing the package maps it not."""
+    import subprocess
+    import sys
+    pkg = REPO / "mixture-of-tokenizers_amd"
+    for src in [*pkg.rglob("*.py"), *(pkg / "csrc").iterdir(), REPO / "include" / "mot.h", REPO / "mixture_of_tokenizers_amd.py"]:
+        if src.suffix in (".py", ".hip", ".hpp", ".cpp", ".h"):
+            assert "probe" not in src.read_text().lower(), src
+    code = ("import mixture_of_tokenizers_amd as m; m.build_info(); "
+            "maps = open('/proc/self/maps').read(); assert 'libmot_hip' in maps; print('libmot_probe' in maps)")
+    r = subprocess.run([sys.executable, "-c", code], cwd=REPO, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    assert r.stdout.strip() == "False"
+
+
 def test_cpu_tensors_are_refused():
     import mixture_of_tokenizers_amd as mot
     with pytest.raises(RuntimeError, match="HIP device only"):
