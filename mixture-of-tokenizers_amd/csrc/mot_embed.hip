@@ -15,45 +15,39 @@
 //               Algorithmic traffic: 4 + 2*bpt + 4*Dt B read and 4*Dm B written per token; HBM-bound.
 #include <stdlib.h>
 
+#include <algorithm>
+
 #include "mot_wave.hpp"
 
 namespace mot {
 
 // ------------------------------------------------------------------------------------------ fused kernel
-// MODE: MOT_MIX_NOOP / SUM / MEAN.   NCH: 16-byte chunks per lane (covers Dm <= 64*NCH*VEC).   U: tokens in flight per wave.
-// Every WAVE is on its own (mot_wave.hpp): it owns a unit of A.unit consecutive tokens of one row, produces their byte ids
-// in wave-private LDS and streams them; the four waves of a workgroup share nothing and never meet at a barrier.
-// (105 VGPRs at fp32 / 768 columns: four waves per SIMD.  Forcing the fifth with a launch bound spills into the streaming loop:
-// 471 us instead of 435 at 524 288 tokens.)
+// Phase 2 of one wave, shared by embed_mix_kernel and the routed kernel: `ntok` tokens whose ids sit in lanes unit_lane0 .. of
+// `tokv` and whose byte ids sit in W.ids (W.ids2) at [t * (bpt | 1) + k]; token t's output row is out_row(t).  U tokens in flight.
 template <int MODE, int NCH, int U, typename T, bool DUAL>
-__global__ __launch_bounds__(kThreads) void embed_mix_kernel(const MixArgs A) {
-    const T *tok_table = (const T *)A.tok_table, *byte_table = (const T *)A.byte_table;
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_wave[];
-    constexpr bool has_ids = MODE != MOT_MIX_NOOP;
-    constexpr bool dual = DUAL;                   // two id tensors: emb(padded) + emb(pulled)
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t unit_id = (int64_t)blockIdx.x * kWaves + wave;
-    if (unit_id >= A.n_units) return;             // no barrier anywhere below: a wave may leave on its own
-    const int64_t row = unit_id / A.units_per_row;
-    const int64_t u0 = (unit_id - row * A.units_per_row) * A.unit;
-    const int ntok = (int)min((int64_t)A.unit, A.T - u0);
-    const int stream_eb = (has_ids && A.id_source == MOT_IDS_FROM_TTB && A.pull_dir != kPullNone) ? A.ttb_elem : 0;
-    const WaveLds W = wave_lds_carve(lds_wave + (size_t)wave * A.wave_lds, A.unit, has_ids ? A.bpt : 0, dual, stream_eb);
-
+struct MixStream {
     typedef typename Elem<T>::vec vec_t;          // VEC floats: one 16-byte lane load (4 fp32 / 8 bf16)
     typedef typename Elem<T>::raw raw_t;
-    constexpr int VEC = Elem<T>::kVec;
-    const int Dm = A.Dt, nchunk = Dm / VEC;
-    bool act[NCH];
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) act[i] = lane + 64 * i < nchunk;
-    // token rows of a batch of U tokens: lane unit_lane0 + j of `tokv` holds the unit's token j.  The first batch is requested
-    // as soon as the token ids are known -- BEFORE the byte-index pass, which then runs under the rows' flight time instead of
-    // in front of the first HBM request of every wave of a small launch.
+    static constexpr int VEC = Elem<T>::kVec;
+    const MixArgs &A;
+    const WaveLds &W;
+    const T *tok_table, *byte_table;
+    int lane, Dm, nchunk, ntok;
     int tokv = 0, unit_lane0 = 0;
-    raw_t ar[U][NCH];
-    auto request_tok_rows = [&](int tb) {
+    bool act[NCH];
+    raw_t ar[U][NCH];                               // token rows of the batch in flight
+
+    __device__ __forceinline__ MixStream(const MixArgs &A_, const WaveLds &W_, int ntok_) : A(A_), W(W_), ntok(ntok_) {
+        tok_table = (const T *)A.tok_table;
+        byte_table = (const T *)A.byte_table;
+        lane = threadIdx.x & 63;
+        Dm = A.Dt;
+        nchunk = Dm / VEC;
+#pragma unroll
+        for (int i = 0; i < NCH; ++i) act[i] = lane + 64 * i < nchunk;
+    }
+    // token rows of a batch of U tokens: lane unit_lane0 + j of `tokv` holds token j
+    __device__ __forceinline__ void request(int tb) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int t = min(tb + u, ntok - 1);  // the tail re-reads the last token; its store is skipped
@@ -66,19 +60,156 @@ __global__ __launch_bounds__(kThreads) void embed_mix_kernel(const MixArgs A) {
 #pragma unroll
             for (int i = 0; i < NCH; ++i) ar[u][i] = Elem<T>::load_raw(trow + VEC * (act[i] ? lane + 64 * i : 0));
         }
-    };
+    }
+    // the first batch's token rows must have been requested
+    template <class RowOf>
+    __device__ __forceinline__ void run(RowOf &&out_row) {
+        constexpr bool dual = DUAL;
+        const int sv = A.bpt | 1;
+        int slot[NCH], within[NCH];
+#pragma unroll
+        for (int i = 0; i < NCH; ++i) {
+            const int c = lane + 64 * i;
+            const int cc = act[i] ? c : 0;
+            if (MODE == MOT_MIX_SUM) {
+                slot[i] = (VEC * cc) / A.Db;            // concat_k: column j belongs to slot j / Db
+                within[i] = VEC * cc - slot[i] * A.Db;
+            } else {
+                slot[i] = 0;
+                within[i] = VEC * cc;
+            }
+        }
+        const float s_tok = A.scale_tok ? *A.scale_tok : 1.0f;
+        const float s_byte = A.scale_byte ? *A.scale_byte : 1.0f;
+        const bool scale_t = A.scale_tok != nullptr, scale_b = A.scale_byte != nullptr;
+        auto sumsq = [](const vec_t &v) {
+            float s = 0.f;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) s += v[e] * v[e];
+            return s;
+        };
+
+        for (int tb = 0; tb < ntok; tb += U) {
+            raw_t br[U][NCH], br2[DUAL ? U : 1][NCH];  // rows exactly as loaded (bf16 stays packed until it is used)
+            vec_t bm[U][NCH];                           // MEAN accumulates while loading
+            int idr[U][NCH];
+            // ---- issue every load of the U tokens before touching any of them (the first batch's token rows are already in flight)
+            if (tb > 0) request(tb);
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int t = min(tb + u, ntok - 1);
+#pragma unroll
+                for (int i = 0; i < NCH; ++i) {
+                    if (MODE == MOT_MIX_SUM) {
+                        const int id = W.ids[t * sv + slot[i]];
+                        idr[u][i] = id;
+                        br[u][i] = Elem<T>::load_raw(byte_table + (int64_t)id * A.Db + within[i]);
+                        if (dual) br2[DUAL ? u : 0][i] = Elem<T>::load_raw(byte_table + (int64_t)W.ids2[t * sv + slot[i]] * A.Db + within[i]);
+                    } else if (MODE == MOT_MIX_MEAN) {
+                        vec_t acc = (vec_t)(0.f);
+                        for (int k = 0; k < A.bpt; ++k) {  // chars.mean(dim=-2), inference.py:267
+                            const int id = W.ids[t * sv + k];
+                            vec_t v = Elem<T>::loadv(byte_table + (int64_t)id * A.Db + within[i]);
+                            if (dual) {
+                                const int id2 = W.ids2[t * sv + k];
+                                v += Elem<T>::loadv(byte_table + (int64_t)id2 * A.Db + within[i]);
+                            }
+                            if (A.norm_byte) v *= A.byte_rnorm[id];
+                            acc += v;
+                        }
+                        bm[u][i] = acc / (float)A.bpt;
+                    }
+                }
+            }
+            // ---- mix, normalise, store
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int t = tb + u;
+                vec_t a[1][NCH], b[1][NCH];
+#pragma unroll
+                for (int i = 0; i < NCH; ++i) {
+                    a[0][i] = Elem<T>::widen(ar[u][i]);   // lanes past the row end hold a copy of the row's first chunk: kept out of the sums below, never stored
+                    if (MODE == MOT_MIX_SUM) {
+                        vec_t v = Elem<T>::widen(br[u][i]);
+                        if (dual) v += Elem<T>::widen(br2[DUAL ? u : 0][i]);  // emb(padded) + emb(pulled), train_gpt.py:378
+                        if (A.norm_byte) v *= A.byte_rnorm[idr[u][i]];
+                        b[0][i] = v;
+                    } else if (MODE == MOT_MIX_MEAN) {
+                        b[0][i] = bm[u][i];
+                    }
+                }
+                if (A.norm_tok) {
+                    float ss = 0.f;
+#pragma unroll
+                    for (int i = 0; i < NCH; ++i) ss += act[i] ? sumsq(a[0][i]) : 0.f;
+                    const float r = rms_scale(wave_sum(ss), Dm, A.eps);
+#pragma unroll
+                    for (int i = 0; i < NCH; ++i) a[0][i] *= r;
+                }
+                if (scale_t) {
+#pragma unroll
+                    for (int i = 0; i < NCH; ++i) a[0][i] *= s_tok;
+                }
+                vec_t x[NCH];
+#pragma unroll
+                for (int i = 0; i < NCH; ++i) {
+                    if (MODE == MOT_MIX_NOOP) x[i] = a[0][i];
+                    else x[i] = a[0][i] + (scale_b ? b[0][i] * s_byte : b[0][i]);
+                }
+                if (A.norm_out) {
+                    float ss = 0.f;
+#pragma unroll
+                    for (int i = 0; i < NCH; ++i) ss += act[i] ? sumsq(x[i]) : 0.f;
+                    const float r = rms_scale(wave_sum(ss), Dm, A.eps);
+#pragma unroll
+                    for (int i = 0; i < NCH; ++i) x[i] *= r;
+                }
+                if (t < ntok) {
+                    T *orow = out_row(t);
+#pragma unroll
+                    for (int i = 0; i < NCH; ++i)
+                        if (act[i]) Elem<T>::storev_nt(orow + VEC * (lane + 64 * i), x[i]);
+                }
+            }
+        }
+    }
+};
+
+// MODE: MOT_MIX_NOOP / SUM / MEAN.   NCH: 16-byte chunks per lane (covers Dm <= 64*NCH*VEC).   U: tokens in flight per wave.
+// Every WAVE is on its own (mot_wave.hpp): it owns a unit of A.unit consecutive tokens of one row, produces their byte ids
+// in wave-private LDS and streams them; the four waves of a workgroup share nothing and never meet at a barrier.
+// (105 VGPRs at fp32 / 768 columns: four waves per SIMD.  Forcing the fifth with a launch bound spills into the streaming loop:
+// 471 us instead of 435 at 524 288 tokens.)
+template <int MODE, int NCH, int U, typename T, bool DUAL>
+__global__ __launch_bounds__(kThreads) void embed_mix_kernel(const MixArgs A) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_wave[];
+    constexpr bool has_ids = MODE != MOT_MIX_NOOP;
+    constexpr bool dual = DUAL;                   // two id tensors: emb(padded) + emb(pulled)
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t unit_id = (int64_t)blockIdx.x * kWaves + wave;
+    if (unit_id >= A.n_units) return;             // no barrier anywhere below: a wave may leave on its own
+    const int64_t row = unit_id / A.units_per_row;
+    const int64_t u0 = (unit_id - row * A.units_per_row) * A.unit;
+    const int ntok = (int)min((int64_t)A.unit, A.T - u0);
+    const int stream_eb = (has_ids && A.id_source == MOT_IDS_FROM_TTB && A.pull_dir != kPullNone) ? A.ttb_elem : 0;
+    const WaveLds W = wave_lds_carve(lds_wave + (size_t)wave * A.wave_lds, A.unit, has_ids ? A.bpt : 0, dual, stream_eb);
+    MixStream<MODE, NCH, U, T, DUAL> S(A, W, ntok);
+
     // ---- phase 1: the unit's byte ids into wave-private LDS.  Request order: token ids, their token->byte rows, the first
-    // batch's token rows; the index pass waits for the table rows only (older in the queue than the token rows).
+    // batch's token rows (as soon as the token ids are known -- BEFORE the byte-index pass, which then runs under the rows'
+    // flight time instead of in front of the first HBM request of every wave of a small launch); the index pass waits for the
+    // table rows only (older in the queue than the token rows).
     auto from_ttb = [&](auto indexer) {
-        tokv = indexer.tokens();
-        unit_lane0 = indexer.unit_lane0;
+        S.tokv = indexer.tokens();
+        S.unit_lane0 = indexer.unit_lane0;
         indexer.load_rows();
 #ifndef MOT_VAR_NOPREFETCH      // dev A/B (tools/variants.sh): rows requested after the index pass cost 1.6 us at 65 536 tokens
-        request_tok_rows(0);
+        S.request(0);
 #endif
         indexer.finish();
 #ifdef MOT_VAR_NOPREFETCH
-        request_tok_rows(0);
+        S.request(0);
 #endif
     };
     if (has_ids && A.id_source == MOT_IDS_FROM_TTB) {
@@ -92,118 +223,159 @@ __global__ __launch_bounds__(kThreads) void embed_mix_kernel(const MixArgs A) {
             else from_ttb(WaveIndexer<kPullNone, int32_t>(A, W, row, u0, ntok, dual));
         }
     } else {
-        tokv = lane < ntok ? A.tokens[row * A.T + u0 + lane] : 0;
-        request_tok_rows(0);
+        S.tokv = lane < ntok ? A.tokens[row * A.T + u0 + lane] : 0;
+        S.request(0);
         if (has_ids) wave_ids_given(A, W, row, u0, ntok);
         else if (A.counters && lane == 0) atomicAdd((unsigned long long *)A.counters, (unsigned long long)ntok);
     }
 
     // ---- phase 2
-    const int sv = A.bpt | 1;
-    int slot[NCH], within[NCH];
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-        const int c = lane + 64 * i;
-        const int cc = act[i] ? c : 0;
-        if (MODE == MOT_MIX_SUM) {
-            slot[i] = (VEC * cc) / A.Db;            // concat_k: column j belongs to slot j / Db
-            within[i] = VEC * cc - slot[i] * A.Db;
-        } else {
-            slot[i] = 0;
-            within[i] = VEC * cc;
-        }
-    }
-    const float s_tok = A.scale_tok ? *A.scale_tok : 1.0f;
-    const float s_byte = A.scale_byte ? *A.scale_byte : 1.0f;
-    const bool scale_t = A.scale_tok != nullptr, scale_b = A.scale_byte != nullptr;
-    T *orow = (T *)A.out + (row * A.T + u0) * (int64_t)Dm;
-    auto sumsq = [](const vec_t &v) {
-        float s = 0.f;
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) s += v[e] * v[e];
-        return s;
-    };
+    T *orow = (T *)A.out + (row * A.T + u0) * (int64_t)S.Dm;
+    S.run([&](int t) { return orow + (int64_t)t * S.Dm; });
+}
 
-    for (int tb = 0; tb < ntok; tb += U) {
-        raw_t br[U][NCH], br2[DUAL ? U : 1][NCH];  // rows exactly as loaded (bf16 stays packed until it is used)
-        vec_t bm[U][NCH];                           // MEAN accumulates while loading
-        int idr[U][NCH];
-        // ---- issue every load of the U tokens before touching any of them (the first batch's token rows are already in flight)
-        if (tb > 0) request_tok_rows(tb);
+// ------------------------------------------------------------------------------------------ routed SUM forward
+// At 524 288 tokens the fused kernel is bound by the bytes that leave L2, and most of them are token rows that miss: workgroups
+// are dealt round-robin over the 8 XCDs, so every XCD's L2 sees the whole id distribution and holds the same hot rows.  The
+// routed path sends the tokens whose id & 7 == k to workgroups with blockIdx.x % 8 == k -- one XCD under round-robin dispatch
+// (speed only: any placement computes the same result) -- so the eight L2s hold eight disjoint hot sets.  Two launches:
+//   route_index_kernel   the fused kernel's phase 1 unchanged (WaveIndexer, same units, halos, counters, status), then the
+//                        unit's byte ids as uint16 into the workspace and its positions sorted by bucket (uint8 offsets in the
+//                        unit + the eight bucket ends): no atomics, nothing to clear besides the eight claim counters.
+//   embed_mix_routed_kernel  persistent; a wave claims items (chunk of kRouteUnits units, bucket) from one shard of its own
+//                        bucket, then from that shard of the other buckets once it is drained (load balance whatever the id
+//                        distribution; every shard is drained by the waves that start on it, so every item runs once), and runs
+//                        phase 2 of the fused kernel (MixStream) on the item's positions: same arithmetic, same output bits.
+constexpr int kRouteUnits = 8;                   // units per chunk: an item is ~kRouteUnits * unit / 8 tokens, one per wave
+constexpr int64_t kRouteMinTokens = 131072;       // routed from here on (the fused kernel's unit switch, pick_unit)
+// Each bucket's chunks are split into kClaimShards ranges with a claim counter each, on lines of their own: with one counter per
+// bucket, the ~512 waves of an XCD queue on one address at every item start (0.74 ms instead of 0.44 at 524 288 tokens).
+constexpr int kClaimShards = 64;
+constexpr int kClaimStride = 64;                  // uint32 counters 256 bytes apart
+
+struct RouteWs {
+    uint32_t *claim;   // [8][kClaimShards] next chunk of each shard of each bucket, kClaimStride apart
+    uint8_t *ends;     // [n_units][8] inclusive end of each bucket in the unit's sorted offsets
+    uint8_t *offs;     // [n_units][unit] the unit's token offsets, grouped by bucket
+    uint16_t *ids;     // [tokens][bpt] byte ids (pulled), clamped to the byte table
+    uint16_t *ids2;    // [tokens][bpt] unpulled byte ids (add_padded), else unused
+};
+
+template <int DIR, typename E>
+__global__ __launch_bounds__(kThreads) void route_index_kernel(const MixArgs A, const RouteWs R) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_wave[];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (blockIdx.x < 2) R.claim[(blockIdx.x * kThreads + threadIdx.x) * kClaimStride] = 0;   // the routed kernel behind this one claims from 0
+    const int64_t unit_id = (int64_t)blockIdx.x * kWaves + wave;
+    if (unit_id >= A.n_units) return;
+    const int64_t row = unit_id / A.units_per_row;
+    const int64_t u0 = (unit_id - row * A.units_per_row) * A.unit;
+    const int ntok = (int)min((int64_t)A.unit, A.T - u0);
+    const bool dual = A.add_padded != 0;
+    const WaveLds W = wave_lds_carve(lds_wave + (size_t)wave * A.wave_lds, A.unit, A.bpt, dual, DIR != kPullNone ? A.ttb_elem : 0);
+    WaveIndexer<DIR, E> ix(A, W, row, u0, ntok, dual);
+    const int tok = ix.tokens();
+    ix.load_rows();
+    ix.finish();
+
+    const int bpt = A.bpt, sv = bpt | 1, n = ntok * bpt;
+    const int64_t base = (row * A.T + u0) * bpt;
+    for (int i = lane; i < n; i += 64) {
+        const int t = i / bpt, k = i - t * bpt;
+        R.ids[base + i] = (uint16_t)W.ids[t * sv + k];
+        if (dual) R.ids2[base + i] = (uint16_t)W.ids2[t * sv + k];
+    }
+    // counting sort of the unit's tokens by bucket
+    const bool in = ix.in_unit;
+    const int b = tok & 7;
+    int rank = 0, end = 0, acc = 0;
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int t = min(tb + u, ntok - 1);
-#pragma unroll
-            for (int i = 0; i < NCH; ++i) {
-                if (MODE == MOT_MIX_SUM) {
-                    const int id = W.ids[t * sv + slot[i]];
-                    idr[u][i] = id;
-                    br[u][i] = Elem<T>::load_raw(byte_table + (int64_t)id * A.Db + within[i]);
-                    if (dual) br2[DUAL ? u : 0][i] = Elem<T>::load_raw(byte_table + (int64_t)W.ids2[t * sv + slot[i]] * A.Db + within[i]);
-                } else if (MODE == MOT_MIX_MEAN) {
-                    vec_t acc = (vec_t)(0.f);
-                    for (int k = 0; k < A.bpt; ++k) {  // chars.mean(dim=-2), inference.py:267
-                        const int id = W.ids[t * sv + k];
-                        vec_t v = Elem<T>::loadv(byte_table + (int64_t)id * A.Db + within[i]);
-                        if (dual) {
-                            const int id2 = W.ids2[t * sv + k];
-                            v += Elem<T>::loadv(byte_table + (int64_t)id2 * A.Db + within[i]);
-                        }
-                        if (A.norm_byte) v *= A.byte_rnorm[id];
-                        acc += v;
-                    }
-                    bm[u][i] = acc / (float)A.bpt;
-                }
-            }
+    for (int q = 0; q < 8; ++q) {
+        const unsigned long long m = __ballot(in && b == q);
+        if (in && b == q) rank = acc + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+        acc += __popcll(m);
+        if (lane == q) end = acc;
+    }
+    if (in) R.offs[unit_id * A.unit + rank] = (uint8_t)ix.j;
+    if (lane < 8) R.ends[unit_id * 8 + lane] = (uint8_t)end;
+}
+
+template <int NCH, int U, typename T, bool DUAL>
+__global__ __launch_bounds__(kThreads) void embed_mix_routed_kernel(const MixArgs A, const RouteWs R) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_wave[];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const WaveLds W = wave_lds_carve(lds_wave + (size_t)wave * A.wave_lds, 64, A.bpt, DUAL, 0);
+    MixStream<MOT_MIX_SUM, NCH, U, T, DUAL> S(A, W, 0);
+    const int bpt = A.bpt, sv = bpt | 1;
+    const int64_t n_chunks = (A.n_units + kRouteUnits - 1) / kRouteUnits;
+    const int home = blockIdx.x & 7;
+    const int shard = ((blockIdx.x >> 3) * kWaves + wave) % kClaimShards;
+    for (int q = 0; q < 8;) {
+        const int b = (home + q) & 7;
+        const int64_t lo = n_chunks * shard / kClaimShards, hi = n_chunks * (shard + 1) / kClaimShards;
+        uint32_t k = 0;
+        if (lane == 0) k = atomicAdd(R.claim + (b * kClaimShards + shard) * kClaimStride, 1u);
+        const int64_t c = lo + __builtin_amdgcn_readfirstlane(k);
+        if (c >= hi) { ++q; continue; }                   // shard drained: help with the next bucket's
+        // the item's tokens: bucket b of units c * kRouteUnits + g, g < kRouteUnits
+        const int64_t uc = c * kRouteUnits;
+        int nb = 0, sb = 0;
+        if (lane < kRouteUnits && uc + lane < A.n_units) {
+            const uint8_t *e = R.ends + (uc + lane) * 8;
+            sb = b ? e[b - 1] : 0;
+            nb = e[b] - sb;
         }
-        // ---- mix, normalise, store
+        const int incl = wave_scan_add(nb), excl = incl - nb;
+        const int total = __builtin_amdgcn_readlane(incl, kRouteUnits - 1);
+        for (int p0 = 0; p0 < total; p0 += 64) {
+            const int l = p0 + lane;
+            int g = 0;
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int t = tb + u;
-            vec_t a[1][NCH], b[1][NCH];
+            for (int gg = 1; gg < kRouteUnits; ++gg) g = l >= __builtin_amdgcn_readlane(excl, gg) ? gg : g;   // last unit starting at or before l
+            const int ex = __shfl(excl, g, 64), st = __shfl(sb, g, 64);
+            int64_t pos = 0;
+            int tok = 0;
+            if (l < total) {
+                const int64_t u = uc + g;
+                const int64_t row = u / A.units_per_row;
+                pos = row * A.T + (u - row * A.units_per_row) * A.unit + R.offs[u * A.unit + st + (l - ex)];
+                tok = A.tokens[pos];
+                if ((uint64_t)(uint32_t)tok >= (uint64_t)A.ttb_rows) tok = 0;   // as the index pass clamped it (status set there)
+            }
+            S.tokv = tok;
+            S.ntok = min(64, total - p0);
+            S.request(0);
+            if (l < total) {
+                const uint16_t *ia = R.ids + pos * bpt, *ib = R.ids2 + pos * bpt;
+                if ((bpt & 7) == 0) {                   // 16-byte aligned rows of ids
+                    typedef uint16_t u16x8 __attribute__((ext_vector_type(8)));
+                    for (int k = 0; k < bpt; k += 8) {
+                        const u16x8 va = *(const u16x8 *)(ia + k);
+                        u16x8 vb;
+                        if (DUAL) vb = *(const u16x8 *)(ib + k);
 #pragma unroll
-            for (int i = 0; i < NCH; ++i) {
-                a[0][i] = Elem<T>::widen(ar[u][i]);   // lanes past the row end hold a copy of the row's first chunk: kept out of the sums below, never stored
-                if (MODE == MOT_MIX_SUM) {
-                    vec_t v = Elem<T>::widen(br[u][i]);
-                    if (dual) v += Elem<T>::widen(br2[DUAL ? u : 0][i]);  // emb(padded) + emb(pulled), train_gpt.py:378
-                    if (A.norm_byte) v *= A.byte_rnorm[idr[u][i]];
-                    b[0][i] = v;
-                } else if (MODE == MOT_MIX_MEAN) {
-                    b[0][i] = bm[u][i];
+                        for (int e = 0; e < 8; ++e) {
+                            W.ids[lane * sv + k + e] = va[e];
+                            if (DUAL) W.ids2[lane * sv + k + e] = vb[e];
+                        }
+                    }
+                } else {
+                    for (int k = 0; k < bpt; ++k) {
+                        W.ids[lane * sv + k] = ia[k];
+                        if (DUAL) W.ids2[lane * sv + k] = ib[k];
+                    }
                 }
             }
-            if (A.norm_tok) {
-                float ss = 0.f;
-#pragma unroll
-                for (int i = 0; i < NCH; ++i) ss += act[i] ? sumsq(a[0][i]) : 0.f;
-                const float r = rms_scale(wave_sum(ss), Dm, A.eps);
-#pragma unroll
-                for (int i = 0; i < NCH; ++i) a[0][i] *= r;
-            }
-            if (scale_t) {
-#pragma unroll
-                for (int i = 0; i < NCH; ++i) a[0][i] *= s_tok;
-            }
-            vec_t x[NCH];
-#pragma unroll
-            for (int i = 0; i < NCH; ++i) {
-                if (MODE == MOT_MIX_NOOP) x[i] = a[0][i];
-                else x[i] = a[0][i] + (scale_b ? b[0][i] * s_byte : b[0][i]);
-            }
-            if (A.norm_out) {
-                float ss = 0.f;
-#pragma unroll
-                for (int i = 0; i < NCH; ++i) ss += act[i] ? sumsq(x[i]) : 0.f;
-                const float r = rms_scale(wave_sum(ss), Dm, A.eps);
-#pragma unroll
-                for (int i = 0; i < NCH; ++i) x[i] *= r;
-            }
-            if (t < ntok) {
-#pragma unroll
-                for (int i = 0; i < NCH; ++i)
-                    if (act[i]) Elem<T>::storev_nt(orow + (int64_t)t * Dm + VEC * (lane + 64 * i), x[i]);
-            }
+            wave_lds_sync();
+            const int plo = (int)(uint32_t)pos, phi = (int)(pos >> 32);
+            S.run([&](int t) {
+                const int64_t p = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane(phi, t) << 32) |
+                                            (uint32_t)__builtin_amdgcn_readlane(plo, t));
+                return (T *)A.out + p * (int64_t)S.Dm;
+            });
+            wave_lds_sync();                            // this piece's W.ids reads are done before the next piece's writes
         }
     }
 }
@@ -408,15 +580,87 @@ int launch_rows_rnorm(const void *table, int64_t rows, int dim, float eps, float
     return check_launch("rows_rnorm_kernel");
 }
 
+// Tokens per wave.  16 below 131 072 tokens: the shard a GPU gets when config 4 is split over 8 GPUs is 65 536 tokens, and 16 puts
+// 16 waves on every CU there (measured 58.8 us = 86 % of the roofline, 60.4 us with 32); 32 from there on: the index pass over
+// the 64-token window is then shared by twice the tokens (434.6 us at 524 288 tokens against 438.3).
+static int pick_unit(int64_t n_tokens) { return n_tokens >= 131072 ? 32 : 16; }
+
+// The routed SUM forward: byte ids from the token->byte table, no id outputs (the index pass writes them only in the fused
+// kernel), byte ids that fit uint16, and enough tokens.  fp32 tables that fit the 256 MiB Infinity Cache only: measured at
+// 524 288 tokens, bf16 tables took 0.235 ms routed against 0.224, and a 394 MB fp32 table 0.508 / 0.554 ms (FineWeb-shaped /
+// uniform ids) against 0.505 / 0.509.
+static bool sum_routed(const MotEmbedMixDesc &d) {
+    return d.mode == MOT_MIX_SUM && d.id_source == MOT_IDS_FROM_TTB && !d.out_ids_padded && !d.out_ids_pulled && d.bpt > 0 &&
+           d.byte_rows <= 65536 && d.n_rows * d.tokens_per_row >= kRouteMinTokens && d.dtype == MOT_F32 &&
+           (uint64_t)d.tok_rows * d.tok_dim * sizeof(float) <= ((uint64_t)256 << 20);
+}
+
+// workspace: [byte_rnorm (norm_byte)] [routed path: claim | ends | offs | ids | ids2], each part 256-byte aligned
+struct MixWorkspace {
+    size_t rnorm, claim, ends, offs, ids, ids2, total;
+};
+static MixWorkspace mix_workspace(const MotEmbedMixDesc &d) {
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    MixWorkspace w{};
+    w.total = (d.mode != MOT_MIX_NOOP && d.norm_byte) ? up((size_t)d.byte_rows * sizeof(float)) : 0;
+    if (!sum_routed(d)) return w;
+    const int64_t tokens = d.n_rows * d.tokens_per_row;
+    const int unit = pick_unit(tokens);
+    const int64_t n_units = d.n_rows * ((d.tokens_per_row + unit - 1) / unit);
+    const size_t id_bytes = up((size_t)tokens * d.bpt * sizeof(uint16_t));
+    w.claim = w.total;
+    w.ends = w.claim + (size_t)8 * kClaimShards * kClaimStride * sizeof(uint32_t);
+    w.offs = w.ends + up((size_t)n_units * 8);
+    w.ids = w.offs + up((size_t)n_units * unit);
+    w.ids2 = w.ids + id_bytes;
+    w.total = w.ids2 + (d.add_padded ? id_bytes : 0);
+    return w;
+}
+
 size_t embed_mix_workspace_bytes(const MotEmbedMixDesc &d) {
     if (d.mode == MOT_MIX_CONCAT_LINEAR) return d.dtype == MOT_BF16 ? embed_mix_linear_bf16_workspace_bytes(d) : embed_mix_linear_workspace_bytes(d);
-    if (d.mode != MOT_MIX_NOOP && d.norm_byte) return (size_t)d.byte_rows * sizeof(float);
-    return 0;
+    return mix_workspace(d).total;
+}
+
+template <int DIR, typename E>
+static void launch_route_index(const MixArgs &A, const RouteWs &R, int64_t blocks, size_t lds, hipStream_t stream) {
+    hipLaunchKernelGGL((route_index_kernel<DIR, E>), dim3((unsigned)blocks), dim3(kThreads), lds, stream, A, R);
+}
+
+// the routed SUM forward: index pre-pass over the fused kernel's units, then the persistent streaming kernel
+template <int NCH, int U, typename T, bool DUAL>
+static int launch_routed(const MixArgs &A, const RouteWs &R, int64_t blocks, size_t lds, hipStream_t stream) {
+    if (A.ttb_elem == 2) {
+        if (A.pull_dir == kPullLeft) launch_route_index<kPullLeft, int16_t>(A, R, blocks, lds, stream);
+        else if (A.pull_dir == kPullRight) launch_route_index<kPullRight, int16_t>(A, R, blocks, lds, stream);
+        else launch_route_index<kPullNone, int16_t>(A, R, blocks, lds, stream);
+    } else {
+        if (A.pull_dir == kPullLeft) launch_route_index<kPullLeft, int32_t>(A, R, blocks, lds, stream);
+        else if (A.pull_dir == kPullRight) launch_route_index<kPullRight, int32_t>(A, R, blocks, lds, stream);
+        else launch_route_index<kPullNone, int32_t>(A, R, blocks, lds, stream);
+    }
+    if (int rc = check_launch("route_index_kernel")) return rc;
+    MixArgs Ar = A;
+    Ar.wave_lds = (int)wave_lds_bytes(64, A.bpt, DUAL, 0);
+    const size_t lds_r = (size_t)Ar.wave_lds * kWaves;
+    // persistent grid: the resident workgroups, a multiple of 8 so that every bucket has its share of them, and at least enough
+    // waves to start on every claim shard (more than resident is only slower, never wrong)
+    const void *kern = (const void *)embed_mix_routed_kernel<NCH, U, T, DUAL>;
+    int dev = 0, cus = 0, per_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kThreads, lds_r) != hipSuccess || per_cu < 1)
+        return set_error(MOT_EHIP, "embed_mix: no occupancy for embed_mix_routed_kernel");
+    const int64_t grid = std::max<int64_t>(((int64_t)cus * per_cu) & ~(int64_t)7, 8 * kClaimShards / kWaves);
+    hipLaunchKernelGGL((embed_mix_routed_kernel<NCH, U, T, DUAL>), dim3((unsigned)grid), dim3(kThreads), lds_r, stream, Ar, R);
+    return check_launch("embed_mix_routed_kernel");
 }
 
 template <int MODE, int NCH, int U, typename T>
-static int launch_mix(const MixArgs &A, int64_t blocks, size_t lds, hipStream_t stream) {
+static int launch_mix(const MixArgs &A, int64_t blocks, size_t lds, hipStream_t stream, const RouteWs *route) {
     const bool dual = MODE != MOT_MIX_NOOP && (A.id_source == MOT_IDS_FROM_TTB ? A.add_padded != 0 : A.ids_b != nullptr);
+    if constexpr (MODE == MOT_MIX_SUM && sizeof(T) == 4) {
+        if (route) return dual ? launch_routed<NCH, U, T, true>(A, *route, blocks, lds, stream) : launch_routed<NCH, U, T, false>(A, *route, blocks, lds, stream);
+    }
     if (dual)
         hipLaunchKernelGGL((embed_mix_kernel<MODE, NCH, U, T, true>), dim3((unsigned)blocks), dim3(kThreads), lds, stream, A);
     else
@@ -426,25 +670,25 @@ static int launch_mix(const MixArgs &A, int64_t blocks, size_t lds, hipStream_t 
 
 // NCH = 16-byte chunks per lane: ceil(D / (64 * VEC)).  U keeps ~12 independent 16 B loads per lane in flight.
 template <int MODE>
-static int dispatch_nch(const MixArgs &A, int dtype, int64_t blocks, size_t lds, hipStream_t stream) {
+static int dispatch_nch(const MixArgs &A, int dtype, int64_t blocks, size_t lds, hipStream_t stream, const RouteWs *route = nullptr) {
     if (dtype == MOT_BF16) {
         switch ((A.Dt / 8 + 63) / 64) {
-            case 1: return launch_mix<MODE, 1, 4, __bf16>(A, blocks, lds, stream);
-            case 2: return launch_mix<MODE, 2, 4, __bf16>(A, blocks, lds, stream);
-            case 3: return launch_mix<MODE, 3, 2, __bf16>(A, blocks, lds, stream);
-            case 4: return launch_mix<MODE, 4, 2, __bf16>(A, blocks, lds, stream);
+            case 1: return launch_mix<MODE, 1, 4, __bf16>(A, blocks, lds, stream, route);
+            case 2: return launch_mix<MODE, 2, 4, __bf16>(A, blocks, lds, stream, route);
+            case 3: return launch_mix<MODE, 3, 2, __bf16>(A, blocks, lds, stream, route);
+            case 4: return launch_mix<MODE, 4, 2, __bf16>(A, blocks, lds, stream, route);
             default: return set_error(MOT_EUNSUPPORTED, "embed_mix: model_dim %d > 2048 is not built", A.Dt);
         }
     }
     switch ((A.Dt / 4 + 63) / 64) {
-        case 1: return launch_mix<MODE, 1, 4, float>(A, blocks, lds, stream);
-        case 2: return launch_mix<MODE, 2, 4, float>(A, blocks, lds, stream);
-        case 3: return launch_mix<MODE, 3, 2, float>(A, blocks, lds, stream);
-        case 4: return launch_mix<MODE, 4, 2, float>(A, blocks, lds, stream);
+        case 1: return launch_mix<MODE, 1, 4, float>(A, blocks, lds, stream, route);
+        case 2: return launch_mix<MODE, 2, 4, float>(A, blocks, lds, stream, route);
+        case 3: return launch_mix<MODE, 3, 2, float>(A, blocks, lds, stream, route);
+        case 4: return launch_mix<MODE, 4, 2, float>(A, blocks, lds, stream, route);
         case 5:
-        case 6: return launch_mix<MODE, 6, 1, float>(A, blocks, lds, stream);
+        case 6: return launch_mix<MODE, 6, 1, float>(A, blocks, lds, stream, route);
         case 7:
-        case 8: return launch_mix<MODE, 8, 1, float>(A, blocks, lds, stream);
+        case 8: return launch_mix<MODE, 8, 1, float>(A, blocks, lds, stream, route);
         default: return set_error(MOT_EUNSUPPORTED, "embed_mix: model_dim %d > 2048 is not built", A.Dt);
     }
 }
@@ -666,11 +910,6 @@ static int mean_lds_slice(const MotEmbedMixDesc &d) {
     return chunk;   // one chunk per slice: the most slices, the smallest table image
 }
 
-// Tokens per wave.  16 below 131 072 tokens: the shard a GPU gets when config 4 is split over 8 GPUs is 65 536 tokens, and 16 puts
-// 16 waves on every CU there (measured 58.8 us = 86 % of the roofline, 60.4 us with 32); 32 from there on: the index pass over
-// the 64-token window is then shared by twice the tokens (434.6 us at 524 288 tokens against 438.3).
-static int pick_unit(int64_t n_tokens) { return n_tokens >= 131072 ? 32 : 16; }
-
 bool embed_mix_mean_takes_add16(const MotEmbedMixDesc &d) { return d.dtype == MOT_F32 && mean_lds_slice(d) != 0; }
 
 int launch_embed_mix(const MotEmbedMixDesc &d, hipStream_t stream, __bf16 *add16, bool add_out) {
@@ -695,11 +934,11 @@ int launch_embed_mix(const MotEmbedMixDesc &d, hipStream_t stream, __bf16 *add16
     A.wave_lds = (int)wave_lds_bytes(A.unit, has_ids ? d.bpt : 0, dual, stream_eb);
     const size_t lds = (size_t)A.wave_lds * kWaves;
 
+    const MixWorkspace ws = mix_workspace(d);
+    if (ws.total && (!d.workspace || d.workspace_bytes < ws.total))
+        return set_error(MOT_EWORKSPACE, "embed_mix: needs %zu workspace bytes, got %zu", ws.total, d.workspace_bytes);
     if (d.mode != MOT_MIX_NOOP && d.norm_byte) {
-        const size_t need = (size_t)d.byte_rows * sizeof(float);
-        if (!d.workspace || d.workspace_bytes < need)
-            return set_error(MOT_EWORKSPACE, "embed_mix: norm_byte needs %zu workspace bytes, got %zu", need, d.workspace_bytes);
-        float *rn = (float *)d.workspace;
+        float *rn = (float *)((unsigned char *)d.workspace + ws.rnorm);
         int rc = launch_rows_rnorm(d.byte_table, d.byte_rows, d.byte_dim, A.eps, rn, d.dtype, stream);
         if (rc) return rc;
         A.byte_rnorm = rn;
@@ -709,7 +948,14 @@ int launch_embed_mix(const MotEmbedMixDesc &d, hipStream_t stream, __bf16 *add16
     }
     switch (d.mode) {
         case MOT_MIX_NOOP: return dispatch_nch<MOT_MIX_NOOP>(A, d.dtype, blocks, lds, stream);
-        case MOT_MIX_SUM: return dispatch_nch<MOT_MIX_SUM>(A, d.dtype, blocks, lds, stream);
+        case MOT_MIX_SUM: {
+            if (sum_routed(d) && A.unit == pick_unit(d.n_rows * d.tokens_per_row)) {
+                unsigned char *w = (unsigned char *)d.workspace;
+                const RouteWs R{(uint32_t *)(w + ws.claim), w + ws.ends, w + ws.offs, (uint16_t *)(w + ws.ids), (uint16_t *)(w + ws.ids2)};
+                return dispatch_nch<MOT_MIX_SUM>(A, d.dtype, blocks, lds, stream, &R);
+            }
+            return dispatch_nch<MOT_MIX_SUM>(A, d.dtype, blocks, lds, stream);
+        }
         case MOT_MIX_MEAN: return dispatch_nch<MOT_MIX_MEAN>(A, d.dtype, blocks, lds, stream);
         default: return set_error(MOT_EINVAL, "embed_mix: bad mode %d", d.mode);
     }

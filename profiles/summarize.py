@@ -5,8 +5,9 @@ usage: python profiles/summarize.py <tag> <kernel-trace dir> [<fetch pmc dir> <w
 
 Writes profiles/<tag>_kernel_stats.csv (rocprofv3 --kernel-trace --stats summary, kernel names cut
 to 100 chars), profiles/<tag>_pmc.json (per-kernel mean FETCH_SIZE / WRITE_SIZE in KB as reported),
-and updates profiles/traffic.json[key] = HBM bytes per launch of the dominant mot:: kernel:
-    2 * FETCH_SIZE * 1024 + WRITE_SIZE * 1024
+and updates profiles/traffic.json[key] = HBM bytes per call, summed over the mot:: kernels of one call (those launched as often
+as the dominant one: the routed SUM forward is an index pre-pass plus the streaming kernel):
+    sum over those kernels of 2 * FETCH_SIZE * 1024 + WRITE_SIZE * 1024
 (MI355X_MICROARCH.md, HBM: on gfx950 FETCH_SIZE reports exactly half the bytes of a 16 B/lane
 coalesced read stream; WRITE_SIZE is exact for 16 B/lane streaming stores; separate --pmc passes).
 """
@@ -43,11 +44,14 @@ def main():
                          for k, v in agg.items() if k.startswith(("void mot::", "mot::", "_ZN3mot"))}   # (kernels with __bf16 template arguments come out mangled)
         (HERE / f"{tag}_pmc.json").write_text(json.dumps(pmc, indent=1) + "\n")
         kern = max(pmc["WRITE_SIZE"], key=lambda k: pmc["WRITE_SIZE"][k]["mean_KB"])
-        fetch, write = pmc["FETCH_SIZE"][kern]["mean_KB"], pmc["WRITE_SIZE"][kern]["mean_KB"]
+        calls = pmc["WRITE_SIZE"][kern]["launches"]
+        kerns = [k for k in pmc["WRITE_SIZE"] if pmc["WRITE_SIZE"][k]["launches"] == calls and k in pmc["FETCH_SIZE"]]
+        fetch = sum(pmc["FETCH_SIZE"][k]["mean_KB"] for k in kerns)
+        write = sum(pmc["WRITE_SIZE"][k]["mean_KB"] for k in kerns)
         tfile = HERE / "traffic.json"
         t = json.loads(tfile.read_text()) if tfile.exists() else {}
         t[key] = int(2 * fetch * 1024 + write * 1024)
-        t[key + "_detail"] = {"kernel": kern, "FETCH_SIZE_KB": fetch, "WRITE_SIZE_KB": write,
+        t[key + "_detail"] = {"kernel": kern, "kernels": kerns, "FETCH_SIZE_KB": fetch, "WRITE_SIZE_KB": write,
                               "fetch_bytes_corrected_x2": int(2 * fetch * 1024), "write_bytes": int(write * 1024),
                               "profile": f"profiles/{tag}_pmc.json",
                               # bench.py refuses the figure once the kernel's sources differ from what was profiled
