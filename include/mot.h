@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MOT_ABI_VERSION 12
+#define MOT_ABI_VERSION 13
 #define MOT_MAX_BPT 64 /* bytes (characters) per token; the reference uses 3, 8, 16, 18, 20, 32 */
 
 typedef void *mot_stream_t; /* hipStream_t */
@@ -49,6 +49,7 @@ typedef enum MotStatus {
  * never fault -- the host shim turns a non-zero word into the reference's IndexError. */
 #define MOT_STATUS_TOKEN_OOR 1u /* token id outside [0, tok_rows) / [0, ttb_rows) */
 #define MOT_STATUS_BYTE_OOR 2u  /* byte id outside [0, byte_rows)                 */
+#define MOT_STATUS_TARGET_OOR 4u /* byte target outside [0, vocab) (mot_byte_head_*) */
 
 typedef enum MotPullDir {
     MOT_PULL_NONE = 0,
@@ -439,6 +440,53 @@ typedef struct MotCharSwaDesc {
 size_t mot_char_swa_desc_size(void);
 size_t mot_char_swa_workspace_bytes(const MotCharSwaDesc *desc /* host */);
 int mot_char_swa_fwd(const MotCharSwaDesc *desc /* host */, mot_stream_t stream);
+
+/*
+ * Byte output head of a mixout run with identity ByteSelfAttn layers (use_byte_self_attn off), forward: replaces
+ *   ByteMixoutCopy / ByteMixoutSplit.forward          scaled-pre-train/train_gpt.py:483-527 (ByteSelfAttn identity, 382-419)
+ *   and the head of GPT.forward                       :618-623  (x = byte_mixout(x); norm; lm_head; 30 sigmoid(l / 7.5); cross_entropy)
+ * Rows: copy = the token rows of x [n_tokens, model_dim] (every byte row of a token is the same row); split = the byte rows of x
+ * viewed as [n_tokens * bpt, model_dim / bpt].  Per row, h <- h + norm(h) n_layer_out times, then l = norm(h) W^T, z = 30 sigmoid(l / 7.5);
+ * the loss is the mean over all M = n_tokens * bpt targets of lse(z) - z[y] (no ignore_index), written as one fp32 scalar; the sum runs
+ * in a fixed order, so the same inputs give the same bits.  A target outside [0, vocab) addresses nothing: its term leaves the sum
+ * (the mean still divides by M) and MOT_STATUS_TARGET_OOR is ORed into `status`.
+ * dtype follows x: MOT_F32, or MOT_BF16 with `weight` already cast to bf16 (CastedLinear, train_gpt.py:185-186): the products run on
+ * the bf16 MFMA with fp32 accumulation, the epilogue and the loss in fp32.  vocab must be 512 (next_multiple_of_n(458, n=128), :574);
+ * the row width K (model_dim, or model_dim / bpt in split mode) a multiple of 16 and at most 2048.  Checked before any HIP call:
+ * an unknown method, dtype, vocab or row width returns MOT_EUNSUPPORTED, a shape the reference asserts on MOT_ESHAPE.
+ */
+typedef enum MotByteHeadMethod { MOT_HEAD_COPY = 0, MOT_HEAD_SPLIT = 1 } MotByteHeadMethod;
+
+typedef struct MotByteHeadDesc {
+    uint32_t struct_size; /* sizeof(MotByteHeadDesc) */
+    int32_t method;       /* MotByteHeadMethod */
+    int32_t dtype;        /* MotDType of x and weight */
+    int32_t bpt;          /* bytes per token */
+    int64_t n_tokens;     /* B * T */
+    int32_t model_dim;    /* columns of x */
+    int32_t n_layer_out;  /* identity mixout layers, h <- h + norm(h) */
+    int32_t vocab;        /* rows of weight: 512 */
+    float eps;            /* of every norm; <= 0 -> FLT_EPSILON: F.rms_norm(eps=None) takes the epsilon of its fp32 opmath type,
+                             on bf16 inputs too (checked against the reference's bf16 outputs) */
+    const void *x;        /* [n_tokens, model_dim], 16-byte aligned */
+    const void *weight;   /* [vocab, K] lm_head.weight in dtype, 16-byte aligned */
+    const int64_t *targets; /* [n_tokens * bpt] byte targets, token-major */
+    float *loss;          /* forward: fp32 scalar */
+    float *row_stats;     /* [2 * rows] fp32: the forward writes lse of every row, then its norm factor c; the backward reads them */
+    uint32_t *status;     /* optional, as in MotEmbedMixDesc */
+    void *workspace;      /* >= mot_byte_head_workspace_bytes(desc), for the forward and the backward */
+    size_t workspace_bytes;
+} MotByteHeadDesc;
+
+size_t mot_byte_head_desc_size(void);
+size_t mot_byte_head_workspace_bytes(const MotByteHeadDesc *desc /* host */);
+int mot_byte_head_fwd(const MotByteHeadDesc *desc /* host */, mot_stream_t stream);
+/*
+ * Backward (loss.backward(), train_gpt.py:1319): `desc` as in the forward, with the row_stats it wrote.  grad_loss is a device fp32
+ * scalar (never read on the host, so the pair is hipGraph-capturable).  dx [n_tokens, model_dim] in dtype and dW [vocab, K] fp32 are
+ * OVERWRITTEN.  dx is written once per row (the same bits every run); dW sums products over the rows with fp32 atomics.
+ */
+int mot_byte_head_bwd(const MotByteHeadDesc *desc /* host */, const float *grad_loss, void *dx, float *dW, mot_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -25,13 +25,15 @@ IS_DEV_LIB = _dev_lib is not None
 
 # ---- enums of include/mot.h
 MOT_OK, MOT_EINVAL, MOT_ESHAPE, MOT_EUNSUPPORTED, MOT_EHIP, MOT_EWORKSPACE = 0, -1, -2, -3, -4, -5
-STATUS_TOKEN_OOR, STATUS_BYTE_OOR = 1, 2
+STATUS_TOKEN_OOR, STATUS_BYTE_OOR, STATUS_TARGET_OOR = 1, 2, 4
 PULL_NONE, PULL_LEFT, PULL_RIGHT = 0, 1, 2
 MIX_NOOP, MIX_SUM, MIX_MEAN, MIX_CONCAT_LINEAR = 0, 1, 2, 3
 IDS_NONE, IDS_FROM_TTB, IDS_GIVEN = 0, 1, 2
 F32, BF16 = 0, 1
 MAX_BPT = 64
-ABI_VERSION = 12
+ABI_VERSION = 13
+HEAD_COPY, HEAD_SPLIT = 0, 1
+HEAD_VOCAB = 512
 FLAG_LINEAR_ONE_LAUNCH, FLAG_MEAN_GENERIC, FLAG_BWD_DU_FP32, FLAG_LINEAR_COMPOSED = 1, 2, 4, 8
 HEADS_AS_VIEWED, HEADS_PER_TOKEN = 0, 1
 
@@ -50,6 +52,7 @@ EXPORTS = (
     "mot_cross_attn_desc_size", "mot_cross_attn_workspace_bytes", "mot_cross_attn_fwd",
     "mot_cross_attn_bwd_workspace_bytes", "mot_cross_attn_bwd",
     "mot_char_swa_desc_size", "mot_char_swa_workspace_bytes", "mot_char_swa_fwd",
+    "mot_byte_head_desc_size", "mot_byte_head_workspace_bytes", "mot_byte_head_fwd", "mot_byte_head_bwd",
 )
 SWA_NO_RESIDUAL, SWA_ONE_RESIDUAL, SWA_TWO_RESIDUAL = 0, 1, 2
 
@@ -123,6 +126,16 @@ class MotCharSwaDesc(C.Structure):
     ]
 
 
+class MotByteHeadDesc(C.Structure):
+    """Mirror of struct MotByteHeadDesc (include/mot.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("method", C.c_int32), ("dtype", C.c_int32), ("bpt", C.c_int32), ("n_tokens", C.c_int64),
+        ("model_dim", C.c_int32), ("n_layer_out", C.c_int32), ("vocab", C.c_int32), ("eps", C.c_float),
+        ("x", C.c_void_p), ("weight", C.c_void_p), ("targets", C.c_void_p), ("loss", C.c_void_p), ("row_stats", C.c_void_p),
+        ("status", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
 def _load() -> C.CDLL:
     if not LIB_PATH.exists():
         raise ImportError(
@@ -162,6 +175,13 @@ def _load() -> C.CDLL:
     lib.mot_char_swa_workspace_bytes.argtypes = [C.POINTER(MotCharSwaDesc)]
     lib.mot_char_swa_fwd.argtypes = [C.POINTER(MotCharSwaDesc), vp]
     lib.mot_char_swa_fwd.restype = C.c_int
+    lib.mot_byte_head_desc_size.restype = C.c_size_t
+    lib.mot_byte_head_workspace_bytes.restype = C.c_size_t
+    lib.mot_byte_head_workspace_bytes.argtypes = [C.POINTER(MotByteHeadDesc)]
+    lib.mot_byte_head_fwd.argtypes = [C.POINTER(MotByteHeadDesc), vp]
+    lib.mot_byte_head_fwd.restype = C.c_int
+    lib.mot_byte_head_bwd.argtypes = [C.POINTER(MotByteHeadDesc), vp, vp, vp, vp]
+    lib.mot_byte_head_bwd.restype = C.c_int
     for name in ("mot_tokens_to_bytes", "mot_pull_bytes", "mot_create_batch", "mot_char_matrix", "mot_gather_rows", "mot_embed_mix_fwd",
                  "mot_embed_mix_bwd"):
         getattr(lib, name).restype = C.c_int
@@ -173,6 +193,8 @@ def _load() -> C.CDLL:
         raise ImportError("MotCharSwaDesc layout mismatch between include/mot.h and _capi.py")
     if lib.mot_cross_attn_desc_size() != C.sizeof(MotCrossAttnDesc):
         raise ImportError("MotCrossAttnDesc layout mismatch between include/mot.h and _capi.py")
+    if lib.mot_byte_head_desc_size() != C.sizeof(MotByteHeadDesc):
+        raise ImportError("MotByteHeadDesc layout mismatch between include/mot.h and _capi.py")
     return lib
 
 
@@ -223,7 +245,8 @@ def check_status(device=None) -> None:
         v = int(w.item())
         if v:
             w.zero_()
-            what = [n for bit, n in ((STATUS_TOKEN_OOR, "token id"), (STATUS_BYTE_OOR, "byte id")) if v & bit]
+            what = [n for bit, n in ((STATUS_TOKEN_OOR, "token id"), (STATUS_BYTE_OOR, "byte id"), (STATUS_TARGET_OOR, "byte target"))
+                    if v & bit]
             raise IndexError(f"index out of range in self ({' and '.join(what)} out of range)")
 
 

@@ -326,4 +326,23 @@ int mot_cross_attn_bwd(const MotCrossAttnDesc *desc, const MotCrossAttnGrads *gr
     return launch_cross_attn_bwd(d, *grads, (hipStream_t)stream);
 }
 
+size_t mot_byte_head_desc_size(void) { return sizeof(MotByteHeadDesc); }
+
+size_t mot_byte_head_workspace_bytes(const MotByteHeadDesc *desc) {
+    if (byte_head_check(desc)) return 0;
+    return byte_head_workspace_bytes(*desc);
+}
+
+int mot_byte_head_fwd(const MotByteHeadDesc *desc, mot_stream_t stream) {
+    int rc = byte_head_check(desc);
+    if (rc) return rc;
+    return launch_byte_head_fwd(*desc, (hipStream_t)stream);
+}
+
+int mot_byte_head_bwd(const MotByteHeadDesc *desc, const float *grad_loss, void *dx, float *dW, mot_stream_t stream) {
+    int rc = byte_head_check(desc);
+    if (rc) return rc;
+    return launch_byte_head_bwd(*desc, grad_loss, dx, dW, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -98,5 +98,10 @@ size_t char_swa_workspace_bytes(const MotCharSwaDesc &d);
 int launch_char_swa(const MotCharSwaDesc &d, hipStream_t stream);
 size_t cross_attn_workspace_bytes(const MotCrossAttnDesc &d);
 int launch_cross_attn(const MotCrossAttnDesc &d, hipStream_t stream);
+// the byte output head (mot_head.hip): validation before any HIP call, then the launches
+int byte_head_check(const MotByteHeadDesc *d);
+size_t byte_head_workspace_bytes(const MotByteHeadDesc &d);
+int launch_byte_head_fwd(const MotByteHeadDesc &d, hipStream_t stream);
+int launch_byte_head_bwd(const MotByteHeadDesc &d, const float *grad_loss, void *dx, float *dW, hipStream_t stream);
 
 }  // namespace mot

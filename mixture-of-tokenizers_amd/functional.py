@@ -858,3 +858,80 @@ def char_swa(tokens: torch.Tensor, char_ids: torch.Tensor, tok_table: torch.Tens
     capi.check(capi.lib.mot_char_swa_fwd(C.byref(d), capi.stream_of(dev)))
     capi.after_call(dev)
     return out.to(torch.bfloat16) if bf else out
+
+
+# ----------------------------------------------------------------------------------------------
+# byte output head: mixout (identity layers) + norm + lm_head + softcap + cross-entropy, train_gpt.py:618-623
+# ----------------------------------------------------------------------------------------------
+_HEAD_METHODS = {"copy": capi.HEAD_COPY, "split": capi.HEAD_SPLIT}
+
+
+def _byte_head_desc(x, w, targets, method, bpt, n_layer_out, row_stats, loss):
+    if method not in _HEAD_METHODS:
+        raise ValueError(f"byte_head_loss: method must be 'copy' or 'split', got {method!r}")
+    dev = capi.require_device(x, w, targets)
+    d = capi.MotByteHeadDesc()
+    d.struct_size = C.sizeof(capi.MotByteHeadDesc)
+    d.method, d.dtype, d.bpt = _HEAD_METHODS[method], capi.dtype_code(x.dtype), int(bpt)
+    d.n_tokens, d.model_dim, d.n_layer_out, d.vocab, d.eps = x.shape[0], x.shape[1], int(n_layer_out), w.shape[0], 0.0
+    d.x, d.weight, d.targets, d.loss, d.row_stats = capi.ptr(x), capi.ptr(w), capi.ptr(targets), capi.ptr(loss), capi.ptr(row_stats)
+    d.status = capi.ptr(capi.status_word(dev))
+    ws = _workspace(dev, capi.lib.mot_byte_head_workspace_bytes(C.byref(d)))
+    if ws is not None:
+        d.workspace, d.workspace_bytes = capi.ptr(ws), ws.numel()
+    return d, dev
+
+
+def _byte_head_operands(x, weight, targets, bpt):
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"byte_head_loss: x must be float32 or bfloat16, got {x.dtype}")
+    D = x.shape[-1]
+    x2 = _contig(x.detach().reshape(-1, D), x.dtype, "x")
+    w = _contig(weight.detach().to(x2.dtype), x2.dtype, "weight")   # CastedLinear: the weight in x's dtype (train_gpt.py:185-186)
+    t = _contig(targets.reshape(-1), torch.int64, "targets")
+    if t.numel() != x2.shape[0] * bpt:
+        raise ValueError(f"byte_head_loss: {t.numel()} targets for {x2.shape[0]} tokens x {bpt} bytes")
+    if w.ndim != 2:
+        raise ValueError("byte_head_loss: weight must be (vocab, in_features)")
+    return x2, w, t
+
+
+class _ByteHeadFn(torch.autograd.Function):
+    """forward = mot_byte_head_fwd (the loss and the per-row lse / norm factor), backward = mot_byte_head_bwd (dx, fp32 dW)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, targets, method, bpt, n_layer_out):
+        x2, w, t = _byte_head_operands(x, weight, targets, bpt)
+        rows = x2.shape[0] * (bpt if method == "split" else 1)
+        row_stats = torch.empty(2 * rows, dtype=torch.float32, device=x2.device)
+        loss = torch.empty((), dtype=torch.float32, device=x2.device)
+        d, dev = _byte_head_desc(x2, w, t, method, bpt, n_layer_out, row_stats, loss)
+        capi.check(capi.lib.mot_byte_head_fwd(C.byref(d), capi.stream_of(dev)))
+        capi.after_call(dev)
+        ctx.save_for_backward(x2, w, t, row_stats)
+        ctx.cfg = (method, bpt, n_layer_out, x.shape, weight.dtype)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        x2, w, t, row_stats = ctx.saved_tensors
+        method, bpt, n_layer_out, xshape, wdtype = ctx.cfg
+        d, dev = _byte_head_desc(x2, w, t, method, bpt, n_layer_out, row_stats, None)
+        go = _contig(grad_loss.detach().reshape(()).float(), torch.float32, "grad_loss")
+        dx = torch.empty_like(x2)
+        dw = torch.empty(w.shape, dtype=torch.float32, device=dev)
+        capi.check(capi.lib.mot_byte_head_bwd(C.byref(d), capi.ptr(go), capi.ptr(dx), capi.ptr(dw), capi.stream_of(dev)))
+        capi.after_call(dev)
+        return dx.reshape(xshape), dw.to(wdtype), None, None, None, None
+
+
+@torch.compiler.disable
+def byte_head_loss(x: torch.Tensor, weight: torch.Tensor, targets: torch.Tensor, *, method: str, bytes_per_token: int,
+                   n_layer_out: int = 0) -> torch.Tensor:
+    """The byte output head of a mixout run with identity layers (use_byte_self_attn off), train_gpt.py:618-623:
+    h = repeat (copy) or rearrange (split) of x into byte rows; h = h + norm(h) n_layer_out times; logits = norm(h) @ weight.T;
+    z = 30 sigmoid(logits.float() / 7.5); returns cross_entropy(z, targets) (mean over all n_tokens * bytes_per_token targets) as an
+    fp32 scalar.  x (..., model_dim) float32 or bfloat16; weight (512, model_dim or model_dim / bpt), cast to x's dtype as CastedLinear
+    does; targets int64 (..., T * bpt).  Differentiable in x and weight (the weight's gradient in the weight's dtype).
+    A target outside [0, 512) raises the status bit that check_status() reports; its term is left out of the sum."""
+    return _ByteHeadFn.apply(x, weight, targets, method, int(bytes_per_token), int(n_layer_out))

@@ -5,7 +5,7 @@ work done by the fused HIP kernels.
 scaled-pre-train (train_gpt.py):  ByteHyperparameters, ModelDims (146-169), norm (172-173),
     CastedLinear (175-186), FlexibleEmbedding (327-379), ByteMixinNoop / ByteMixinConcat /
     ByteMixin (421-443, 467-480); call site ``xt, xb = self.embed(...); x = self.byte_mixin(xt, xb)``
-    (605-606) works unchanged.
+    (605-606) works unchanged; ByteMixout (483-542, identity layers) with ``loss()``, the fused byte head of 618-623.
 mathblations (model.py):  GPTConfig (16-29), DigitMixinConcat / DigitMixinNoOp / make_digit_mixin
     (256-284), and the ``wte`` / ``dte`` / ``digit_mixin`` triple of GPT (304-306, 323-327).
 modded-nanogpt (runs/71*.py):  the SUM mixin ``norm(embed_tokens(tok) + concat_k embed_bytes(b_k))``
@@ -321,6 +321,67 @@ class ByteMixin(nn.Module):  # train_gpt.py:467-480
 
     def forward(self, tok_embs, byte_embs=None) -> Tensor:
         return self.mixin(tok_embs, byte_embs)
+
+
+class _IdentityByteSelfAttn(nn.Module):  # train_gpt.py:382-419 with use_byte_self_attn off: the layer returns its input
+    def __init__(self):
+        super().__init__()
+        self.attention = nn.Identity()
+
+    def forward(self, byte_embs: Tensor) -> Tensor:
+        return byte_embs
+
+
+class _ByteMixoutRows(nn.Module):  # ByteMixoutCopy / ByteMixoutSplit, train_gpt.py:483-527
+    def __init__(self, method: str, dims: ModelDims, byte_params: ByteHyperparameters):
+        super().__init__()
+        if method == "split":
+            assert dims.model_dim % byte_params.bytes_per_token == 0
+        self.method = method
+        self.attention_layers = nn.ModuleList([_IdentityByteSelfAttn() for _ in range(byte_params.n_layer_out)])
+        self.bpt = byte_params.bytes_per_token
+
+    def forward(self, x: Tensor) -> Tensor:
+        if self.method == "copy":   # einops.repeat "... T D -> ... (T bpt) D"
+            x = x.repeat_interleave(self.bpt, dim=-2)
+        else:                       # einops.rearrange "... T (bpt D) -> ... (T bpt) D"
+            x = x.reshape(*x.shape[:-2], x.shape[-2] * self.bpt, x.shape[-1] // self.bpt)
+        for layer in self.attention_layers:
+            x = x + layer(norm(x))
+        return x
+
+
+class _ByteMixoutNoop(nn.Module):  # train_gpt.py:530-535
+    def forward(self, x: Tensor) -> Tensor:
+        return x
+
+
+class ByteMixout(nn.Module):  # train_gpt.py:530-542
+    """The reference's ByteMixout with identity ByteSelfAttn layers (the only kind its runs build at the output).
+    forward(x) returns the byte-level states in plain torch ops, so an unmodified GPT.forward still works;
+    loss(x, lm_head, target_seq) is the fused head, one mot_byte_head_fwd / _bwd pair in place of train_gpt.py:618-623."""
+
+    def __init__(self, dims: ModelDims, max_seq_len: int, byte_params: ByteHyperparameters):
+        super().__init__()
+        method = byte_params.byte_mixout_method
+        if method not in ("noop", "copy", "split"):
+            raise ValueError(f"byte_mixout_method {method!r}")
+        if method != "noop" and byte_params.use_byte_self_attn:
+            raise NotImplementedError("use_byte_self_attn at the output (ByteSelfAttn, train_gpt.py:382-419) is not built: "
+                                      "only identity mixout layers are")
+        self.method = method
+        self.n_layer_out = byte_params.n_layer_out if method != "noop" else 0
+        self.bpt = byte_params.bytes_per_token
+        self.mixout = _ByteMixoutNoop() if method == "noop" else _ByteMixoutRows(method, dims, byte_params)
+
+    def forward(self, x: Tensor) -> Tensor:
+        return self.mixout(x)
+
+    def loss(self, x: Tensor, lm_head: nn.Module, target_seq: Tensor) -> Tensor:
+        """cross_entropy(30 sigmoid(lm_head(norm(self(x))).float() / 7.5), target_seq), fused; x (..., T, model_dim)."""
+        if self.method == "noop":
+            raise NotImplementedError("the token-level head of byte_mixout_method='noop' (vocabulary 50 304) is not part of the byte head")
+        return F_mot.byte_head_loss(x, lm_head.weight, target_seq, method=self.method, bytes_per_token=self.bpt, n_layer_out=self.n_layer_out)
 
 
 class FusedFrontEnd(nn.Module):
