@@ -488,6 +488,66 @@ int mot_byte_head_fwd(const MotByteHeadDesc *desc /* host */, mot_stream_t strea
  */
 int mot_byte_head_bwd(const MotByteHeadDesc *desc /* host */, const float *grad_loss, void *dx, float *dW, mot_stream_t stream);
 
+/*
+ * Byte self-attention in front of the concat mixin, forward: replaces ByteSelfAttn.forward with use_byte_self_attn on
+ *   scaled-pre-train/train_gpt.py:382-418 around CausalSelfAttention.forward :226-240 (Rotary 189-206, norm 172-173)
+ * x [n_rows, row_len, dim] are the byte embeddings of n_rows batch rows, row_len = T * bpt byte positions each.
+ *   (q, k, v) = x qkv_w^T per head of 128 columns; q, k <- rms_norm over the head, then rotary with the byte's index in its batch
+ *   row; v <- lambda_v v; p = softmax(0.12 q.k) over the allowed keys; out = x + (sum p v) proj_w^T.
+ * Key j is allowed for query i of the same batch row when i - j < window and j <= i (block_causal = 0) or
+ * j / bpt <= i / bpt (block_causal = 1).  window is in bytes (sliding_window_tokens * bpt), at most 256.
+ * fp32 only; bf16 tensors are the follow-up and return MOT_EUNSUPPORTED.  Asynchronous on `stream`, no host synchronisation.
+ * The forward leaves the raw projections, the attention output and the row statistics in `saved`
+ * (mot_byte_self_attn_saved_bytes: 2052 * n_heads bytes per byte position) for the backward; it needs no workspace, the backward does.
+ */
+typedef struct MotByteSelfAttnDesc {
+    uint32_t struct_size;   /* sizeof(MotByteSelfAttnDesc) */
+    int32_t dtype;          /* MOT_F32 */
+    int64_t n_rows;         /* B */
+    int64_t row_len;        /* L = T * bpt byte positions per batch row */
+    int32_t bpt;            /* bytes per token */
+    int32_t window;         /* bytes: 1 .. 256, a multiple of bpt */
+    int32_t block_causal;   /* mix_byte_in_tok */
+    int32_t dim;            /* columns of x: a multiple of 16, at most 2048 */
+    int32_t n_heads;        /* max(1, dim / 128) */
+    int32_t head_dim;       /* 128 */
+    const void *x;          /* [n_rows * row_len, dim] */
+    const void *qkv_w;      /* [3, n_heads * 128, dim] */
+    const void *proj_w;     /* [dim, n_heads * 128] c_proj.weight */
+    const float *lambda_v;  /* device scalar: lambdas[0] */
+    const float *cos, *sin; /* [rope_rows, 64] Rotary buffers */
+    int64_t rope_rows;      /* >= row_len */
+    float eps;              /* of the q / k norm; <= 0 -> FLT_EPSILON (F.rms_norm(eps=None) on fp32) */
+    int32_t reserved0;      /* must be 0 */
+    void *out;              /* [n_rows * row_len, dim] */
+    void *saved;            /* 16-byte aligned; written by the forward, read by the backward */
+    size_t saved_bytes;
+    uint32_t *status;       /* optional, reserved: nothing in this call raises a status bit */
+    void *workspace;        /* backward only, 16-byte aligned */
+    size_t workspace_bytes;
+} MotByteSelfAttnDesc;
+
+/*
+ * Backward: `fwd` as in the forward, with the `saved` buffer it filled.  Every non-null gradient is OVERWRITTEN.
+ * dx, the gradient of the raw projections and d_lambda are written once per element / summed in a fixed order (the same bits on
+ * every run); d_qkv_w and d_proj_w sum products over all byte positions with fp32 atomics.
+ */
+typedef struct MotByteSelfAttnGrads {
+    uint32_t struct_size;  /* sizeof(MotByteSelfAttnGrads) */
+    uint32_t reserved;
+    const void *grad_out;  /* [n_rows * row_len, dim] */
+    void *dx;              /* [n_rows * row_len, dim] */
+    void *d_qkv_w;         /* [3, n_heads * 128, dim] */
+    void *d_proj_w;        /* [dim, n_heads * 128] */
+    float *d_lambda;       /* scalar */
+} MotByteSelfAttnGrads;
+
+size_t mot_byte_self_attn_desc_size(void);
+size_t mot_byte_self_attn_saved_bytes(const MotByteSelfAttnDesc *desc /* host */);     /* 0 for a descriptor the call would refuse */
+size_t mot_byte_self_attn_workspace_bytes(const MotByteSelfAttnDesc *desc /* host */); /* likewise */
+int mot_byte_self_attn_fwd(const MotByteSelfAttnDesc *desc /* host */, mot_stream_t stream);
+int mot_byte_self_attn_bwd(const MotByteSelfAttnDesc *fwd /* host */, const MotByteSelfAttnGrads *grads /* host */, mot_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,8 @@ Hand-written HIP kernels behind a C ABI (include/mot.h, csrc/), called through c
 Python layer mirrors the reference's interfaces for this path and nothing else:
 
   data_creation   make_embedding / tokens_to_bytes / pull_from_left / pull_from_right / create_batch
-  functional      tensor-level wrappers (embed_mix = the fused gather + mix forward; byte_head_loss = the mixout byte head)
+  functional      tensor-level wrappers (embed_mix = the fused gather + mix forward; byte_head_loss = the mixout byte head;
+                  byte_self_attn = the sliding-window byte self-attention layer of the concat mixin)
   modules         FlexibleEmbedding / ByteMixin* / CastedLinear (scaled-pre-train), DigitMixin* / GPTConfig
                   (mathblations), SumFrontEnd (modded-nanogpt), FusedFrontEnd (tokens -> x in one launch)
   loader          shard reader, rank slice, input/target shift (distributed_data_generator)
@@ -16,9 +17,9 @@ shim at the repo root maps that name onto this directory).
 from . import _capi
 from . import data_creation, functional, grad_sync, loader, modules
 from ._capi import build_info, check_status, set_debug_ids
-from .functional import byte_head_loss, create_batch, embed_mix, embed_mix_plan, gather_rows, pull_bytes, tokens_to_bytes
+from .functional import byte_head_loss, byte_self_attn, create_batch, embed_mix, embed_mix_plan, gather_rows, pull_bytes, tokens_to_bytes
 
 __all__ = [
     "build_info", "check_status", "set_debug_ids", "data_creation", "functional", "grad_sync", "loader", "modules",
-    "byte_head_loss", "create_batch", "embed_mix", "embed_mix_plan", "gather_rows", "pull_bytes", "tokens_to_bytes",
+    "byte_head_loss", "byte_self_attn", "create_batch", "embed_mix", "embed_mix_plan", "gather_rows", "pull_bytes", "tokens_to_bytes",
 ]

@@ -53,6 +53,8 @@ EXPORTS = (
     "mot_cross_attn_bwd_workspace_bytes", "mot_cross_attn_bwd",
     "mot_char_swa_desc_size", "mot_char_swa_workspace_bytes", "mot_char_swa_fwd",
     "mot_byte_head_desc_size", "mot_byte_head_workspace_bytes", "mot_byte_head_fwd", "mot_byte_head_bwd",
+    "mot_byte_self_attn_desc_size", "mot_byte_self_attn_saved_bytes", "mot_byte_self_attn_workspace_bytes",
+    "mot_byte_self_attn_fwd", "mot_byte_self_attn_bwd",
 )
 SWA_NO_RESIDUAL, SWA_ONE_RESIDUAL, SWA_TWO_RESIDUAL = 0, 1, 2
 
@@ -136,6 +138,26 @@ class MotByteHeadDesc(C.Structure):
     ]
 
 
+class MotByteSelfAttnDesc(C.Structure):
+    """Mirror of struct MotByteSelfAttnDesc (include/mot.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("dtype", C.c_int32), ("n_rows", C.c_int64), ("row_len", C.c_int64),
+        ("bpt", C.c_int32), ("window", C.c_int32), ("block_causal", C.c_int32), ("dim", C.c_int32), ("n_heads", C.c_int32),
+        ("head_dim", C.c_int32), ("x", C.c_void_p), ("qkv_w", C.c_void_p), ("proj_w", C.c_void_p), ("lambda_v", C.c_void_p),
+        ("cos", C.c_void_p), ("sin", C.c_void_p), ("rope_rows", C.c_int64), ("eps", C.c_float), ("reserved0", C.c_int32),
+        ("out", C.c_void_p), ("saved", C.c_void_p), ("saved_bytes", C.c_size_t), ("status", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
+class MotByteSelfAttnGrads(C.Structure):
+    """Mirror of struct MotByteSelfAttnGrads (include/mot.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("grad_out", C.c_void_p), ("dx", C.c_void_p),
+        ("d_qkv_w", C.c_void_p), ("d_proj_w", C.c_void_p), ("d_lambda", C.c_void_p),
+    ]
+
+
 def _load() -> C.CDLL:
     if not LIB_PATH.exists():
         raise ImportError(
@@ -182,6 +204,14 @@ def _load() -> C.CDLL:
     lib.mot_byte_head_fwd.restype = C.c_int
     lib.mot_byte_head_bwd.argtypes = [C.POINTER(MotByteHeadDesc), vp, vp, vp, vp]
     lib.mot_byte_head_bwd.restype = C.c_int
+    lib.mot_byte_self_attn_desc_size.restype = C.c_size_t
+    for name in ("mot_byte_self_attn_saved_bytes", "mot_byte_self_attn_workspace_bytes"):
+        getattr(lib, name).restype = C.c_size_t
+        getattr(lib, name).argtypes = [C.POINTER(MotByteSelfAttnDesc)]
+    lib.mot_byte_self_attn_fwd.argtypes = [C.POINTER(MotByteSelfAttnDesc), vp]
+    lib.mot_byte_self_attn_fwd.restype = C.c_int
+    lib.mot_byte_self_attn_bwd.argtypes = [C.POINTER(MotByteSelfAttnDesc), C.POINTER(MotByteSelfAttnGrads), vp]
+    lib.mot_byte_self_attn_bwd.restype = C.c_int
     for name in ("mot_tokens_to_bytes", "mot_pull_bytes", "mot_create_batch", "mot_char_matrix", "mot_gather_rows", "mot_embed_mix_fwd",
                  "mot_embed_mix_bwd"):
         getattr(lib, name).restype = C.c_int
@@ -195,6 +225,8 @@ def _load() -> C.CDLL:
         raise ImportError("MotCrossAttnDesc layout mismatch between include/mot.h and _capi.py")
     if lib.mot_byte_head_desc_size() != C.sizeof(MotByteHeadDesc):
         raise ImportError("MotByteHeadDesc layout mismatch between include/mot.h and _capi.py")
+    if lib.mot_byte_self_attn_desc_size() != C.sizeof(MotByteSelfAttnDesc):
+        raise ImportError("MotByteSelfAttnDesc layout mismatch between include/mot.h and _capi.py")
     return lib
 
 

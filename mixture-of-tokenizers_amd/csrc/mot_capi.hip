@@ -345,4 +345,73 @@ int mot_byte_head_bwd(const MotByteHeadDesc *desc, const float *grad_loss, void 
     return launch_byte_head_bwd(*desc, grad_loss, dx, dW, (hipStream_t)stream);
 }
 
+size_t mot_byte_self_attn_desc_size(void) { return sizeof(MotByteSelfAttnDesc); }
+
+// everything that does not need the pointers: also what the two size queries run
+static int check_byte_self_attn_shape(const MotByteSelfAttnDesc *d) {
+    if (!d) return set_error(MOT_EINVAL, "byte_self_attn: null descriptor");
+    if (d->struct_size != sizeof(MotByteSelfAttnDesc))
+        return set_error(MOT_EINVAL, "byte_self_attn: struct_size %u != %zu (ABI mismatch)", d->struct_size, sizeof(MotByteSelfAttnDesc));
+    if (d->dtype != MOT_F32)
+        return set_error(MOT_EUNSUPPORTED, "byte_self_attn: only MOT_F32 is built (bf16 byte embeddings, the production cast, are the follow-up)");
+    if (d->head_dim != 128) return set_error(MOT_EUNSUPPORTED, "byte_self_attn: head_dim %d (128 is built, train_gpt.py:391)", d->head_dim);
+    if (d->window < 1 || d->window > 256) return set_error(MOT_EUNSUPPORTED, "byte_self_attn: window of %d bytes outside [1, 256]", d->window);
+    if (d->dim < 16 || (d->dim & 15) || d->dim > 2048)
+        return set_error(MOT_EUNSUPPORTED, "byte_self_attn: dim %d must be a multiple of 16 and at most 2048", d->dim);
+    if (d->n_heads != (d->dim / 128 > 1 ? d->dim / 128 : 1))
+        return set_error(MOT_EUNSUPPORTED, "byte_self_attn: n_heads %d != max(1, dim // 128) (train_gpt.py:389)", d->n_heads);
+    if (int rc = check_bpt("byte_self_attn", d->bpt)) return rc;
+    if (d->reserved0) return set_error(MOT_EINVAL, "byte_self_attn: reserved0 %d", d->reserved0);
+    if (d->n_rows < 0 || d->row_len < 0) return set_error(MOT_ESHAPE, "byte_self_attn: negative shape");
+    if (d->row_len % d->bpt) return set_error(MOT_ESHAPE, "byte_self_attn: row_len %lld is not a multiple of bpt %d", (long long)d->row_len, d->bpt);
+    if (d->window % d->bpt) return set_error(MOT_ESHAPE, "byte_self_attn: window %d is not a multiple of bpt %d", d->window, d->bpt);
+    if (d->rope_rows < d->row_len)   /* Rotary.forward's assert, line 200 */
+        return set_error(MOT_ESHAPE, "byte_self_attn: rotary buffers hold %lld positions, need %lld", (long long)d->rope_rows, (long long)d->row_len);
+    if (d->n_rows > 65535 || d->row_len > 0x3fffffffLL || d->n_rows * d->row_len * d->n_heads > 0x7fffffffLL)
+        return set_error(MOT_EUNSUPPORTED, "byte_self_attn: %lld rows of %lld positions are more than one launch takes", (long long)d->n_rows, (long long)d->row_len);
+    return MOT_OK;
+}
+
+static int check_byte_self_attn(const MotByteSelfAttnDesc *d, bool backward) {
+    if (int rc = check_byte_self_attn_shape(d)) return rc;
+    if (d->n_rows == 0 || d->row_len == 0) return MOT_OK;
+    if (!d->x || !d->qkv_w || !d->proj_w || !d->lambda_v || !d->cos || !d->sin || !d->saved || (!backward && !d->out))
+        return set_error(MOT_EINVAL, "byte_self_attn: x/qkv_w/proj_w/lambda_v/cos/sin/out/saved must be non-null");
+    if (((uintptr_t)d->saved & 15) || ((uintptr_t)d->cos & 15) || ((uintptr_t)d->sin & 15))
+        return set_error(MOT_EINVAL, "byte_self_attn: saved / cos / sin must be 16-byte aligned");
+    if (d->saved_bytes < byte_self_attn_saved_bytes(*d))
+        return set_error(MOT_EWORKSPACE, "byte_self_attn: saved buffer of %zu bytes, need %zu", d->saved_bytes, byte_self_attn_saved_bytes(*d));
+    if (backward) {
+        if (!d->workspace || ((uintptr_t)d->workspace & 15)) return set_error(MOT_EINVAL, "byte_self_attn_bwd: workspace missing or not 16-byte aligned");
+        if (d->workspace_bytes < byte_self_attn_workspace_bytes(*d))
+            return set_error(MOT_EWORKSPACE, "byte_self_attn_bwd: workspace of %zu bytes, need %zu", d->workspace_bytes, byte_self_attn_workspace_bytes(*d));
+    }
+    return MOT_OK;
+}
+
+size_t mot_byte_self_attn_saved_bytes(const MotByteSelfAttnDesc *desc) {
+    if (check_byte_self_attn_shape(desc)) return 0;
+    return byte_self_attn_saved_bytes(*desc);
+}
+
+size_t mot_byte_self_attn_workspace_bytes(const MotByteSelfAttnDesc *desc) {
+    if (check_byte_self_attn_shape(desc)) return 0;
+    return byte_self_attn_workspace_bytes(*desc);
+}
+
+int mot_byte_self_attn_fwd(const MotByteSelfAttnDesc *desc, mot_stream_t stream) {
+    if (int rc = check_byte_self_attn(desc, false)) return rc;
+    if (desc->n_rows == 0 || desc->row_len == 0) return MOT_OK;
+    return launch_byte_self_attn_fwd(*desc, (hipStream_t)stream);
+}
+
+int mot_byte_self_attn_bwd(const MotByteSelfAttnDesc *desc, const MotByteSelfAttnGrads *grads, mot_stream_t stream) {
+    if (!grads || grads->struct_size != sizeof(MotByteSelfAttnGrads))
+        return set_error(MOT_EINVAL, "byte_self_attn_bwd: grads struct missing or struct_size mismatch");
+    if (int rc = check_byte_self_attn(desc, true)) return rc;
+    if (desc->n_rows == 0 || desc->row_len == 0) return MOT_OK;
+    if (!grads->grad_out) return set_error(MOT_EINVAL, "byte_self_attn_bwd: grad_out missing");
+    return launch_byte_self_attn_bwd(*desc, *grads, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -103,5 +103,10 @@ int byte_head_check(const MotByteHeadDesc *d);
 size_t byte_head_workspace_bytes(const MotByteHeadDesc &d);
 int launch_byte_head_fwd(const MotByteHeadDesc &d, hipStream_t stream);
 int launch_byte_head_bwd(const MotByteHeadDesc &d, const float *grad_loss, void *dx, float *dW, hipStream_t stream);
+// byte self-attention of the concat mixin (mot_bsa.hip); the descriptor is validated in mot_capi.hip
+size_t byte_self_attn_saved_bytes(const MotByteSelfAttnDesc &d);
+size_t byte_self_attn_workspace_bytes(const MotByteSelfAttnDesc &d);
+int launch_byte_self_attn_fwd(const MotByteSelfAttnDesc &d, hipStream_t stream);
+int launch_byte_self_attn_bwd(const MotByteSelfAttnDesc &d, const MotByteSelfAttnGrads &g, hipStream_t stream);
 
 }  // namespace mot

@@ -935,3 +935,83 @@ def byte_head_loss(x: torch.Tensor, weight: torch.Tensor, targets: torch.Tensor,
     does; targets int64 (..., T * bpt).  Differentiable in x and weight (the weight's gradient in the weight's dtype).
     A target outside [0, 512) raises the status bit that check_status() reports; its term is left out of the sum."""
     return _ByteHeadFn.apply(x, weight, targets, method, int(bytes_per_token), int(n_layer_out))
+
+
+# ----------------------------------------------------------------------------------------------
+# byte self-attention in front of the concat mixin: ByteSelfAttn with use_byte_self_attn, train_gpt.py:382-418
+# ----------------------------------------------------------------------------------------------
+def _byte_self_attn_desc(x3, qkv_w, proj_w, lam, cos, sin, bpt, window, block_causal, out, saved):
+    dev = capi.require_device(x3, qkv_w, proj_w, lam, cos, sin)
+    B, L, D = x3.shape
+    d = capi.MotByteSelfAttnDesc()
+    d.struct_size = C.sizeof(capi.MotByteSelfAttnDesc)
+    d.dtype, d.n_rows, d.row_len, d.bpt, d.window, d.block_causal = capi.F32, B, L, int(bpt), int(window), int(bool(block_causal))
+    d.dim, d.n_heads, d.head_dim = D, qkv_w.shape[1] // 128, 128
+    d.x, d.qkv_w, d.proj_w, d.lambda_v = capi.ptr(x3), capi.ptr(qkv_w), capi.ptr(proj_w), capi.ptr(lam)
+    d.cos, d.sin, d.rope_rows, d.eps = capi.ptr(cos), capi.ptr(sin), cos.shape[0], 0.0
+    d.out, d.status = capi.ptr(out), capi.ptr(capi.status_word(dev))
+    if saved is not None:
+        d.saved, d.saved_bytes = capi.ptr(saved), saved.numel()
+    return d, dev
+
+
+class _ByteSelfAttnFn(torch.autograd.Function):
+    """forward = mot_byte_self_attn_fwd (out, and the saved projections / attention output / row statistics),
+    backward = mot_byte_self_attn_bwd (dx, d qkv_w, d c_proj.weight, d lambdas[0])."""
+
+    @staticmethod
+    def forward(ctx, x, qkv_w, proj_w, lambdas, cos, sin, bpt, window, block_causal):
+        for t, what in ((x, "x"), (qkv_w, "qkv_w"), (proj_w, "proj_w"), (lambdas, "lambdas")):
+            if t.is_cuda and t.dtype != torch.float32:
+                raise NotImplementedError(f"byte_self_attn: {what} is {t.dtype}; only float32 is built (bfloat16 byte embeddings, the "
+                                          "production cast of train_gpt.py:1124-1126, are the follow-up)")
+        capi.require_device(x, qkv_w, proj_w, lambdas, cos, sin)
+        if x.ndim != 3 or qkv_w.ndim != 3 or qkv_w.shape[0] != 3 or qkv_w.shape[2] != x.shape[2] or qkv_w.shape[1] % 128:
+            raise ValueError(f"byte_self_attn: x (B, L, D) and qkv_w (3, heads * 128, D) expected, got {tuple(x.shape)} and {tuple(qkv_w.shape)}")
+        if tuple(proj_w.shape) != (x.shape[2], qkv_w.shape[1]) or lambdas.numel() != 2:
+            raise ValueError("byte_self_attn: proj_w must be (D, heads * 128) and lambdas a 2-vector")
+        x3 = _contig(x.detach(), torch.float32, "x")
+        w, pw = _contig(qkv_w.detach(), torch.float32, "qkv_w"), _contig(proj_w.detach(), torch.float32, "proj_w")
+        lam = _contig(lambdas.detach(), torch.float32, "lambdas")
+        cs, sn = _contig(cos, torch.float32, "cos"), _contig(sin, torch.float32, "sin")
+        out = torch.empty_like(x3)
+        d, dev = _byte_self_attn_desc(x3, w, pw, lam, cs, sn, bpt, window, block_causal, out, None)
+        saved = torch.empty(int(capi.lib.mot_byte_self_attn_saved_bytes(C.byref(d))), dtype=torch.uint8, device=dev)
+        d.saved, d.saved_bytes = capi.ptr(saved), saved.numel()
+        capi.check(capi.lib.mot_byte_self_attn_fwd(C.byref(d), capi.stream_of(dev)))
+        capi.after_call(dev)
+        ctx.save_for_backward(x3, w, pw, lam, cs, sn, saved)
+        ctx.cfg = (bpt, window, block_causal)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x3, w, pw, lam, cs, sn, saved = ctx.saved_tensors
+        bpt, window, block_causal = ctx.cfg
+        d, dev = _byte_self_attn_desc(x3, w, pw, lam, cs, sn, bpt, window, block_causal, None, saved)
+        ws = _workspace(dev, capi.lib.mot_byte_self_attn_workspace_bytes(C.byref(d)))
+        if ws is not None:
+            d.workspace, d.workspace_bytes = capi.ptr(ws), ws.numel()
+        go = _contig(grad_out.detach(), torch.float32, "grad_out")
+        need = ctx.needs_input_grad
+        dx = torch.empty_like(x3) if need[0] else None
+        dw = torch.empty_like(w) if need[1] else None
+        dpw = torch.empty_like(pw) if need[2] else None
+        dlam = torch.zeros(2, dtype=torch.float32, device=dev) if need[3] else None   # lambdas[1] takes no part: its gradient is 0
+        g = capi.MotByteSelfAttnGrads()
+        g.struct_size = C.sizeof(capi.MotByteSelfAttnGrads)
+        g.grad_out, g.dx, g.d_qkv_w, g.d_proj_w, g.d_lambda = capi.ptr(go), capi.ptr(dx), capi.ptr(dw), capi.ptr(dpw), capi.ptr(dlam)
+        capi.check(capi.lib.mot_byte_self_attn_bwd(C.byref(d), C.byref(g), capi.stream_of(dev)))
+        capi.after_call(dev)
+        return dx, dw, dpw, dlam, None, None, None, None, None
+
+
+@torch.compiler.disable
+def byte_self_attn(x: torch.Tensor, qkv_w: torch.Tensor, proj_w: torch.Tensor, lambdas: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, *,
+                   bpt: int, window: int, block_causal: bool = False) -> torch.Tensor:
+    """ByteSelfAttn.forward with use_byte_self_attn (train_gpt.py:382-418): x + CausalSelfAttention(x, None, block_mask) for x (B, L, D),
+    L = T * bpt byte positions per batch row.  qkv_w (3, heads * 128, D), proj_w = c_proj.weight (D, heads * 128), lambdas the module's
+    2-vector (the first entry scales v; the second takes no part and gets a zero gradient), cos / sin the Rotary buffers (>= L, 64).
+    `window` is in bytes (sliding_window_tokens * bpt, at most 256); block_causal = mix_byte_in_tok.  float32; differentiable in x,
+    qkv_w, proj_w and lambdas.  A non-contiguous x is copied."""
+    return _ByteSelfAttnFn.apply(x, qkv_w, proj_w, lambdas, cos, sin, int(bpt), int(window), bool(block_causal))

@@ -4,7 +4,7 @@ work done by the fused HIP kernels.
 
 scaled-pre-train (train_gpt.py):  ByteHyperparameters, ModelDims (146-169), norm (172-173),
     CastedLinear (175-186), FlexibleEmbedding (327-379), ByteMixinNoop / ByteMixinConcat /
-    ByteMixin (421-443, 467-480); call site ``xt, xb = self.embed(...); x = self.byte_mixin(xt, xb)``
+    ByteMixin (421-443, 467-480), CausalSelfAttention / ByteSelfAttn as the concat mixin uses them (209-240, 382-418); call site ``xt, xb = self.embed(...); x = self.byte_mixin(xt, xb)``
     (605-606) works unchanged; ByteMixout (483-542, identity layers) with ``loss()``, the fused byte head of 618-623.
 mathblations (model.py):  GPTConfig (16-29), DigitMixinConcat / DigitMixinNoOp / make_digit_mixin
     (256-284), and the ``wte`` / ``dte`` / ``digit_mixin`` triple of GPT (304-306, 323-327).
@@ -24,6 +24,8 @@ weight / bias / scalars, rounded once to the parameter dtype:
   * the MEAN residual (config 5): fp32 parameters, no output norm;
   * the cross-attention mixin over one id tensor OR two (norm(emb(padded) + emb(pulled))): fp32 arithmetic, bf16 tables
     accepted (widened once).
+  * the concat mixin with byte self-attention (use_byte_self_attn): fp32; the attention layer is one HIP call each way, the
+    gather + norm in front of it and the concat + linear + norm behind it are torch ops.
 What has no backward raises at FORWARD time instead of silently dropping the graph: MEAN with bf16 tables or an output norm,
 the character mixer (inference-only in the reference), and the materialised (non-fused) seam tensors.
 """
@@ -232,20 +234,6 @@ def _mix_concat(h_or_tok, byte_embs, *, bpt: int, weight: Tensor, bias: Tensor |
                            norm_out=norm_out)
 
 
-class ByteMixinConcat(nn.Module):  # train_gpt.py:430-443
-    def __init__(self, dims: ModelDims, max_seq_len: int, byte_params: ByteHyperparameters):
-        super().__init__()
-        self.byte_params = byte_params
-        if byte_params.use_byte_self_attn:
-            raise NotImplementedError("use_byte_self_attn (ByteSelfAttn, train_gpt.py:382-418) is outside the front-end path")
-        self.attention = nn.Identity()
-        self.mixin = CastedLinear(dims.token_dim + dims.byte_dim * byte_params.bytes_per_token, dims.model_dim)
-
-    def forward(self, tok_embs, byte_embs=None) -> Tensor:
-        return _mix_concat(tok_embs, byte_embs, bpt=self.byte_params.bytes_per_token, weight=self.mixin.weight, bias=None,
-                           bytes_first=False, norm_out=True)
-
-
 class Rotary(nn.Module):  # train_gpt.py:188-207: the buffers, built with the same torch expressions
     def __init__(self, dim: int, max_seq_len: int):
         super().__init__()
@@ -255,6 +243,88 @@ class Rotary(nn.Module):  # train_gpt.py:188-207: the buffers, built with the sa
         theta = torch.einsum("i,j -> ij", t, angular_freq)
         self.cos = nn.Buffer(theta.cos(), persistent=False)
         self.sin = nn.Buffer(theta.sin(), persistent=False)
+
+
+class CausalSelfAttention(nn.Module):
+    """train_gpt.py:209-240 as ByteSelfAttn uses it: the parameters (qkv_w, lambdas, c_proj.weight, zero-initialised) and the
+    non-persistent Rotary buffers under the reference's names.  The work -- projections, per-head norm, rotary, the banded
+    softmax, c_proj and the residual around it -- is one library call issued by ByteSelfAttn.forward; this class holds the weights."""
+
+    def __init__(self, dim: int, num_heads: int, max_seq_len: int, head_dim=128):
+        super().__init__()
+        if head_dim != 128:
+            raise NotImplementedError("CausalSelfAttention: head_dim 128 only (every instance ByteSelfAttn builds, train_gpt.py:391)")
+        self.num_heads, self.head_dim = num_heads, head_dim
+        hdim = num_heads * head_dim
+        bound = (3 ** 0.5) * 0.5 * (dim ** -0.5)
+        self.qkv_w = nn.Parameter(torch.empty(3, hdim, dim).uniform_(-bound, bound))
+        self.lambdas = nn.Parameter(torch.tensor([0.5, 0.5]))
+        self.rotary = Rotary(head_dim, max_seq_len)
+        self.c_proj = CastedLinear(hdim, dim)
+        self.c_proj.weight.detach().zero_()
+        self.attn_scale = 0.12
+
+
+class ByteSelfAttn(nn.Module):
+    """train_gpt.py:382-418.  forward(byte_embs (B, T * bpt, D)) = byte_embs + attention(byte_embs) under the sliding-window causal
+    (or, with mix_byte_in_tok, block-causal) mask, as mot_byte_self_attn_fwd / _bwd.  The reference's BlockMask has no counterpart:
+    the kernels derive the band from bytes_per_token and sliding_window_tokens."""
+
+    def __init__(self, dim: int, max_seq_len: int, byte_params: ByteHyperparameters, mix_byte_in_tok: bool = False):
+        super().__init__()
+        self.byte_params = byte_params
+        self.mix_byte_in_tok = mix_byte_in_tok
+        self.attention = CausalSelfAttention(dim=dim, num_heads=max(1, dim // 128), max_seq_len=max_seq_len * byte_params.bytes_per_token,
+                                             head_dim=128) if byte_params.use_byte_self_attn else nn.Identity()
+        self.block_mask = None
+
+    def forward(self, byte_embs: Tensor) -> Tensor:
+        if not self.byte_params.use_byte_self_attn:
+            return byte_embs
+        a, bp = self.attention, self.byte_params
+        return F_mot.byte_self_attn(byte_embs, a.qkv_w, a.c_proj.weight, a.lambdas, a.rotary.cos, a.rotary.sin, bpt=bp.bytes_per_token,
+                                    window=bp.sliding_window_tokens * bp.bytes_per_token, block_causal=self.mix_byte_in_tok)
+
+
+class ByteMixinConcat(nn.Module):  # train_gpt.py:430-443
+    """With use_byte_self_attn (runs 1.3 / 1.4 of experiments10_000steps.sh) the byte rows are materialised for the attention layer:
+    gather + norm of the two tables and the concat + linear + norm behind the attention are plain torch ops (autograd included), the
+    attention layer itself is the HIP call.  Without it the module takes the fused gather-GEMM path it always took."""
+
+    def __init__(self, dims: ModelDims, max_seq_len: int, byte_params: ByteHyperparameters):
+        super().__init__()
+        self.byte_params = byte_params
+        self.attention = ByteSelfAttn(dims.byte_dim, max_seq_len, byte_params,
+                                      byte_params.mix_bytes_within_tok_in) if byte_params.use_byte_self_attn else nn.Identity()
+        self.mixin = CastedLinear(dims.token_dim + dims.byte_dim * byte_params.bytes_per_token, dims.model_dim)
+
+    def _forward_self_attn(self, tok_embs, byte_embs) -> Tensor:
+        bpt = self.byte_params.bytes_per_token
+        if isinstance(tok_embs, EmbedHandle):
+            h = tok_embs
+            if h.scale_tok is not None or h.scale_byte is not None:
+                raise NotImplementedError("ByteMixinConcat with use_byte_self_attn: learned embedding scalars are not part of this mixin")
+            for w, what in ((h.tok_weight, "token table"), (h.byte_weight, "byte table")):
+                if w.dtype != torch.float32:
+                    raise NotImplementedError(f"ByteMixinConcat with use_byte_self_attn: the {what} is {w.dtype}; only float32 is built "
+                                              "(bfloat16 embeddings, the production cast, are the follow-up)")
+            F_mot.capi.require_device(h.tok_weight, h.byte_weight, h.tokens, h.ids_a)
+            B = h.tokens.shape[0] if h.tokens.ndim > 1 else 1
+            tok_embs = F.embedding(h.tokens.reshape(B, -1).long(), h.tok_weight)
+            byte_embs = F.embedding(h.ids_a.reshape(B, -1), h.byte_weight)
+            if h.ids_b is not None:   # norm(emb(padded) + emb(pulled)), train_gpt.py:364-372
+                byte_embs = byte_embs + F.embedding(h.ids_b.reshape(B, -1), h.byte_weight)
+            tok_embs = norm(tok_embs) if h.norm_tok else tok_embs
+            byte_embs = norm(byte_embs) if h.norm_byte else byte_embs
+        byte_embs = self.attention(byte_embs)
+        byte_embs = byte_embs.reshape(byte_embs.shape[0], byte_embs.shape[1] // bpt, bpt * byte_embs.shape[2])   # "B (S bpt) D -> B S (bpt D)"
+        return norm(self.mixin(torch.cat([tok_embs, byte_embs], dim=-1)))
+
+    def forward(self, tok_embs, byte_embs=None) -> Tensor:
+        if self.byte_params.use_byte_self_attn:
+            return self._forward_self_attn(tok_embs, byte_embs)
+        return _mix_concat(tok_embs, byte_embs, bpt=self.byte_params.bytes_per_token, weight=self.mixin.weight, bias=None,
+                           bytes_first=False, norm_out=True)
 
 
 class CrossAttention(nn.Module):
