@@ -61,7 +61,9 @@ typedef enum MotMixMode {
     MOT_MIX_NOOP = 0,         /* x = tok part            (train_gpt.py:342-348, 421-427)            */
     MOT_MIX_SUM = 1,          /* x = a + concat_k b_k    (modded-nanogpt/runs/71_*.py:227-230)      */
     MOT_MIX_MEAN = 2,         /* x = a + mean_k b_k      (inference/inference.py:266-267)           */
-    MOT_MIX_CONCAT_LINEAR = 3 /* x = W.cat(a, b_*) + bias (train_gpt.py:430-443; model.py:256-268)  */
+    MOT_MIX_CONCAT_LINEAR = 3, /* x = W.cat(a, b_*) + bias (train_gpt.py:430-443; model.py:256-268) */
+    MOT_MIX_CONCAT = 4        /* x = cat(a, b_*): "MoT via pure concatenation", no weight, no GEMM
+                                 (modded-nanogpt/runs/711_*.py:224-232, call site 314-316; runs 712, 713) */
 } MotMixMode;
 
 typedef enum MotIdSource {
@@ -149,7 +151,12 @@ int mot_gather_rows(const void *ids_a, const void *ids_b, int ids_elem_bytes, in
  *   (train_gpt.py:686-728) folded in;
  *   GPT.wte / GPT.dte / digit_mixin                mathblations/model.py:256-268, 304-306, 323-327;
  *   embed_tokens / embed_bytes / mixin_bytes       modded-nanogpt/runs/71_*.py:227-230, 312-314
- *   (and the per-embedding-norm / lambda variants runs/71041_*.py:311-313, runs/71081_*.py:302-315).
+ *   (and the per-embedding-norm / lambda variants runs/71041_*.py:311-313, runs/71081_*.py:302-315);
+ *   mixin_bytes of the pure-concatenation runs      modded-nanogpt/runs/711_*.py:224-232, 314-316
+ *   (MOT_MIX_CONCAT: x = [a | b_0 | .. | b_{bpt-1}], model_dim = tok_dim + bpt*byte_dim; tok_dim and byte_dim multiples of the
+ *   16-byte vector, 4 fp32 / 8 bf16 elements, so that no vector straddles two parts; no weight, no bias; norm_tok is over the tok_dim
+ *   columns, norm_out over all model_dim; with two id tensors b_k = E[idsA] + E[idsB], normalised as a sum when norm_byte is set,
+ *   which needs byte_dim = vector * 2^k and tok_dim a multiple of byte_dim).
  *
  * Per token n of row-major (B, T):
  *   a   = tok_table[tokens[n]];            if norm_tok:  a = rms_norm(a);    a *= *scale_tok
@@ -201,7 +208,7 @@ typedef struct MotEmbedMixDesc {
     int64_t byte_rows;
 
     /* mixing */
-    int32_t model_dim;   /* output columns; SUM/MEAN/NOOP require == tok_dim */
+    int32_t model_dim;   /* output columns; SUM/MEAN/NOOP require == tok_dim, CONCAT == tok_dim + bpt*byte_dim */
     int32_t bytes_first; /* CONCAT_LINEAR: 0 = [a, b_*] (train_gpt.py:443), 1 = [b_*, a] (model.py:267) */
     const void *weight;  /* CONCAT_LINEAR: [model_dim, tok_dim + bpt*byte_dim] row-major (nn.Linear) */
     const void *bias;    /* optional [model_dim] */
@@ -231,7 +238,7 @@ typedef struct MotEmbedMixDesc {
  * `fwd` is the forward's descriptor with id_source == MOT_IDS_GIVEN (pass the byte ids the forward
  * returned through out_ids_*); `out`, `out_ids_*`, `counters` are ignored.  Gradients are ACCUMULATED
  * (+=) into the given buffers, so a parameter's .grad can be passed directly; NULL = not wanted.
- * Built: MOT_MIX_SUM, MOT_MIX_NOOP, MOT_MIX_CONCAT_LINEAR, and MOT_MIX_MEAN without an output norm (the residual of
+ * Built: MOT_MIX_SUM, MOT_MIX_NOOP, MOT_MIX_CONCAT, MOT_MIX_CONCAT_LINEAR, and MOT_MIX_MEAN without an output norm (the residual of
  * inference.py:267 has none; its small character table makes the table gradient a dense product, mot_backward.hip; with
  * bf16 tables that product runs on operands widened slab by slab into the workspace).
  * With dtype == MOT_BF16 the tables, weight/bias, `out` and grad_out are bf16 as in the forward, while

@@ -7,7 +7,7 @@ Python layer mirrors the reference's interfaces for this path and nothing else:
   functional      tensor-level wrappers (embed_mix = the fused gather + mix forward; byte_head_loss = the mixout byte head;
                   byte_self_attn = the sliding-window byte self-attention layer of the concat mixin)
   modules         FlexibleEmbedding / ByteMixin* / CastedLinear (scaled-pre-train), DigitMixin* / GPTConfig
-                  (mathblations), SumFrontEnd (modded-nanogpt), FusedFrontEnd (tokens -> x in one launch)
+                  (mathblations), SumFrontEnd / ConcatFrontEnd (modded-nanogpt), FusedFrontEnd (tokens -> x in one launch)
   loader          shard reader, rank slice, input/target shift (distributed_data_generator)
   grad_sync       GradBucket: one flat all-reduce for the front-end's gradients (train_gpt.py:1320-1321)
 
@@ -17,9 +17,10 @@ shim at the repo root maps that name onto this directory).
 from . import _capi
 from . import data_creation, functional, grad_sync, loader, modules
 from ._capi import build_info, check_status, set_debug_ids
+from .modules import ConcatFrontEnd
 from .functional import byte_head_loss, byte_self_attn, create_batch, embed_mix, embed_mix_plan, gather_rows, pull_bytes, tokens_to_bytes
 
 __all__ = [
-    "build_info", "check_status", "set_debug_ids", "data_creation", "functional", "grad_sync", "loader", "modules",
+    "build_info", "check_status", "set_debug_ids", "ConcatFrontEnd", "data_creation", "functional", "grad_sync", "loader", "modules",
     "byte_head_loss", "byte_self_attn", "create_batch", "embed_mix", "embed_mix_plan", "gather_rows", "pull_bytes", "tokens_to_bytes",
 ]

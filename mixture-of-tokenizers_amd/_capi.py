@@ -27,7 +27,7 @@ IS_DEV_LIB = _dev_lib is not None
 MOT_OK, MOT_EINVAL, MOT_ESHAPE, MOT_EUNSUPPORTED, MOT_EHIP, MOT_EWORKSPACE = 0, -1, -2, -3, -4, -5
 STATUS_TOKEN_OOR, STATUS_BYTE_OOR, STATUS_TARGET_OOR = 1, 2, 4
 PULL_NONE, PULL_LEFT, PULL_RIGHT = 0, 1, 2
-MIX_NOOP, MIX_SUM, MIX_MEAN, MIX_CONCAT_LINEAR = 0, 1, 2, 3
+MIX_NOOP, MIX_SUM, MIX_MEAN, MIX_CONCAT_LINEAR, MIX_CONCAT = 0, 1, 2, 3, 4
 IDS_NONE, IDS_FROM_TTB, IDS_GIVEN = 0, 1, 2
 F32, BF16 = 0, 1
 MAX_BPT = 64

@@ -44,6 +44,11 @@ __device__ __forceinline__ void seg_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
+// MOT_MIX_CONCAT (x = norm(cat(a, b_*)), runs/711_*.py:224-232) shares the split row layout [token part | byte part] of the
+// CONCAT_LINEAR scatter (there the row is du = dy.W) and, like SUM, carries its own output norm: the row IS the mixed row.
+constexpr bool split_row(int mode) { return mode == MOT_MIX_CONCAT_LINEAR || mode == MOT_MIX_CONCAT; }
+constexpr bool mixes_bytes(int mode) { return mode == MOT_MIX_SUM || mode == MOT_MIX_CONCAT; }   // the byte rows are part of the normed row
+
 constexpr int kBwdThreads = 512;  // 8 waves, 2 per SIMD: a 256-register budget per lane
 constexpr int kBwdWaves = kBwdThreads / 64;
 constexpr int kWindow = 64;  // sorted positions per wave work item
@@ -126,7 +131,7 @@ __global__ __launch_bounds__(kBwdThreads) void embed_mix_bwd_kernel(const BwdArg
     auto tok_off = [&](int e) { const int o = e - A.tok_lo; return (e < D && (unsigned)o < (unsigned)Dt) ? o : -1; };
     auto byte_off = [&](int e) { const int o = e - A.byte_lo; return (MODE != MOT_MIX_NOOP && e < D && (unsigned)o < (unsigned)A.nbk) ? o : -1; };
     // norm over the sum of two embeddings only exists in front of the concat mixin (train_gpt.py:378, 443)
-    const bool pair_norm = MODE == MOT_MIX_CONCAT_LINEAR && A.norm_byte && A.ids_b;
+    const bool pair_norm = split_row(MODE) && A.norm_byte && A.ids_b;
     const float s_tok = A.scale_tok ? *A.scale_tok : 1.0f;
     const float s_byte = A.scale_byte ? *A.scale_byte : 1.0f;
     float ds_t = 0.f, ds_b = 0.f;
@@ -244,17 +249,17 @@ __global__ __launch_bounds__(kBwdThreads) void embed_mix_bwd_kernel(const BwdArg
             float ss = 0.f;
 #pragma unroll
             for (int j = 0; j < NE; ++j) {
-                const float y = an[j] * s_tok + (MODE == MOT_MIX_SUM ? bn[j] * s_byte : 0.f);
+                const float y = an[j] * s_tok + (mixes_bytes(MODE) ? bn[j] * s_byte : 0.f);
                 ss += y * y;
             }
             const float ry = rms_scale((A.abl & 4) ? ss : wave_sum(ss), D, A.eps);
             float m = 0.f;
 #pragma unroll
-            for (int j = 0; j < NE; ++j) m += dy[j] * ((an[j] * s_tok + (MODE == MOT_MIX_SUM ? bn[j] * s_byte : 0.f)) * ry);
+            for (int j = 0; j < NE; ++j) m += dy[j] * ((an[j] * s_tok + (mixes_bytes(MODE) ? bn[j] * s_byte : 0.f)) * ry);
             m = ((A.abl & 4) ? m : wave_sum(m)) / (float)D;
 #pragma unroll
             for (int j = 0; j < NE; ++j) {
-                const float x = (an[j] * s_tok + (MODE == MOT_MIX_SUM ? bn[j] * s_byte : 0.f)) * ry;
+                const float x = (an[j] * s_tok + (mixes_bytes(MODE) ? bn[j] * s_byte : 0.f)) * ry;
                 dy[j] = ry * (dy[j] - x * m);
             }
         }
@@ -375,7 +380,7 @@ __global__ __launch_bounds__(kBwdThreads) void embed_mix_bwd_full_kernel(const B
     if (tid == 0) *fx_bits = 0u;
     // SPLIT: the gradient row is du of CONCAT_LINEAR -- [token part | byte part] (or the reverse), every 64-element
     // chunk j belonging wholly to one part (host-checked); SUM / NOOP rows are token part and byte part at once.
-    constexpr bool SPLIT = MODE == MOT_MIX_CONCAT_LINEAR;
+    constexpr bool SPLIT = split_row(MODE);
     constexpr bool BYTES = MODE != MOT_MIX_NOOP;
     uint32_t tmask = 0, bmask = 0;   // bit j: chunk j carries token-row / byte-row elements
 #pragma unroll
@@ -661,7 +666,7 @@ __global__ __launch_bounds__(kBwdThreads) void embed_mix_bwd_full_kernel(const B
                 float ss = 0.f, m = 0.f;
 #pragma unroll
                 for (int j = 0; j < NE; ++j) {
-                    const float y = an[j] * s_tok + (MODE == MOT_MIX_SUM ? bn[j] * s_byte : 0.f);
+                    const float y = an[j] * s_tok + (mixes_bytes(MODE) ? bn[j] * s_byte : 0.f);
                     ss += y * y;
                     m += dy[j] * y;
                 }
@@ -669,7 +674,7 @@ __global__ __launch_bounds__(kBwdThreads) void embed_mix_bwd_full_kernel(const B
                 m = wave_sum(m) * ry * (1.0f / (float)D);       // mean(g * x), x = y * ry   (a multiply, not an IEEE divide: <= 1 ulp)
 #pragma unroll
                 for (int j = 0; j < NE; ++j) {
-                    const float x = (an[j] * s_tok + (MODE == MOT_MIX_SUM ? bn[j] * s_byte : 0.f)) * ry;
+                    const float x = (an[j] * s_tok + (mixes_bytes(MODE) ? bn[j] * s_byte : 0.f)) * ry;
                     dy[j] = ry * (dy[j] - x * m);
                 }
             }
@@ -1548,10 +1553,10 @@ static int launch_bwd_full_t(const BwdArgs &A, size_t lds, hipStream_t stream) {
 
 template <int MODE, int NE>
 static int launch_bwd_full(const BwdArgs &A, size_t lds, hipStream_t stream) {
-    if constexpr (MODE != MOT_MIX_CONCAT_LINEAR) {
+    if constexpr (!split_row(MODE)) {
         if (A.in_bf16) return launch_bwd_full_t<MODE, NE, true>(A, lds, stream);
-    } else if (A.in_bf16) {
-        return set_error(MOT_EUNSUPPORTED, "embed_mix_bwd: the CONCAT_LINEAR scatter takes fp32 operands");
+    } else if (A.in_bf16) {   // (full_layout sends bf16 split rows to the general kernel)
+        return set_error(MOT_EUNSUPPORTED, "embed_mix_bwd: the split-row scatter of this kernel takes fp32 operands");
     }
     return launch_bwd_full_t<MODE, NE, false>(A, lds, stream);
 }
@@ -1560,7 +1565,7 @@ static int launch_bwd_full(const BwdArgs &A, size_t lds, hipStream_t stream) {
 template <int MODE>
 static bool full_layout(const BwdArgs &A) {
     if (A.D & 63) return false;
-    if (MODE == MOT_MIX_CONCAT_LINEAR) {   // split row: every 64-element chunk wholly token part or wholly byte part
+    if (split_row(MODE)) {   // split row: every 64-element chunk wholly token part or wholly byte part
         if ((A.Dt & 63) || (A.tok_lo & 63) || (A.byte_lo & 63) || (A.nbk & 63) || A.Dt + A.nbk != A.D || A.Db > 0xffff || A.in_bf16) return false;
     } else {
         if (A.Dt != A.D || A.tok_lo != 0) return false;
@@ -1645,7 +1650,7 @@ static int run_scatter(BwdArgs &A, const MotEmbedMixDesc &d, int32_t *ws_ints, f
         return set_error(MOT_EUNSUPPORTED, "embed_mix_bwd: token tables of %lld rows (>= 2^21 - 1) are not built", (long long)d.tok_rows);
     const bool full = full_layout<MODE>(A) && !A.g_ld;   // (a row stride is known to the lane-contiguous kernel and to the general one)
     bool lc = false, plain = false;
-    if constexpr (MODE != MOT_MIX_CONCAT_LINEAR) {
+    if constexpr (!split_row(MODE)) {
         lc = lc_layout<MODE>(A) && !(A.abl & 8);   // abl 8: dev switch back to the strided kernels
         plain = plain_layout<MODE>(A) && !(A.abl & 24);   // abl 16: dev switch back to the general kernels
         lc = lc || plain;                           // (LDS layout below: one fp32 row per wave, byte-table rows padded by one sum)
@@ -1667,13 +1672,13 @@ static int run_scatter(BwdArgs &A, const MotEmbedMixDesc &d, int32_t *ws_ints, f
         if (cap >= d.byte_rows) { A.priv_lo = (int)d.byte_rows; A.priv_rows = (int)d.byte_rows; }
         else if (cap > 64) { A.priv_lo = (int)cap - 32; A.priv_hi0 = (int)d.byte_rows - 32; A.priv_rows = (int)cap; }
         lds += (size_t)A.priv_rows * row_q * 8 + 8;
-        if (d.norm_byte && !(MODE == MOT_MIX_CONCAT_LINEAR && d.ids_b)) {
+        if (d.norm_byte && !(split_row(MODE) && d.ids_b)) {
             rc = launch_rows_rnorm(A.byte_table, d.byte_rows, d.byte_dim, A.eps, rnorm_ws, A.in_bf16 ? MOT_BF16 : MOT_F32, stream);
             if (rc) return rc;
             A.byte_rnorm = rnorm_ws;
         }
     }
-    if constexpr (MODE != MOT_MIX_CONCAT_LINEAR) {
+    if constexpr (!split_row(MODE)) {
         if (plain) return dispatch_ne_plain<MODE>(A, lds, stream);
         if (lc) return dispatch_ne_lc<MODE>(A, lds, stream);
     }
@@ -1702,6 +1707,7 @@ static void fill_bwd_args(BwdArgs &A, const MotEmbedMixDesc &d, const MotEmbedMi
         A.tok_sorted = A.pos_sorted + n;
     }
     A.Dt = d.tok_dim; A.tok_lo = 0; A.byte_lo = 0; A.nbk = d.bpt * d.byte_dim;
+    if (d.mode == MOT_MIX_CONCAT) { A.D = d.tok_dim + A.nbk; A.byte_lo = d.tok_dim; }   // the row is cat(token row, byte rows)
 }
 
 // ==========================================================================================
@@ -2397,7 +2403,7 @@ __global__ __launch_bounds__(kThreads) void ids_column_i32_kernel(const int64_t 
     }
 }
 
-static size_t bwd_rnorm_floats(const MotEmbedMixDesc &d) { return d.mode == MOT_MIX_SUM ? ((size_t)d.byte_rows + 3) & ~(size_t)3 : 0; }
+static size_t bwd_rnorm_floats(const MotEmbedMixDesc &d) { return mixes_bytes(d.mode) ? ((size_t)d.byte_rows + 3) & ~(size_t)3 : 0; }
 size_t embed_mix_bwd_mean_workspace_bytes(const MotEmbedMixDesc &d);
 size_t embed_mix_bwd_workspace_bytes(const MotEmbedMixDesc &d) {
     if (d.mode == MOT_MIX_MEAN) return embed_mix_bwd_mean_workspace_bytes(d);
@@ -2756,7 +2762,7 @@ int launch_embed_mix_bwd(const MotEmbedMixDesc &d, const MotEmbedMixGrads &gr, h
     if (d.n_rows * d.tokens_per_row > 0x7fffffffLL) return set_error(MOT_EUNSUPPORTED, "embed_mix_bwd: more than 2^31 tokens");
     if (d.mode == MOT_MIX_CONCAT_LINEAR) return launch_embed_mix_bwd_linear(d, gr, stream);
     if (d.mode == MOT_MIX_MEAN) return launch_embed_mix_bwd_mean(d, gr, stream);
-    if (d.mode == MOT_MIX_SUM && d.id_source != MOT_IDS_GIVEN)
+    if (mixes_bytes(d.mode) && d.id_source != MOT_IDS_GIVEN)
         return set_error(MOT_EUNSUPPORTED, "embed_mix_bwd: pass the byte ids the forward returned (MOT_IDS_GIVEN)");
     BwdArgs A;
     fill_bwd_args(A, d, gr);
@@ -2766,6 +2772,7 @@ int launch_embed_mix_bwd(const MotEmbedMixDesc &d, const MotEmbedMixGrads &gr, h
     float *rn = (float *)d.workspace;
     int32_t *ints = (int32_t *)(rn + bwd_rnorm_floats(d));
     if (d.mode == MOT_MIX_SUM) return run_scatter<MOT_MIX_SUM>(A, d, ints, rn, stream);
+    if (d.mode == MOT_MIX_CONCAT) return run_scatter<MOT_MIX_CONCAT>(A, d, ints, rn, stream);
     return run_scatter<MOT_MIX_NOOP>(A, d, ints, rn, stream);
 }
 

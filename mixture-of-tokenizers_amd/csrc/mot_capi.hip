@@ -49,7 +49,7 @@ static int validate_embed_mix(const MotEmbedMixDesc *d) {
     if ((d->flags & ~(MOT_FLAG_LINEAR_ONE_LAUNCH | MOT_FLAG_MEAN_GENERIC | MOT_FLAG_BWD_DU_FP32 | MOT_FLAG_LINEAR_COMPOSED)) || d->reserved0)
         return set_error(MOT_EINVAL, "embed_mix: unknown flags 0x%x / reserved0 %u", d->flags, d->reserved0);
     if (d->n_rows < 0 || d->tokens_per_row < 0) return set_error(MOT_ESHAPE, "embed_mix: negative shape");
-    if (d->mode < MOT_MIX_NOOP || d->mode > MOT_MIX_CONCAT_LINEAR) return set_error(MOT_EINVAL, "embed_mix: bad mode %d", d->mode);
+    if (d->mode < MOT_MIX_NOOP || d->mode > MOT_MIX_CONCAT) return set_error(MOT_EINVAL, "embed_mix: bad mode %d", d->mode);
     if (!d->tokens || !d->tok_table || !d->out) return set_error(MOT_EINVAL, "embed_mix: tokens/tok_table/out must be non-null");
     if (d->tok_rows <= 0 || d->tok_dim <= 0 || d->model_dim <= 0) return set_error(MOT_ESHAPE, "embed_mix: empty token table");
     if (d->tokens_per_row * (int64_t)(d->bpt > 0 ? d->bpt : 1) > 0x7fffffffLL)
@@ -86,15 +86,29 @@ static int validate_embed_mix(const MotEmbedMixDesc *d) {
         case MOT_MIX_CONCAT_LINEAR:
             if (!d->weight) return set_error(MOT_EINVAL, "embed_mix concat_linear: weight missing");
             break;
+        case MOT_MIX_CONCAT:   // x = norm(cat(a, b_*)): no weight, no GEMM (modded-nanogpt/runs/711_*.py:224-232)
+            if (d->weight || d->bias) return set_error(MOT_EINVAL, "embed_mix concat: the pure concatenation takes no weight / bias");
+            if ((int64_t)d->model_dim != (int64_t)d->tok_dim + (int64_t)d->bpt * d->byte_dim)
+                return set_error(MOT_ESHAPE, "embed_mix concat: need model_dim == tok_dim + bpt*byte_dim (got %d, %d + %d*%d)", d->model_dim,
+                                 d->tok_dim, d->bpt, d->byte_dim);
+            break;
     }
     if (d->mode != MOT_MIX_CONCAT_LINEAR) {
         const int vec = d->dtype == MOT_BF16 ? 8 : 4;  // elements per 16-byte lane load
-        if ((d->tok_dim % vec) || (d->mode == MOT_MIX_SUM && (d->byte_dim % vec)))
+        const bool concat = d->mode == MOT_MIX_CONCAT;
+        // (CONCAT: a 16-byte chunk must never straddle the boundary between the token part and a byte slot)
+        if ((d->tok_dim % vec) || ((d->mode == MOT_MIX_SUM || concat) && (d->byte_dim % vec)))
             return set_error(MOT_EUNSUPPORTED, "embed_mix: tok_dim %d / byte_dim %d must be multiples of %d elements (16 bytes)", d->tok_dim,
                              d->byte_dim, vec);
-        if (d->tok_dim > 2048) return set_error(MOT_EUNSUPPORTED, "embed_mix: model_dim %d > 2048 is not built", d->tok_dim);
-        if (dual && d->norm_byte)
-            return set_error(MOT_EUNSUPPORTED, "embed_mix: norm_byte over two id tensors is only built for CONCAT_LINEAR");
+        if (d->model_dim > 2048) return set_error(MOT_EUNSUPPORTED, "embed_mix: model_dim %d > 2048 is not built", d->model_dim);
+        if (dual && d->norm_byte) {
+            if (!concat) return set_error(MOT_EUNSUPPORTED, "embed_mix: norm_byte over two id tensors is only built for CONCAT_LINEAR and CONCAT");
+            // the per-(token, slot) rms factor is reduced inside the slot's lane group: an aligned power-of-two run of 16-byte chunks
+            const int l = d->byte_dim / vec;
+            if ((l & (l - 1)) || l > 64 || (d->tok_dim / vec) % l)
+                return set_error(MOT_EUNSUPPORTED, "embed_mix concat: norm_byte over two id tensors needs byte_dim %d = %d * 2^k elements and tok_dim %d a multiple of it",
+                                 d->byte_dim, vec, d->tok_dim);
+        }
     }
     return MOT_OK;
 }
@@ -212,7 +226,7 @@ int mot_embed_mix_bwd(const MotEmbedMixDesc *desc, const MotEmbedMixGrads *grads
     if (rc) return rc;
     if (!grads->grad_out) return set_error(MOT_EINVAL, "embed_mix_bwd: grad_out missing");
     if (!grads->d_tok_table) return set_error(MOT_EINVAL, "embed_mix_bwd: d_tok_table missing");
-    if (d.mode == MOT_MIX_SUM && !grads->d_byte_table) return set_error(MOT_EINVAL, "embed_mix_bwd: d_byte_table missing");
+    if ((d.mode == MOT_MIX_SUM || d.mode == MOT_MIX_CONCAT) && !grads->d_byte_table) return set_error(MOT_EINVAL, "embed_mix_bwd: d_byte_table missing");
     if (d.n_rows == 0 || d.tokens_per_row == 0) return MOT_OK;
     return launch_embed_mix_bwd(d, *grads, (hipStream_t)stream);
 }

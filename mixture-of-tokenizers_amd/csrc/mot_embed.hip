@@ -1,5 +1,5 @@
 // mot_embed.hip -- float path kernels (gfx950): the fused gather + mix forward for the
-// SUM / MEAN / NOOP modes, the seam gather (materialised FlexibleEmbedding outputs) and the
+// SUM / MEAN / NOOP / CONCAT modes, the seam gather (materialised FlexibleEmbedding outputs) and the
 // byte-table inverse-rms prologue.  fp32 throughout (the reference's CPU parity mode).
 //
 // Fused kernel (embed_mix_kernel): every WAVE works alone on a unit of 16 or 32 consecutive tokens of one row -- no workgroup
@@ -35,16 +35,21 @@ struct MixStream {
     int lane, Dm, nchunk, ntok;
     int tokv = 0, unit_lane0 = 0;
     bool act[NCH];
+    bool tact[NCH];                                 // CONCAT: the lane's chunk i is a chunk of the token row (else of a byte slot)
     raw_t ar[U][NCH];                               // token rows of the batch in flight
 
     __device__ __forceinline__ MixStream(const MixArgs &A_, const WaveLds &W_, int ntok_) : A(A_), W(W_), ntok(ntok_) {
         tok_table = (const T *)A.tok_table;
         byte_table = (const T *)A.byte_table;
         lane = threadIdx.x & 63;
-        Dm = A.Dt;
+        Dm = MODE == MOT_MIX_CONCAT ? A.Dt + A.bpt * A.Db : A.Dt;
         nchunk = Dm / VEC;
 #pragma unroll
         for (int i = 0; i < NCH; ++i) act[i] = lane + 64 * i < nchunk;
+        if (MODE == MOT_MIX_CONCAT) {
+#pragma unroll
+            for (int i = 0; i < NCH; ++i) tact[i] = VEC * (lane + 64 * i) < A.Dt;
+        }
     }
     // token rows of a batch of U tokens: lane unit_lane0 + j of `tokv` holds token j
     __device__ __forceinline__ void request(int tb) {
@@ -55,6 +60,12 @@ struct MixStream {
             if ((uint64_t)(uint32_t)tok >= (uint64_t)A.tok_rows) {
                 if (A.status && lane == 0) atomicOr(A.status, kStatusTokenOor);
                 tok = 0;
+            }
+            if (MODE == MOT_MIX_CONCAT) {   // the token row is Dt of the Dm columns: byte-slot lanes re-read its first chunk
+                const T *trow = tok_table + (int64_t)tok * A.Dt;
+#pragma unroll
+                for (int i = 0; i < NCH; ++i) ar[u][i] = Elem<T>::load_raw(trow + VEC * (tact[i] ? lane + 64 * i : 0));
+                continue;
             }
             const T *trow = tok_table + (int64_t)tok * Dm;
 #pragma unroll
@@ -74,6 +85,12 @@ struct MixStream {
             if (MODE == MOT_MIX_SUM) {
                 slot[i] = (VEC * cc) / A.Db;            // concat_k: column j belongs to slot j / Db
                 within[i] = VEC * cc - slot[i] * A.Db;
+            } else if (MODE == MOT_MIX_CONCAT) {
+                // cat(token row, byte rows): column j >= Dt belongs to slot (j - Dt) / Db (runs/711_*.py:229-231); Dt and Db are
+                // multiples of VEC, so a chunk lies in one part.  Token-row lanes read slot 0's first chunk and drop it
+                const int cb = (act[i] && !tact[i]) ? VEC * c - A.Dt : 0;
+                slot[i] = cb / A.Db;
+                within[i] = cb - slot[i] * A.Db;
             } else {
                 slot[i] = 0;
                 within[i] = VEC * cc;
@@ -100,7 +117,7 @@ struct MixStream {
                 const int t = min(tb + u, ntok - 1);
 #pragma unroll
                 for (int i = 0; i < NCH; ++i) {
-                    if (MODE == MOT_MIX_SUM) {
+                    if (MODE == MOT_MIX_SUM || MODE == MOT_MIX_CONCAT) {
                         const int id = W.ids[t * sv + slot[i]];
                         idr[u][i] = id;
                         br[u][i] = Elem<T>::load_raw(byte_table + (int64_t)id * A.Db + within[i]);
@@ -134,6 +151,21 @@ struct MixStream {
                         if (dual) v += Elem<T>::widen(br2[DUAL ? u : 0][i]);  // emb(padded) + emb(pulled), train_gpt.py:378
                         if (A.norm_byte) v *= A.byte_rnorm[idr[u][i]];
                         b[0][i] = v;
+                    } else if (MODE == MOT_MIX_CONCAT) {
+                        vec_t v = Elem<T>::widen(br[u][i]);
+                        if (dual) v += Elem<T>::widen(br2[DUAL ? u : 0][i]);
+                        if (A.norm_byte) {
+                            if (dual) {
+                                // norm(emb(padded) + emb(pulled)) (train_gpt.py:378): the factor belongs to the (token, slot) pair.
+                                // A slot's Db / VEC chunks are an aligned power-of-two group of lanes (host-checked)
+                                float ss = sumsq(v);
+                                for (int o = 1; o < A.Db / VEC; o <<= 1) ss += __shfl_xor(ss, o, 64);
+                                v *= rms_scale(ss, A.Db, A.eps);
+                            } else {
+                                v *= A.byte_rnorm[idr[u][i]];
+                            }
+                        }
+                        b[0][i] = v;
                     } else if (MODE == MOT_MIX_MEAN) {
                         b[0][i] = bm[u][i];
                     }
@@ -141,8 +173,8 @@ struct MixStream {
                 if (A.norm_tok) {
                     float ss = 0.f;
 #pragma unroll
-                    for (int i = 0; i < NCH; ++i) ss += act[i] ? sumsq(a[0][i]) : 0.f;
-                    const float r = rms_scale(wave_sum(ss), Dm, A.eps);
+                    for (int i = 0; i < NCH; ++i) ss += (MODE == MOT_MIX_CONCAT ? tact[i] : act[i]) ? sumsq(a[0][i]) : 0.f;
+                    const float r = rms_scale(wave_sum(ss), MODE == MOT_MIX_CONCAT ? A.Dt : Dm, A.eps);
 #pragma unroll
                     for (int i = 0; i < NCH; ++i) a[0][i] *= r;
                 }
@@ -154,6 +186,7 @@ struct MixStream {
 #pragma unroll
                 for (int i = 0; i < NCH; ++i) {
                     if (MODE == MOT_MIX_NOOP) x[i] = a[0][i];
+                    else if (MODE == MOT_MIX_CONCAT) x[i] = tact[i] ? a[0][i] : (scale_b ? b[0][i] * s_byte : b[0][i]);
                     else x[i] = a[0][i] + (scale_b ? b[0][i] * s_byte : b[0][i]);
                 }
                 if (A.norm_out) {
@@ -175,7 +208,8 @@ struct MixStream {
     }
 };
 
-// MODE: MOT_MIX_NOOP / SUM / MEAN.   NCH: 16-byte chunks per lane (covers Dm <= 64*NCH*VEC).   U: tokens in flight per wave.
+// MODE: MOT_MIX_NOOP / SUM / MEAN / CONCAT (x = cat(token row, byte rows), Dm = Dt + bpt * Db columns: a lane's chunk comes from the
+// token row or from one byte slot, a per-lane constant per chunk).   NCH: 16-byte chunks per lane (covers Dm <= 64*NCH*VEC).   U: tokens in flight per wave.
 // Every WAVE is on its own (mot_wave.hpp): it owns a unit of A.unit consecutive tokens of one row, produces their byte ids
 // in wave-private LDS and streams them; the four waves of a workgroup share nothing and never meet at a barrier.
 // (105 VGPRs at fp32 / 768 columns: four waves per SIMD.  Forcing the fifth with a launch bound spills into the streaming loop:
@@ -671,16 +705,17 @@ static int launch_mix(const MixArgs &A, int64_t blocks, size_t lds, hipStream_t 
 // NCH = 16-byte chunks per lane: ceil(D / (64 * VEC)).  U keeps ~12 independent 16 B loads per lane in flight.
 template <int MODE>
 static int dispatch_nch(const MixArgs &A, int dtype, int64_t blocks, size_t lds, hipStream_t stream, const RouteWs *route = nullptr) {
+    const int Dm = MODE == MOT_MIX_CONCAT ? A.Dt + A.bpt * A.Db : A.Dt;   // output columns: what a wave's lanes cover
     if (dtype == MOT_BF16) {
-        switch ((A.Dt / 8 + 63) / 64) {
+        switch ((Dm / 8 + 63) / 64) {
             case 1: return launch_mix<MODE, 1, 4, __bf16>(A, blocks, lds, stream, route);
             case 2: return launch_mix<MODE, 2, 4, __bf16>(A, blocks, lds, stream, route);
             case 3: return launch_mix<MODE, 3, 2, __bf16>(A, blocks, lds, stream, route);
             case 4: return launch_mix<MODE, 4, 2, __bf16>(A, blocks, lds, stream, route);
-            default: return set_error(MOT_EUNSUPPORTED, "embed_mix: model_dim %d > 2048 is not built", A.Dt);
+            default: return set_error(MOT_EUNSUPPORTED, "embed_mix: model_dim %d > 2048 is not built", Dm);
         }
     }
-    switch ((A.Dt / 4 + 63) / 64) {
+    switch ((Dm / 4 + 63) / 64) {
         case 1: return launch_mix<MODE, 1, 4, float>(A, blocks, lds, stream, route);
         case 2: return launch_mix<MODE, 2, 4, float>(A, blocks, lds, stream, route);
         case 3: return launch_mix<MODE, 3, 2, float>(A, blocks, lds, stream, route);
@@ -689,7 +724,7 @@ static int dispatch_nch(const MixArgs &A, int dtype, int64_t blocks, size_t lds,
         case 6: return launch_mix<MODE, 6, 1, float>(A, blocks, lds, stream, route);
         case 7:
         case 8: return launch_mix<MODE, 8, 1, float>(A, blocks, lds, stream, route);
-        default: return set_error(MOT_EUNSUPPORTED, "embed_mix: model_dim %d > 2048 is not built", A.Dt);
+        default: return set_error(MOT_EUNSUPPORTED, "embed_mix: model_dim %d > 2048 is not built", Dm);
     }
 }
 
@@ -957,6 +992,7 @@ int launch_embed_mix(const MotEmbedMixDesc &d, hipStream_t stream, __bf16 *add16
             return dispatch_nch<MOT_MIX_SUM>(A, d.dtype, blocks, lds, stream);
         }
         case MOT_MIX_MEAN: return dispatch_nch<MOT_MIX_MEAN>(A, d.dtype, blocks, lds, stream);
+        case MOT_MIX_CONCAT: return dispatch_nch<MOT_MIX_CONCAT>(A, d.dtype, blocks, lds, stream);
         default: return set_error(MOT_EINVAL, "embed_mix: bad mode %d", d.mode);
     }
 }

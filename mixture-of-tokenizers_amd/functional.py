@@ -32,7 +32,8 @@ def _flags(one_launch=None, mean_generic=None, du_fp32=None, composed=None) -> i
     return f
 
 
-_MODES = {"noop": capi.MIX_NOOP, "sum": capi.MIX_SUM, "mean": capi.MIX_MEAN, "concat_linear": capi.MIX_CONCAT_LINEAR}
+_MODES = {"noop": capi.MIX_NOOP, "sum": capi.MIX_SUM, "mean": capi.MIX_MEAN, "concat_linear": capi.MIX_CONCAT_LINEAR,
+          "concat": capi.MIX_CONCAT}
 _PULLS = {None: capi.PULL_NONE, "none": capi.PULL_NONE, "left": capi.PULL_LEFT, "right": capi.PULL_RIGHT}
 
 
@@ -200,6 +201,8 @@ def _embed_mix_fwd(tokens: torch.Tensor, tok_table: torch.Tensor, byte_table: to
     tokens (B, T) integer.  Byte ids either come from `ttb` (+ `pull` = "left" | "right" | None,
     + `add_padded`) inside the kernel, or are given as `ids_a` / `ids_b` (B, T*bpt) int64.
     `scale_*` are 0-dim/1-element DEVICE tensors (learned scalars are read on the device).
+    mode "concat" (x = cat(token row, byte rows), runs/711_*.py:224-232) takes no `weight`; its output has
+    tok_dim + bpt * byte_dim columns.
     `composed` (bf16 concat_linear: the separate gather / GEMM / norm kernels instead of the one gather-GEMM),
     `one_launch` (concat_linear: the one-launch tile kernel instead of the composed kernels) and `mean_generic` (mean: the
     whole-row kernel instead of the LDS column-slice kernel) override the import-time defaults (MotEmbedMixDesc.flags).
@@ -272,7 +275,10 @@ def _embed_mix_fwd(tokens: torch.Tensor, tok_table: torch.Tensor, byte_table: to
             d.bias = capi.ptr(bs)
         d.bytes_first = int(bytes_first)
     else:
-        d.model_dim = tt.shape[1]
+        if m == capi.MIX_CONCAT and (weight is not None or bias is not None):
+            raise ValueError("mode == 'concat' is the pure concatenation: it takes no weight / bias (see 'concat_linear')")
+        # "concat": x = cat(token row, byte rows), runs/711_*.py:224-232
+        d.model_dim = tt.shape[1] + int(bpt) * d.byte_dim if m == capi.MIX_CONCAT else tt.shape[1]
     d.norm_tok, d.norm_byte, d.norm_out = int(norm_tok), int(norm_byte), int(norm_out)
     d.eps = float(eps or 0.0)
     d.scale_tok, d.scale_byte = capi.ptr(scale_tok), capi.ptr(scale_byte)
@@ -379,7 +385,7 @@ _token_orders = _TokenOrderCache()
 _HOIST_SORT = not os.environ.get("MOT_NO_ORDER_HOIST")            # dev switch: let every backward group the positions itself
 
 
-_BWD_MODES = ("sum", "noop", "concat_linear", "mean")
+_BWD_MODES = ("sum", "noop", "concat_linear", "mean", "concat")
 
 
 class _EmbedMixFn(torch.autograd.Function):
@@ -512,6 +518,8 @@ def embed_mix_backward(grad_out: torch.Tensor, tokens: torch.Tensor, tok_table: 
         if out["byte_table"] is None:
             out["byte_table"] = torch.zeros_like(bt, dtype=torch.float32)
         gr.d_byte_table = capi.ptr(out["byte_table"])
+    if m == capi.MIX_CONCAT:
+        d.model_dim = tt.shape[1] + int(bpt) * bt.shape[1]
     if m == capi.MIX_CONCAT_LINEAR:
         w = _contig(weight, dt, "weight")
         keep.append(w)
@@ -555,7 +563,7 @@ def embed_mix_backward(grad_out: torch.Tensor, tokens: torch.Tensor, tok_table: 
 def embed_mix(tokens: torch.Tensor, tok_table: torch.Tensor, byte_table: torch.Tensor | None = None, *,
               scale_tok: torch.Tensor | None = None, scale_byte: torch.Tensor | None = None, **kw):
     """The fused front-end (see `_embed_mix_fwd` for the arguments).  With autograd enabled and
-    differentiable parameters it records one backward node: modes "sum", "noop", "concat_linear" with
+    differentiable parameters it records one backward node: modes "sum", "noop", "concat", "concat_linear" with
     float32 or bfloat16 tables; "mean" without an output norm.  Anything else raises here,
     at forward time, rather than in backward()."""
     params = (tok_table, byte_table, scale_tok, scale_byte, kw.get("weight"), kw.get("bias"))

@@ -672,6 +672,35 @@ class SumFrontEnd(nn.Module):
                                _f32(self.embed_bytes.weight, "byte table"), mode="sum", bpt=self.bpt, **kw)
 
 
+class ConcatFrontEnd(nn.Module):
+    """``x = norm(cat([embed_tokens(tok), embed_bytes(byte_0), ..., embed_bytes(byte_{bpt-1})], -1))``: "MoT via pure
+    concatenation" (runs/711_*.py:224-232, call site 314-316; runs 712 and 713 reuse it), one fused launch forward and one
+    backward.  model_dim = token_dim + bytes_per_token * byte_dim; there is no weight.  Per-token byte semantics as in
+    SumFrontEnd (SURVEY section 7, quirk iii).  The attribute names, and so the state-dict keys, are run 711's."""
+
+    def __init__(self, token_vocab_size: int, byte_vocab_size: int, token_dim: int, byte_dim: int, bytes_per_token: int = 16,
+                 ttb=None, pad_byte: int = 456, eot_byte: int = 457):
+        super().__init__()
+        self.embed_tokens = nn.Embedding(token_vocab_size, token_dim)
+        self.embed_bytes = nn.Embedding(byte_vocab_size, byte_dim)
+        self.bpt, self.pad_byte, self.eot_byte = bytes_per_token, pad_byte, eot_byte
+        self.model_dim = token_dim + bytes_per_token * byte_dim
+        self.register_buffer("ttb", _table_of(ttb).clone() if ttb is not None else None, persistent=False)
+
+    def forward(self, token_inputs: Tensor, byte_inputs: Tensor | None = None) -> Tensor:
+        """token_inputs (T,) or (B,T); byte_inputs (.., T*bpt) per-token-ordered pulled ids, or None to
+        produce them in-kernel from the attached token->byte table."""
+        kw = dict(norm_out=True)
+        if byte_inputs is None:
+            if self.ttb is None:
+                raise ValueError("ConcatFrontEnd: pass byte_inputs or construct the module with a token->byte table (ttb)")
+            kw.update(ttb=self.ttb, pull="left", pad_byte=self.pad_byte, eot_byte=self.eot_byte)
+        else:
+            kw.update(ids_a=byte_inputs.to(torch.int64).reshape(1 if token_inputs.ndim == 1 else token_inputs.shape[0], -1))
+        return F_mot.embed_mix(token_inputs, _f32(self.embed_tokens.weight, "token table"),
+                               _f32(self.embed_bytes.weight, "byte table"), mode="concat", bpt=self.bpt, **kw)
+
+
 # ------------------------------------------------------------------------------------------------
 # Llama character mixer (inference/inference.py): BASELINE config 5's front-end
 # ------------------------------------------------------------------------------------------------
