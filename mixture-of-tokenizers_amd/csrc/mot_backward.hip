@@ -1,4 +1,7 @@
-// mot_backward.hip -- backward of the fused front-end for the gather + sum family (SUM, NOOP):
+// mot_backward.hip -- the table-gradient scatter of the fused front-end's backward: the four scatter kernels, the choice
+// between them (run_scatter) and the entry launch_embed_mix_bwd (called by mot_capi.hip and the cross-attention backward
+// of mot_attn.hip).  SUM, NOOP and CONCAT are whole here; CONCAT_LINEAR (mot_bwd_linear.hip) and MEAN (mot_bwd_mean.hip)
+// compute their dense parts and come back through run_scatter (mot_bwd.hpp).  The counting sort is mot_group.hip.
 // dL/dx -> dL/d{token table, byte table, learned scalars}, what autograd computes for
 // norm(embed_tokens(tok) + concat_k embed_bytes(byte_k)) and its variants
 // (modded-nanogpt/runs/71_*.py:227-230, 312-314; 71041: 311-313; 71081: 302-315;
@@ -29,7 +32,7 @@
 
 #include <type_traits>
 
-#include "mot_mix.hpp"
+#include "mot_bwd.hpp"
 
 namespace mot {
 
@@ -44,48 +47,20 @@ __device__ __forceinline__ void seg_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
-// MOT_MIX_CONCAT (x = norm(cat(a, b_*)), runs/711_*.py:224-232) shares the split row layout [token part | byte part] of the
-// CONCAT_LINEAR scatter (there the row is du = dy.W) and, like SUM, carries its own output norm: the row IS the mixed row.
-constexpr bool split_row(int mode) { return mode == MOT_MIX_CONCAT_LINEAR || mode == MOT_MIX_CONCAT; }
-constexpr bool mixes_bytes(int mode) { return mode == MOT_MIX_SUM || mode == MOT_MIX_CONCAT; }   // the byte rows are part of the normed row
-
 constexpr int kBwdThreads = 512;  // 8 waves, 2 per SIMD: a 256-register budget per lane
 constexpr int kBwdWaves = kBwdThreads / 64;
 constexpr int kWindow = 64;  // sorted positions per wave work item
 
-struct BwdArgs {
-    const int32_t *tokens;
-    int64_t n_tokens;
-    int bpt;
-    const int64_t *ids_a, *ids_b;
-    const float *tok_table;
-    int64_t tok_rows;
-    int D;
-    const float *byte_table;
-    int64_t byte_rows;
-    int Db;
-    int norm_tok, norm_byte, norm_out;
-    float eps;
-    const float *scale_tok, *scale_byte;
-    const float *byte_rnorm;
-    const float *grad_out;
-    float *d_tok, *d_byte, *d_scale_tok, *d_scale_byte;
-    uint32_t *status;
-    // layout of one gradient row of D elements: token part [tok_lo, tok_lo+Dt), byte part [byte_lo, byte_lo+bpt*Db).
-    // SUM: both parts span the whole row (x = a + concat b); CONCAT_LINEAR: they are the two halves of du = dy.W
-    int Dt, tok_lo, byte_lo, nbk;
-    // byte-table gradient privatised in LDS as 64-bit fixed point: rows [0, priv_lo) and [priv_hi0, byte_rows) have a slot
-    // (everything when the table fits; otherwise the raw byte values and the trailing specials such as pad / eot)
-    int priv_lo, priv_hi0, priv_rows;
-    const int32_t *pos_sorted;  // token positions ordered by token id
-    const int32_t *tok_sorted;  // their (clamped) token ids
-    int in_bf16;  // tables and grad_out are bf16 (gradients are accumulated and returned in fp32 either way)
-    // lane-contiguous kernel only (the two halves of the CONCAT_LINEAR scatter): elements between gradient rows when they are columns of
-    // a wider matrix (0: D), and "no token table" (SUM over byte slots only: nothing is read from or added to a token table)
-    int g_ld, no_tok;
-    int slot0;    // first byte slot of this pass (its ids are ids[n * bpt + slot0 + ...]): the byte part taken in column blocks
-    int abl;  // dev-only timing ablations (MOT_DEV_ABLATION builds): 1 no LDS byte adds, 2 no token-row flush, 4 no wave sums
-};
+// One launch of a scatter kernel: the kernel's dynamic-LDS limit is raised once per (instantiation, device), then `blocks`
+// workgroups of `threads` go out, at most one per CU (the kernels are persistent: their waves stride over the sorted positions).
+template <auto Kernel>
+static int launch_scatter(const BwdArgs &A, size_t lds, hipStream_t stream, int threads, int64_t blocks, const char *name) {
+    static std::atomic<uint64_t> lds_ok{0};   // per-device bits
+    if (int rc_lds = ensure_max_dyn_lds((const void *)Kernel, lds_ok, name)) return rc_lds;
+    if (blocks > 256) blocks = 256;
+    hipLaunchKernelGGL(Kernel, dim3((unsigned)blocks), dim3(threads), lds, stream, A);
+    return check_launch(name);
+}
 
 // element i of a float or bf16 array (uniform choice per launch)
 __device__ __forceinline__ float ld_in(const float *base, int64_t i, int bf16) {
@@ -1057,20 +1032,11 @@ static bool lc_layout(const BwdArgs &A) {
     return ne == 4 || ne == 8 || ne == 12 || ne == 16;   // 1024-thread workgroups cap a lane at 128 registers: NE 24 / 32 would spill
 }
 
-template <int MODE, int NE, bool DUAL, typename T>
-static int launch_bwd_lc_tt(const BwdArgs &A, size_t lds, hipStream_t stream);
 template <int MODE, int NE, bool DUAL>
 static int launch_bwd_lc_t(const BwdArgs &A, size_t lds, hipStream_t stream) {
-    return A.in_bf16 ? launch_bwd_lc_tt<MODE, NE, DUAL, __bf16>(A, lds, stream) : launch_bwd_lc_tt<MODE, NE, DUAL, float>(A, lds, stream);
-}
-template <int MODE, int NE, bool DUAL, typename T>
-static int launch_bwd_lc_tt(const BwdArgs &A, size_t lds, hipStream_t stream) {
-    static std::atomic<uint64_t> lds_ok{0};   // per-device bits
-    if (int rc_lds = ensure_max_dyn_lds((const void *)embed_mix_bwd_lc_kernel<MODE, NE, DUAL, T>, lds_ok, "embed_mix_bwd_lc_kernel")) return rc_lds;
-    int64_t blocks = (A.n_tokens + 16 * kLcWaves - 1) / (16 * kLcWaves);   // >= 16 sorted positions per wave
-    if (blocks > 256) blocks = 256;   // one workgroup per CU
-    hipLaunchKernelGGL((embed_mix_bwd_lc_kernel<MODE, NE, DUAL, T>), dim3((unsigned)blocks), dim3(kLcThreads), lds, stream, A);
-    return check_launch("embed_mix_bwd_lc_kernel");
+    const int64_t blocks = (A.n_tokens + 16 * kLcWaves - 1) / (16 * kLcWaves);   // >= 16 sorted positions per wave
+    if (A.in_bf16) return launch_scatter<embed_mix_bwd_lc_kernel<MODE, NE, DUAL, __bf16>>(A, lds, stream, kLcThreads, blocks, "embed_mix_bwd_lc_kernel");
+    return launch_scatter<embed_mix_bwd_lc_kernel<MODE, NE, DUAL, float>>(A, lds, stream, kLcThreads, blocks, "embed_mix_bwd_lc_kernel");
 }
 template <int MODE, int NE>
 static int launch_bwd_lc(const BwdArgs &A, size_t lds, hipStream_t stream) {
@@ -1390,12 +1356,8 @@ static bool plain_layout(const BwdArgs &A) {
 
 template <int MODE, int NE, bool NORM_OUT, typename T>
 static int launch_bwd_plain_t(const BwdArgs &A, size_t lds, hipStream_t stream) {
-    static std::atomic<uint64_t> lds_ok{0};   // per-device bits
-    if (int rc_lds = ensure_max_dyn_lds((const void *)embed_mix_bwd_plain_kernel<MODE, NE, NORM_OUT, T>, lds_ok, "embed_mix_bwd_plain_kernel")) return rc_lds;
-    int64_t blocks = (A.n_tokens + 16 * kPlWaves - 1) / (16 * kPlWaves);   // >= 16 sorted positions per wave
-    if (blocks > 256) blocks = 256;   // one workgroup per CU
-    hipLaunchKernelGGL((embed_mix_bwd_plain_kernel<MODE, NE, NORM_OUT, T>), dim3((unsigned)blocks), dim3(kPlThreads), lds, stream, A);
-    return check_launch("embed_mix_bwd_plain_kernel");
+    const int64_t blocks = (A.n_tokens + 16 * kPlWaves - 1) / (16 * kPlWaves);   // >= 16 sorted positions per wave
+    return launch_scatter<embed_mix_bwd_plain_kernel<MODE, NE, NORM_OUT, T>>(A, lds, stream, kPlThreads, blocks, "embed_mix_bwd_plain_kernel");
 }
 template <int MODE, int NE>
 static int launch_bwd_plain(const BwdArgs &A, size_t lds, hipStream_t stream) {
@@ -1416,139 +1378,16 @@ static int dispatch_ne_plain(const BwdArgs &A, size_t lds, hipStream_t stream) {
     }
 }
 
-// ---- grouping of the token positions by (clamped) token id: a counting sort in three small kernels.
-// bwd_rank_kernel: a workgroup sorts (token << 11 | index) for 2048 positions in LDS (bitonic), so equal tokens become
-// runs; the head of a run reserves the run's places in the token's group with ONE atomicAdd(counts[token], length)
-// (a hot token costs one atomic per workgroup, not one per occurrence) and every position gets its rank in the group.
-// bwd_scan_kernel: group starts.  bwd_place_kernel: pos_sorted[start[token] + rank] = position (no atomics).
-constexpr int kRankThreads = 512;
-__device__ __forceinline__ int lower_bound_u32(const uint32_t *a, int n, uint32_t v) {   // first index with a[i] >= v
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (a[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-__global__ __launch_bounds__(kThreads) void zero_i32_kernel(int32_t *__restrict__ p, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads) p[i] = 0;
-}
-
-int launch_zero_words(void *p, int64_t n_words, hipStream_t stream) {
-    if (n_words <= 0) return MOT_OK;
-    int64_t blocks = (n_words + kThreads - 1) / kThreads;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(zero_i32_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, stream, (int32_t *)p, n_words);
-    return check_launch("zero_i32_kernel");
-}
-
-template <int kRankChunk>   // positions per workgroup: 2048, or 512 when there are too few positions to fill the chip with 2048s
-__global__ __launch_bounds__(kRankThreads) void bwd_rank_kernel(const int32_t *__restrict__ tokens, int64_t n, int64_t rows,
-                                                                int32_t *__restrict__ counts, int32_t *__restrict__ rank,
-                                                                uint32_t *status) {
-    __shared__ uint32_t skey[kRankChunk];
-    __shared__ int32_t runbase[kRankChunk];
-    const int tid = threadIdx.x;
-    const int64_t base = (int64_t)blockIdx.x * kRankChunk;
-    for (int i = tid; i < kRankChunk; i += kRankThreads) {
-        uint32_t key = 0xffffffffu;
-        if (base + i < n) {
-            uint32_t t = (uint32_t)tokens[base + i];
-            if ((uint64_t)t >= (uint64_t)rows) { if (status) atomicOr(status, kStatusTokenOor); t = 0; }
-            key = (t << 11) | (uint32_t)i;
-        }
-        skey[i] = key;
-    }
-    __syncthreads();
-    for (int k = 2; k <= kRankChunk; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int p = tid; p < kRankChunk / 2; p += kRankThreads) {
-                const int i = ((p & ~(j - 1)) << 1) | (p & (j - 1)), ixj = i | j;
-                const uint32_t x = skey[i], y = skey[ixj];
-                if ((x > y) == ((i & k) == 0)) { skey[i] = y; skey[ixj] = x; }
-            }
-            __syncthreads();
-        }
-    constexpr int kPer = kRankChunk / kRankThreads;
-    int head[kPer];
-#pragma unroll
-    for (int r = 0; r < kPer; ++r) {
-        const int si = tid + r * kRankThreads;
-        const uint32_t key = skey[si];
-        head[r] = -1;
-        if (key == 0xffffffffu) continue;
-        const uint32_t tok = key >> 11;
-        const int h = (si == 0 || (skey[si - 1] >> 11) != tok) ? si : lower_bound_u32(skey, si, tok << 11);
-        head[r] = h;
-        if (h == si) {
-            const int e = lower_bound_u32(skey, kRankChunk, (tok + 1) << 11);   // padding keys are larger than any token's
-            runbase[si] = atomicAdd(&counts[tok], e - si);
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < kPer; ++r) {
-        const int si = tid + r * kRankThreads;
-        if (head[r] < 0) continue;
-        rank[base + (skey[si] & 2047)] = runbase[head[r]] + (si - head[r]);
-    }
-}
-
-__global__ __launch_bounds__(kThreads) void bwd_place_kernel(const int32_t *__restrict__ tokens, int64_t n, int64_t rows,
-                                                             const int32_t *__restrict__ starts, const int32_t *__restrict__ rank,
-                                                             int32_t *__restrict__ pos_sorted, int32_t *__restrict__ tok_sorted) {
-    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads) {
-        int t = tokens[i];
-        if ((uint64_t)(uint32_t)t >= (uint64_t)rows) t = 0;
-        const int32_t at = starts[t] + rank[i];
-        pos_sorted[at] = (int32_t)i;
-        tok_sorted[at] = t;
-    }
-}
-
-// exclusive scan of counts[0..rows) into starts.  Workgroup b owns the 1024 counts of tile b: it first sums everything in
-// front of its tile (coalesced reads of an L2-resident array, at most a few hundred KB), then scans its own tile.
-__global__ __launch_bounds__(1024) void bwd_scan_kernel(const int32_t *__restrict__ counts, int64_t rows,
-                                                        int32_t *__restrict__ starts) {
-    __shared__ int32_t wsum[16];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t t0 = (int64_t)blockIdx.x * 1024;
-    int32_t before = 0;
-    for (int64_t i = tid; i < t0; i += 1024) before += counts[i];
-    const int64_t i = t0 + tid;
-    const int32_t own = i < rows ? counts[i] : 0;
-    const int32_t incl = wave_incl_add(own, lane);
-    const int32_t bsum = wave_incl_add(before, lane);
-    if (lane == 63) wsum[wave] = incl + bsum;     // this wave's share of (everything before the tile + the tile)
-    __syncthreads();
-    int32_t off = incl - own;
-    for (int w = 0; w < 16; ++w) off += w < wave ? wsum[w] : 0;
-    // the `before` parts of the later waves belong in front of every element of the tile as well
-    __shared__ int32_t bpart[16];
-    if (lane == 63) bpart[wave] = bsum;
-    __syncthreads();
-    for (int w = wave; w < 16; ++w) off += bpart[w];
-    if (i < rows) starts[i] = off;
-}
-
 template <int MODE, int NE>
 static int launch_bwd(const BwdArgs &A, size_t lds, hipStream_t stream) {
-    static std::atomic<uint64_t> lds_ok{0};   // per-device bits
-    if (int rc_lds = ensure_max_dyn_lds((const void *)embed_mix_bwd_kernel<MODE, NE>, lds_ok, "embed_mix_bwd_kernel")) return rc_lds;
-    int64_t blocks = ((A.n_tokens + kWindow - 1) / kWindow + kBwdWaves - 1) / kBwdWaves;
-    if (blocks > 256) blocks = 256;  // one persistent workgroup per CU
-    hipLaunchKernelGGL((embed_mix_bwd_kernel<MODE, NE>), dim3((unsigned)blocks), dim3(kBwdThreads), lds, stream, A);
-    return check_launch("embed_mix_bwd_kernel");
+    const int64_t blocks = ((A.n_tokens + kWindow - 1) / kWindow + kBwdWaves - 1) / kBwdWaves;   // one window of sorted positions per wave
+    return launch_scatter<embed_mix_bwd_kernel<MODE, NE>>(A, lds, stream, kBwdThreads, blocks, "embed_mix_bwd_kernel");
 }
 
 template <int MODE, int NE, bool BF>
 static int launch_bwd_full_t(const BwdArgs &A, size_t lds, hipStream_t stream) {
-    static std::atomic<uint64_t> lds_ok{0};   // per-device bits
-    if (int rc_lds = ensure_max_dyn_lds((const void *)embed_mix_bwd_full_kernel<MODE, NE, BF>, lds_ok, "embed_mix_bwd_full_kernel")) return rc_lds;
-    int64_t blocks = (A.n_tokens + 16 * kBwdWaves - 1) / (16 * kBwdWaves);   // >= 16 sorted positions per wave
-    if (blocks > 256) blocks = 256;   // one workgroup per CU
-    hipLaunchKernelGGL((embed_mix_bwd_full_kernel<MODE, NE, BF>), dim3((unsigned)blocks), dim3(kBwdThreads), lds, stream, A);
-    return check_launch("embed_mix_bwd_full_kernel");
+    const int64_t blocks = (A.n_tokens + 16 * kBwdWaves - 1) / (16 * kBwdWaves);   // >= 16 sorted positions per wave
+    return launch_scatter<embed_mix_bwd_full_kernel<MODE, NE, BF>>(A, lds, stream, kBwdThreads, blocks, "embed_mix_bwd_full_kernel");
 }
 
 template <int MODE, int NE>
@@ -1606,38 +1445,10 @@ static int dispatch_ne(const BwdArgs &A, size_t lds, hipStream_t stream) {
 }
 
 // ------------------------------------------------------------------------------------------
-// scatter stage shared by all modes: sort the positions by token id, then embed_mix_bwd_kernel.
+// scatter stage shared by all modes: sort the positions by token id (launch_group_positions, mot_group.hip), then embed_mix_bwd_kernel.
 // `ws_ints` = [counts: tok_rows][starts: tok_rows][rank: N][pos_sorted: N][tok_sorted: N] (int32).
 // ------------------------------------------------------------------------------------------
-// The counting sort by itself: positions 0..n-1 grouped by ids[position] (clamped into [0, rows)); `ws_ints` holds
-// group_positions_ws_ints(n, rows) int32.  *pos_sorted / *id_sorted point into it.
-size_t group_positions_ws_ints(int64_t n, int64_t rows) { return 2 * (size_t)rows + 3 * (size_t)n; }
-int launch_group_positions(const int32_t *ids, int64_t n, int64_t rows, int32_t *ws_ints, const int32_t **pos_sorted_out, const int32_t **id_sorted_out,
-                           uint32_t *status, hipStream_t stream) {
-    if (rows >= (1 << 21) - 1) return set_error(MOT_EUNSUPPORTED, "group_positions: %lld rows (>= 2^21 - 1) are not built", (long long)rows);
-    int32_t *counts = ws_ints, *starts = counts + rows, *rank = starts + rows, *pos_sorted = rank + n, *id_sorted = pos_sorted + n;
-    int rc;
-    if ((rc = launch_zero_words(counts, rows, stream))) return rc;
-    const int rank_chunk = n >= 256 * 2048 ? 2048 : 512;
-    const int64_t rb = (n + rank_chunk - 1) / rank_chunk;
-    int64_t pb = (n + kThreads - 1) / kThreads;
-    if (pb > 2048) pb = 2048;
-    if (rb > 0x7fffffffLL) return set_error(MOT_EUNSUPPORTED, "group_positions: too many positions");
-    if (n > 0) {
-        if (rank_chunk == 2048)
-            hipLaunchKernelGGL(bwd_rank_kernel<2048>, dim3((unsigned)rb), dim3(kRankThreads), 0, stream, ids, n, rows, counts, rank, status);
-        else
-            hipLaunchKernelGGL(bwd_rank_kernel<512>, dim3((unsigned)rb), dim3(kRankThreads), 0, stream, ids, n, rows, counts, rank, status);
-        hipLaunchKernelGGL(bwd_scan_kernel, dim3((unsigned)((rows + 1023) / 1024)), dim3(1024), 0, stream, counts, rows, starts);
-        hipLaunchKernelGGL(bwd_place_kernel, dim3((unsigned)pb), dim3(kThreads), 0, stream, ids, n, rows, starts, rank, pos_sorted, id_sorted);
-        if ((rc = check_launch("group_positions kernels"))) return rc;
-    }
-    *pos_sorted_out = pos_sorted;
-    *id_sorted_out = id_sorted;
-    return MOT_OK;
-}
-
-static size_t scatter_ws_ints(const MotEmbedMixDesc &d) { return 2 * (size_t)d.tok_rows + 3 * (size_t)(d.n_rows * d.tokens_per_row); }
+size_t scatter_ws_ints(const MotEmbedMixDesc &d) { return 2 * (size_t)d.tok_rows + 3 * (size_t)(d.n_rows * d.tokens_per_row); }
 
 template <int MODE>
 static int run_scatter(BwdArgs &A, const MotEmbedMixDesc &d, int32_t *ws_ints, float *rnorm_ws, hipStream_t stream) {
@@ -1686,7 +1497,18 @@ static int run_scatter(BwdArgs &A, const MotEmbedMixDesc &d, int32_t *ws_ints, f
     return dispatch_ne<MODE>(A, lds, stream);
 }
 
-static void fill_bwd_args(BwdArgs &A, const MotEmbedMixDesc &d, const MotEmbedMixGrads &gr) {
+// what the other backward units see of the scatter (mot_bwd.hpp): the kernels are instantiated in this unit only
+int run_scatter(int mode, BwdArgs &A, const MotEmbedMixDesc &d, int32_t *ws_ints, float *rnorm_ws, hipStream_t stream) {
+    switch (mode) {
+        case MOT_MIX_SUM: return run_scatter<MOT_MIX_SUM>(A, d, ws_ints, rnorm_ws, stream);
+        case MOT_MIX_CONCAT_LINEAR: return run_scatter<MOT_MIX_CONCAT_LINEAR>(A, d, ws_ints, rnorm_ws, stream);
+        case MOT_MIX_CONCAT: return run_scatter<MOT_MIX_CONCAT>(A, d, ws_ints, rnorm_ws, stream);
+        default: return run_scatter<MOT_MIX_NOOP>(A, d, ws_ints, rnorm_ws, stream);
+    }
+}
+bool lc_layout(int mode, const BwdArgs &A) { return mode == MOT_MIX_SUM ? lc_layout<MOT_MIX_SUM>(A) : lc_layout<MOT_MIX_NOOP>(A); }
+
+void fill_bwd_args(BwdArgs &A, const MotEmbedMixDesc &d, const MotEmbedMixGrads &gr) {
     A.tokens = d.tokens; A.n_tokens = d.n_rows * d.tokens_per_row; A.bpt = d.bpt;
     A.ids_a = d.ids_a; A.ids_b = d.ids_b;
     A.tok_table = (const float *)d.tok_table; A.tok_rows = d.tok_rows; A.D = d.tok_dim;
@@ -1710,1053 +1532,12 @@ static void fill_bwd_args(BwdArgs &A, const MotEmbedMixDesc &d, const MotEmbedMi
     if (d.mode == MOT_MIX_CONCAT) { A.D = d.tok_dim + A.nbk; A.byte_lo = d.tok_dim; }   // the row is cat(token row, byte rows)
 }
 
-// ==========================================================================================
-// CONCAT_LINEAR backward:  x = rms_norm?(y), y = W u + bias, u = cat(a, b_*)
-//   dy = r_y (g - x mean(g x))                      dy_kernel (one wave per row)
-//   du = dy . W          (N x Dm) @ (Dm x K)        the forward MFMA kernel with dy as dense "token rows";
-//                                                   W in nn.Linear layout IS the k-major operand it wants
-//   dW += dy^T . u       (Dm x N) @ (N x K)         gemm_tn_kernel: split over tokens, fp32 MFMA, atomic accumulate;
-//                                                   u = the seam tensors (gather_rows with the norms/scales applied)
-//   dbias += colsum(dy)                             colsum_kernel
-//   table gradients: the scatter stage above on du (row layout = the concat layout)
-// ==========================================================================================
-__global__ __launch_bounds__(kThreads) void dy_kernel(const float *__restrict__ g, const float *__restrict__ x,
-                                                      const float *__restrict__ rnorm, int64_t n, int Dm, float *__restrict__ dy) {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
-    if (r >= n) return;
-    const float *gr = g + r * Dm, *xr = x + r * Dm;
-    float m = 0.f;
-    for (int j = lane; j < Dm; j += 64) m += gr[j] * xr[j];
-    m = wave_sum(m) / (float)Dm;
-    const float ry = rnorm[r];
-    for (int j = lane; j < Dm; j += 64) dy[r * Dm + j] = ry * (gr[j] - xr[j] * m);
-}
-
-// the same from bf16 g and x, result in bf16 (the bf16 route never needs an fp32 dy): Dm a multiple of 8, <= 4096
-__global__ __launch_bounds__(kThreads) void dy16_kernel(const __bf16 *__restrict__ g, const __bf16 *__restrict__ x, const float *__restrict__ rnorm, int64_t n,
-                                                        int Dm, __bf16 *__restrict__ dy) {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
-    if (r >= n) return;
-    const __bf16 *gr = g + r * Dm, *xr = x + r * Dm;
-    float8v gv[8], xv[8];
-    float m = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int c = 8 * (lane + 64 * i);
-        gv[i] = (float8v)(0.f); xv[i] = (float8v)(0.f);
-        if (c < Dm) {
-            gv[i] = Elem<__bf16>::loadv(gr + c);
-            xv[i] = Elem<__bf16>::loadv(xr + c);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) m += gv[i][e] * xv[i][e];
-        }
-    }
-    m = wave_sum(m) / (float)Dm;
-    const float ry = rnorm[r];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int c = 8 * (lane + 64 * i);
-        if (c < Dm) Elem<__bf16>::storev_nt(dy + r * Dm + c, (gv[i] - xv[i] * m) * ry);
-    }
-}
-
-__global__ __launch_bounds__(kThreads) void colsum_kernel(const float *__restrict__ a, int64_t n, int cols, float *__restrict__ out) {
-    // each workgroup sums a strip of rows for every column, then one atomic per column
-    const int64_t rows_per = (n + gridDim.x - 1) / gridDim.x, lo = blockIdx.x * rows_per, hi = min(n, lo + rows_per);
-    for (int c = threadIdx.x; c < cols; c += kThreads) {
-        float s = 0.f;
-        for (int64_t r = lo; r < hi; ++r) s += a[r * cols + c];
-        if (lo < hi) atomicAdd(out + c, s);
-    }
-}
-
-__global__ __launch_bounds__(kThreads) void iota_kernel(int32_t *p, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads) p[i] = (int32_t)i;
-}
-
-__global__ __launch_bounds__(kThreads) void pad_copy_kernel(const float *__restrict__ src, int rows, int cols, float *__restrict__ dst,
-                                                            int rows_pad, int cols_pad) {
-    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < (int64_t)rows_pad * cols_pad; i += (int64_t)gridDim.x * kThreads) {
-        const int r = (int)(i / cols_pad), c = (int)(i - (int64_t)r * cols_pad);
-        dst[i] = (r < rows && c < cols) ? src[(int64_t)r * cols + c] : 0.f;
-    }
-}
-
-int launch_pad_copy(const float *src, int rows, int cols, float *dst, int rows_pad, int cols_pad, hipStream_t stream) {
-    hipLaunchKernelGGL(pad_copy_kernel, dim3(512), dim3(kThreads), 0, stream, src, rows, cols, dst, rows_pad, cols_pad);
-    return check_launch("pad_copy_kernel");
-}
-
-// C[j][k] += sum_n A[n][j] * B[n][k]   (A: n x M, B: n x Nc, C: M x Nc with leading dimension ldc), fp32 MFMA.
-// Workgroup = 128 x 128 output block (4 waves as 2 x 2, each 64 x 64 = 2 x 2 tiles of 32 x 32) over one
-// slice of the rows; 16 rows per step, double-buffered LDS, rows ARE the MFMA k index so both operands are
-// staged in their natural row-major layout.  Partial blocks are accumulated with float atomics
-// (128-byte contiguous segments per instruction).
-typedef float f32x16b __attribute__((ext_vector_type(16)));
-__global__ __launch_bounds__(kThreads) void gemm_tn_kernel(const float *__restrict__ A_, int lda, int M, const float *__restrict__ B_, int ldb,
-                                                           int Nc, int64_t n, int64_t rows_per_split, float *__restrict__ C, int ldc) {
-    __shared__ __attribute__((aligned(16))) float lA[2][16 * 128], lB[2][16 * 128];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, li = lane & 31;
-    const int j0 = blockIdx.x * 128, k0 = blockIdx.y * 128;
-    const int64_t r0 = (int64_t)blockIdx.z * rows_per_split, r1 = min(n, r0 + rows_per_split);
-    const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
-    f32x16b acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-    // staging role: 16 rows x 32 float4 per operand = 512 float4 -> 2 per thread
-    float4v ra[2], rb[2];
-    const bool va = (lda & 3) == 0 && ((uintptr_t)A_ & 15) == 0, vb = (ldb & 3) == 0 && ((uintptr_t)B_ & 15) == 0;   // 16-byte loads allowed
-    auto load_stage = [&](int64_t r) {
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            const int q = p * kThreads + tid, row = q >> 5, c4 = (q & 31) * 4;
-            const int64_t rr = r + row;
-            ra[p] = (float4v)(0.f); rb[p] = (float4v)(0.f);
-            if (rr < r1) {
-                const float *pa = A_ + rr * lda + j0 + c4, *pb = B_ + rr * ldb + k0 + c4;
-                if (va && j0 + c4 + 3 < M) ra[p] = *(const float4v *)pa;
-                else
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)   // element-wise guards keep ragged right edges correct
-                        if (j0 + c4 + e < M) ra[p][e] = pa[e];
-                if (vb && k0 + c4 + 3 < Nc) rb[p] = *(const float4v *)pb;
-                else
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (k0 + c4 + e < Nc) rb[p][e] = pb[e];
-            }
-        }
-    };
-    auto store_stage = [&](int buf) {
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            const int q = p * kThreads + tid;
-            *(float4v *)(&lA[buf][q * 4]) = ra[p];
-            *(float4v *)(&lB[buf][q * 4]) = rb[p];
-        }
-    };
-    load_stage(r0);
-    store_stage(0);
-    __syncthreads();
-    int buf = 0;
-    for (int64_t r = r0; r < r1; r += 16, buf ^= 1) {
-        const bool more = r + 16 < r1;
-        if (more) load_stage(r + 16);
-#pragma unroll
-        for (int kk = 0; kk < 16; kk += 2) {
-            const float a0 = lA[buf][(kk + h) * 128 + wm + li], a1 = lA[buf][(kk + h) * 128 + wm + 32 + li];
-            const float b0 = lB[buf][(kk + h) * 128 + wn + li], b1 = lB[buf][(kk + h) * 128 + wn + 32 + li];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-        }
-        if (more) store_stage(buf ^ 1);
-        __syncthreads();
-    }
-    // C/D layout: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5); A is the "row" (j) operand
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int j = j0 + wm + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * h, k = k0 + wn + b * 32 + li;
-                if (j < M && k < Nc) atomicAdd(C + (int64_t)j * ldc + k, acc[a][b][r]);
-            }
-}
-
-int launch_gemm_tn(const float *A_, int lda, int M, const float *B_, int ldb, int Nc, int64_t n, float *C, int ldc, hipStream_t stream) {
-    if (M <= 0 || Nc <= 0 || n <= 0) return MOT_OK;
-    const int gx = (M + 127) / 128, gy = (Nc + 127) / 128;
-    int64_t splits = (1024 + gx * gy - 1) / (gx * gy);                  // ~1024 workgroups in total
-    int64_t rows_per = ((n + splits - 1) / splits + 15) / 16 * 16;     // whole 16-row steps
-    if (rows_per < 256) rows_per = 256;
-    splits = (n + rows_per - 1) / rows_per;
-    hipLaunchKernelGGL(gemm_tn_kernel, dim3((unsigned)gx, (unsigned)gy, (unsigned)splits), dim3(kThreads), 0, stream, A_, lda, M, B_, ldb,
-                       Nc, n, rows_per, C, ldc);
-    return check_launch("gemm_tn_kernel");
-}
-
-// C[n][c] = sum_r A[n][r] * (BT ? B[c][r] : B[r][c])   (A: n x R rows, C: n x Nc; leading dimensions lda / ldb / ldc), fp32 MFMA.
-// Same block shape and inner loop as gemm_tn_kernel -- 128 x 128 output block, 16 reduction indices per step, both operands in
-// LDS as [reduction index][block row / column], one conflict-free ds_read_b32 per MFMA operand -- with the operand whose rows
-// are contiguous along r (A always, B when BT) transposed on its way into LDS: a lane takes 4 consecutive r of one row, 4
-// lanes one 64-byte row segment, and writes them as four ds_write_b32 down a padded column.  The reduction is whole
-// inside the workgroup (plain stores).  The fused gather + norm kernel (mot_linear.hip) runs its dense-row mode at 48 % of
-// the fp32 MFMA peak; this loop reaches ~75 %.
-template <bool BT>
-__device__ __forceinline__ void gemm_rows_body(const float *__restrict__ A_, int lda, int64_t n, const float *__restrict__ B_, int ldb,
-                                               int R, int Nc, float *__restrict__ C, int ldc, const float *__restrict__ bias, int accumulate,
-                                               bool plain_order = false) {
-    // transposed operands sit in LDS with a row stride of 132 floats: the 4 lanes that share a source row (coalesced 64-byte
-    // reads) then write to banks 16 apart, two lanes per bank -- the minimum for 64 dword writes
-    constexpr int LDA = 132, LDB = BT ? 132 : 128;
-    __shared__ __attribute__((aligned(16))) float lA[2][16 * LDA], lB[2][16 * LDB];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, li = lane & 31;
-    // XCD-aware block order (1-D grid, workgroup ids round-robin over the 8 XCDs): an XCD walks all column blocks of a row panel
-    // back to back, so the panel of A is fetched into that XCD's L2 once instead of once per column block
-    const int64_t gx = (n + 127) / 128;
-    const int gy = (Nc + 127) / 128;
-    // (plain_order: gx * gy blocks, no padding -- the sliced few-row launches, where the padded panels were most of the workgroups and
-    //  their dispatch most of the time: 132 rows = 2 panels padded to 8, 2816 workgroups of which 704 work, 100 us)
-    const int64_t bid = blockIdx.x, seq = plain_order ? bid : bid >> 3, panel = plain_order ? bid / gy : (seq / gy) * 8 + (bid & 7);
-    if (panel >= gx) return;   // the grid is padded to whole groups of 8 panels
-    const int64_t j0 = panel * 128;
-    const int k0 = (int)(seq % gy) * 128;
-    const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
-    // acc is the MFMA accumulator of kFold reduction steps at a time; it is then folded into `sum` with vector adds and
-    // restarted, so no fp32 summation chain is longer than 8 * kFold MFMA steps (blocked summation, like the reference's
-    // CPU sgemm: one chain over K = 768 ends up 4x as far from the float64 result as the reference, the parity bar is 2x)
-    constexpr int kFold = 8;
-    f32x16b acc[2][2], sum[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { acc[a][b][r] = 0.f; sum[a][b][r] = 0.f; }
-    const bool va = (lda & 3) == 0 && ((uintptr_t)A_ & 15) == 0, vb = (ldb & 3) == 0 && ((uintptr_t)B_ & 15) == 0;
-    float4v ra[2], rb[2];
-    // rows-contiguous-along-r operand: thread -> (row = q >> 2, 4 consecutive r starting at (q & 3) * 4): 4 lanes read one 64-byte row segment
-    auto load_t = [&](const float *P, int ld, int64_t row0, int64_t rows, bool vec, int r, float4v (&dst)[2]) {
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            const int q = p * kThreads + tid, row = q >> 2, c4 = (q & 3) * 4;
-            dst[p] = (float4v)(0.f);
-            if (row0 + row < rows) {
-                const float *src = P + (row0 + row) * ld + r + c4;
-                if (vec && r + c4 + 3 < R) dst[p] = *(const float4v *)src;
-                else
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (r + c4 + e < R) dst[p][e] = src[e];
-            }
-        }
-    };
-    auto store_t = [&](float *L, const float4v (&srcv)[2]) {
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            const int q = p * kThreads + tid, row = q >> 2, c4 = (q & 3) * 4;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) L[(c4 + e) * 132 + row] = srcv[p][e];
-        }
-    };
-    auto load_stage = [&](int r) {
-        load_t(A_, lda, j0, n, va, r, ra);
-        if (BT) {
-            load_t(B_, ldb, k0, Nc, vb, r, rb);
-        } else {
-#pragma unroll
-            for (int p = 0; p < 2; ++p) {   // natural layout: 16 reduction rows x 32 float4
-                const int q = p * kThreads + tid, row = q >> 5, c4 = (q & 31) * 4;
-                rb[p] = (float4v)(0.f);
-                if (r + row < R) {
-                    const float *src = B_ + (int64_t)(r + row) * ldb + k0 + c4;
-                    if (vb && k0 + c4 + 3 < Nc) rb[p] = *(const float4v *)src;
-                    else
-#pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            if (k0 + c4 + e < Nc) rb[p][e] = src[e];
-                }
-            }
-        }
-    };
-    auto store_stage = [&](int buf) {
-        store_t(lA[buf], ra);
-        if (BT) store_t(lB[buf], rb);
-        else
-#pragma unroll
-            for (int p = 0; p < 2; ++p) *(float4v *)(&lB[buf][(p * kThreads + tid) * 4]) = rb[p];
-    };
-    load_stage(0);
-    store_stage(0);
-    __syncthreads();
-    int buf = 0;
-    for (int r = 0; r < R; r += 16, buf ^= 1) {
-        const bool more = r + 16 < R;
-        if (more) load_stage(r + 16);
-#pragma unroll
-        for (int kk = 0; kk < 16; kk += 2) {
-            const float a0 = lA[buf][(kk + h) * LDA + wm + li], a1 = lA[buf][(kk + h) * LDA + wm + 32 + li];
-            const float b0 = lB[buf][(kk + h) * LDB + wn + li], b1 = lB[buf][(kk + h) * LDB + wn + 32 + li];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-        }
-        if (((r >> 4) & (kFold - 1)) == kFold - 1) {
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int b = 0; b < 2; ++b)
-#pragma unroll
-                    for (int q = 0; q < 16; ++q) { sum[a][b][q] += acc[a][b][q]; acc[a][b][q] = 0.f; }
-        }
-        if (more) store_stage(buf ^ 1);
-        __syncthreads();
-    }
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int64_t j = j0 + wm + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                const int k = k0 + wn + b * 32 + li;
-                if (j < n && k < Nc) {
-                    float v = sum[a][b][r] + acc[a][b][r];
-                    if (bias) v += bias[k];
-                    if (accumulate) v += C[j * ldc + k];
-                    C[j * ldc + k] = v;
-                }
-            }
-}
-
-// The register budget is set per variant: with B transposed the body fits 168 registers (3 waves per SIMD); with B in its
-// natural layout that cap spills inside the loop (0.92 ms instead of 0.72), so that variant runs at 2 waves per SIMD.
-// (blockIdx.y = slice of the reduction, `slice` indices long, whose block goes to C + y * part_stride: launch_gemm_rows_sliced)
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3, 4))) void gemm_rows_bt_kernel(
-    const float *__restrict__ A_, int lda, int64_t n, const float *__restrict__ B_, int ldb, int R, int Nc, float *__restrict__ C, int ldc,
-    const float *__restrict__ bias, int accumulate, int slice, int64_t part_stride) {
-    const int r0 = blockIdx.y * slice;
-    gemm_rows_body<true>(A_ + r0, lda, n, B_ + r0, ldb, slice ? min(slice, R - r0) : R, Nc, C + blockIdx.y * part_stride, ldc, bias, accumulate, slice != 0);
-}
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 4))) void gemm_rows_kernel(
-    const float *__restrict__ A_, int lda, int64_t n, const float *__restrict__ B_, int ldb, int R, int Nc, float *__restrict__ C, int ldc,
-    const float *__restrict__ bias, int accumulate, int slice, int64_t part_stride) {
-    const int r0 = blockIdx.y * slice;
-    gemm_rows_body<false>(A_ + r0, lda, n, B_ + (int64_t)r0 * ldb, ldb, slice ? min(slice, R - r0) : R, Nc, C + blockIdx.y * part_stride, ldc, bias, accumulate,
-                          slice != 0);
-}
-// C[i] = part[0][i] + part[1][i] + ... in that order (C rows ldc apart, the partial blocks dense [n][Nc])
-__global__ __launch_bounds__(kThreads) void gemm_rows_sum_slices_kernel(const float *__restrict__ part, int slices, int64_t n, int Nc, float *__restrict__ C, int ldc) {
-    const int64_t total = n * Nc;
-    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < total; i += (int64_t)gridDim.x * kThreads) {
-        float v = part[i];
-        for (int s = 1; s < slices; ++s) v += part[(int64_t)s * total + i];
-        C[(i / Nc) * ldc + i % Nc] = v;
-    }
-}
-
-// (the reduction can be cut into launches that add to C; with the in-kernel blocked summation one launch covers any K)
-constexpr int kGemmRowsPass = 1 << 30;
-int launch_gemm_rows(const float *A_, int lda, int64_t n, const float *B_, int ldb, int R, int Nc, float *C, int ldc, bool b_transposed,
-                     hipStream_t stream, const float *bias, bool accumulate) {
-    if (n <= 0 || Nc <= 0) return MOT_OK;
-    if (b_transposed && R > 0 && gemm_rows_f32_256_usable(A_, lda, n, B_, ldb, R, Nc))   // 256 x 256 blocks by LDS-DMA (mot_gemm_bf16.hip)
-        return launch_gemm_rows_f32_256(A_, lda, n, B_, ldb, R, Nc, C, ldc, bias, accumulate, stream);
-    const int64_t gx = (n + 127) / 128;
-    const int gy = (Nc + 127) / 128;
-    const int64_t blocks = (gx + 7) / 8 * 8 * gy;   // 1-D, see the block order in the kernel
-    if (blocks > 0x7fffffffLL) return set_error(MOT_EUNSUPPORTED, "gemm_rows: too many rows");
-    for (int r0 = 0; r0 < R || r0 == 0; r0 += kGemmRowsPass) {
-        const int rn = R - r0 < kGemmRowsPass ? R - r0 : kGemmRowsPass;
-        const float *a = A_ + r0, *b = b_transposed ? B_ + r0 : B_ + (int64_t)r0 * ldb;
-        if (b_transposed)
-            hipLaunchKernelGGL(gemm_rows_bt_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, stream, a, lda, n, b, ldb, rn, Nc, C, ldc,
-                               r0 ? nullptr : bias, (r0 || accumulate) ? 1 : 0, 0, (int64_t)0);
-        else
-            hipLaunchKernelGGL(gemm_rows_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, stream, a, lda, n, b, ldb, rn, Nc, C, ldc,
-                               r0 ? nullptr : bias, (r0 || accumulate) ? 1 : 0, 0, (int64_t)0);
-        if (r0 + kGemmRowsPass >= R) break;
-    }
-    return check_launch("gemm_rows_kernel");
-}
-
-// how the reduction of a few-row product is cut: slices of a multiple of 16 indices, at least 64, as many as fill the chip
-static int gemm_rows_slices(int64_t n, int R, int Nc, int *slice_len) {
-    const int64_t blocks = ((n + 127) / 128 + 7) / 8 * 8 * ((Nc + 127) / 128), live = ((n + 127) / 128) * ((Nc + 127) / 128);
-    if (n > 1024 || R < 256 || live >= 128 || blocks > 4096) return 1;
-    int want = (int)(768 / live);   // (three workgroups a CU: a step of this kernel is one exposed load latency, ~5 us of it per step measured)
-    if (want > R / 64) want = R / 64;
-    if (want > 32) want = 32;
-    if (want < 2) return 1;
-    const int len = ((R + want - 1) / want + 15) / 16 * 16;
-    *slice_len = len;
-    return (R + len - 1) / len;
-}
-size_t gemm_rows_sliced_floats(int64_t n, int R, int Nc) {
-    int len = 0;
-    const int s = gemm_rows_slices(n, R, Nc, &len);
-    return s > 1 ? (size_t)s * n * Nc : 0;
-}
-int launch_gemm_rows_sliced(const float *A_, int lda, int64_t n, const float *B_, int ldb, int R, int Nc, float *C, int ldc, bool b_transposed, float *part,
-                            size_t part_floats, hipStream_t stream) {
-    int len = 0;
-    const int slices = n > 0 && Nc > 0 ? gemm_rows_slices(n, R, Nc, &len) : 1;
-    if (slices < 2 || !part || part_floats < (size_t)slices * n * Nc) return launch_gemm_rows(A_, lda, n, B_, ldb, R, Nc, C, ldc, b_transposed, stream);
-    const int64_t blocks = ((n + 127) / 128) * ((Nc + 127) / 128);   // (plain block order in the sliced launches: no padded panels)
-    const dim3 grid((unsigned)blocks, (unsigned)slices);
-    if (b_transposed)
-        hipLaunchKernelGGL(gemm_rows_bt_kernel, grid, dim3(kThreads), 0, stream, A_, lda, n, B_, ldb, R, Nc, part, Nc, (const float *)nullptr, 0, len, n * Nc);
-    else
-        hipLaunchKernelGGL(gemm_rows_kernel, grid, dim3(kThreads), 0, stream, A_, lda, n, B_, ldb, R, Nc, part, Nc, (const float *)nullptr, 0, len, n * Nc);
-    if (int rc = check_launch("gemm_rows_kernel")) return rc;
-    const int64_t total = n * Nc;
-    hipLaunchKernelGGL(gemm_rows_sum_slices_kernel, dim3((unsigned)((total + kThreads - 1) / kThreads < 2048 ? (total + kThreads - 1) / kThreads : 2048)), dim3(kThreads), 0,
-                       stream, part, slices, n, Nc, C, ldc);
-    return check_launch("gemm_rows_sum_slices_kernel");
-}
-
-// workspace of the CONCAT backward, in floats unless noted:
-//   [rnorm: byte_rows][dy: N*Dm][du: N*K][u_tok: N*Dt][u_byte: N*bpt*Db][Wk: Dm16*K128][byte0: 4][iota: N int32][zero ids: 0]
-//   [sort ints: 3*tok_rows + N]
-struct LinBwdLayout { size_t rnorm, dy, du, utok, ubyte, wk, byte0, iota, sort, total; int Kp, Dmp; };
-static LinBwdLayout lin_bwd_layout(const MotEmbedMixDesc &d) {
-    LinBwdLayout L;
-    const size_t N = (size_t)(d.n_rows * d.tokens_per_row), K = (size_t)d.tok_dim + (size_t)d.bpt * d.byte_dim;
-    L.Kp = (int)((K + 127) / 128 * 128);            // output columns of the du GEMM, padded as the MFMA kernel pads them
-    if (L.Kp > 512 && L.Kp <= 768) L.Kp = 768; else if (L.Kp > 768) L.Kp = 1024;
-    L.Dmp = (d.model_dim + 15) / 16 * 16;
-    size_t o = 0;
-    auto take = [&](size_t n) { size_t at = o; o += (n + 3) & ~(size_t)3; return at; };
-    L.rnorm = take(d.byte_rows); L.dy = take(N * d.model_dim); L.du = take(N * K); L.utok = take(N * d.tok_dim);
-    L.ubyte = take(N * d.bpt * d.byte_dim); L.wk = take((size_t)L.Dmp * L.Kp); L.byte0 = take(4); L.iota = take(N);
-    L.sort = take(scatter_ws_ints(d)); L.total = o;
-    return L;
-}
-
-// bf16 CONCAT_LINEAR backward: the operands are widened once into fp32 workspace copies and the fp32 pipeline
-// above runs on them (fp32 MFMA and fp32 accumulation throughout -- never less precise than bf16 autograd;
-// the bf16-MFMA version of the three GEMMs is the open item).  Layout in floats, in front of LinBwdLayout.
-struct UpLayout { size_t tok, byte, w, bias, g, x, total; };
-static UpLayout up_layout(const MotEmbedMixDesc &d) {
-    UpLayout U;
-    const size_t N = (size_t)(d.n_rows * d.tokens_per_row), K = (size_t)d.tok_dim + (size_t)d.bpt * d.byte_dim;
-    size_t o = 0;
-    auto take = [&](size_t n) { size_t at = o; o += (n + 3) & ~(size_t)3; return at; };
-    U.tok = take((size_t)d.tok_rows * d.tok_dim); U.byte = take((size_t)d.byte_rows * d.byte_dim); U.w = take((size_t)d.model_dim * K);
-    U.bias = take(d.bias ? d.model_dim : 0); U.g = take(N * d.model_dim); U.x = take(d.norm_out ? N * d.model_dim : 0);
-    U.total = o;
-    return U;
-}
-
-__global__ __launch_bounds__(kThreads) void widen_kernel(const __bf16 *__restrict__ src, int64_t n, float *__restrict__ dst) {
-    for (int64_t i = ((int64_t)blockIdx.x * kThreads + threadIdx.x) * 8; i < n; i += (int64_t)gridDim.x * kThreads * 8) {
-        if (i + 8 <= n && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0) {
-            const float8v v = Elem<__bf16>::loadv(src + i);
-            *(float4v *)(dst + i) = __builtin_shufflevector(v, v, 0, 1, 2, 3);
-            *(float4v *)(dst + i + 4) = __builtin_shufflevector(v, v, 4, 5, 6, 7);
-        } else {
-            for (int64_t j = i; j < min(n, i + 8); ++j) dst[j] = (float)src[j];
-        }
-    }
-}
-static int launch_widen(const void *src, size_t n, float *dst, hipStream_t stream) {
-    if (!n) return MOT_OK;
-    size_t blocks = (n / 8 + kThreads) / kThreads;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(widen_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, stream, (const __bf16 *)src, (int64_t)n, dst);
-    return check_launch("widen_kernel");
-}
-
-// du = dy . W of the bf16 backward on the bf16 MFMA (what autograd does for bf16 parameters): dy rounded to bf16,
-// W^T as the [K, Dm] "weight" of the forward bf16 kernel in dense-row mode, du widened back for the scatter stage.
-// Scratch behind the fp32 layouts, in bytes: [dy16: N*Dm*2][wt16: K*Dm*2][u16: N*K*2].
-struct Du16Layout { size_t dy16, wt16, uT, total; };
-static Du16Layout du16_layout(const MotEmbedMixDesc &d) {
-    Du16Layout U;
-    const size_t N = (size_t)(d.n_rows * d.tokens_per_row), K = (size_t)d.tok_dim + (size_t)d.bpt * d.byte_dim, Dm = (size_t)d.model_dim;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
-    U.dy16 = take(N * Dm * 2); U.wt16 = take(K * Dm * 2);
-    U.uT = take(N * K * 2);   // the concat operand in bf16, row-major (dW)
-    U.total = o;
-    return U;
-}
-static bool du16_usable(const MotEmbedMixDesc &d) {
-    const int K = d.tok_dim + d.bpt * d.byte_dim;
-    return d.dtype == MOT_BF16 && (d.model_dim & 7) == 0 && (K & 7) == 0 && K <= 4096 && ((d.n_rows * d.tokens_per_row) & 7) == 0 &&
-           !(d.flags & MOT_FLAG_BWD_DU_FP32);
-}
-
-__global__ __launch_bounds__(kThreads) void narrow_kernel(const float *__restrict__ src, int64_t n, __bf16 *__restrict__ dst) {
-    for (int64_t i = ((int64_t)blockIdx.x * kThreads + threadIdx.x) * 8; i < n; i += (int64_t)gridDim.x * kThreads * 8) {
-        if (i + 8 <= n) {   // both buffers are 256-byte aligned workspace regions
-            float8v v;
-            const float4v a = *(const float4v *)(src + i), b = *(const float4v *)(src + i + 4);
-            v = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-            Elem<__bf16>::storev_nt(dst + i, v);
-        } else {
-            for (int64_t j = i; j < n; ++j) dst[j] = (__bf16)src[j];
-        }
-    }
-}
-
-
-// C[m][k] += sum_n A[n][m] * B[n][k]   (A: rows x M, B: rows x Kc, both bf16 ROW-major as the forward and dy_kernel leave them;
-// C fp32, leading dimension ldc) on v_mfma_f32_32x32x16_bf16: dW = dy^T u with the token index as the contraction index.
-// Both MFMA operands want 8 consecutive CONTRACTION elements per lane, i.e. a column of the row-major tiles: the tiles go into
-// LDS as they are (64 token rows x 128 columns, rows padded to 320 bytes) and are read back with ds_read_b64_tr_b16, the
-// transposing LDS read of gfx950 -- a 16-lane group fetches 4 rows x 16 columns and every lane receives ONE column's 4 rows;
-// two reads make a lane's 8 contraction elements.  (Round 1 transposed dy and u in HBM first -- narrow_transpose /
-// transpose_bf16, 0.2 ms at 65 536 x 768 -- and contracted the token-minor copies: 0.30 ms more, with 85-fold split-k atomics.)
-// With 320-byte rows the four rows of a read sit 80 dwords apart: a 32-lane half (two groups, 32 columns) covers all 64 banks once.
-// Workgroup tile 128 x 128, 2 x 4 waves as 2 x 2, each 64 x 64; contraction split over blockIdx.z; partial tiles are added with
-// float atomics (128-byte contiguous segments).  128 x 128 keeps the split count -- and with it the atomic volume
-// (splits x M x Kc x 4 bytes) -- at 8 for 768 x 768 (two workgroups per CU).
-typedef __bf16 bf16x8w __attribute__((ext_vector_type(8)));
-typedef short s16x4w __attribute__((ext_vector_type(4)));
-constexpr int kTnRows = 64, kTnLd = 160;   // token rows per step; elements per staged row (128 data + 32 pad)
-constexpr int kTnThreads = 512;            // 8 waves: two per SIMD.  Waves 0-3 and 4-7 are the same 2 x 2 grid of 64 x 64 sub-tiles and split the
-                                           // step's four 16-row contraction slices between them; the two partial tiles meet in LDS at the end
-__global__ __launch_bounds__(kTnThreads) void gemm_tn_bf16_kernel(const __bf16 *__restrict__ A_, int lda, int M, const __bf16 *__restrict__ B_, int ldb, int Kc,
-                                                                  int64_t rows, int64_t rper, int nz, float *__restrict__ C, int ldc) {
-    extern __shared__ __attribute__((aligned(16))) __bf16 lds_tn[];   // [2][A | B][kTnRows][kTnLd]
-    constexpr int kTile = kTnRows * kTnLd;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, li = lane & 31;
-    // 1-D grid, XCD-aware: workgroup ids go round-robin over the 8 XCDs, so ids 8 g .. 8 g + 7 take the SAME output tile and the
-    // contraction slices z = 0 .. 7: all tiles of one slice then run on one XCD and its rows of A and B come out of that XCD's L2
-    // (every row is wanted by gx + gy tiles; without this they were fetched once per XCD and tile: 1.2 GB instead of 0.2 at 65 536 x 768)
-    const int gx = (M + 127) / 128, tiles = gx * ((Kc + 127) / 128);
-    int tile, z;
-    if ((nz & 7) == 0) { const int g = blockIdx.x >> 3; tile = g % tiles; z = (blockIdx.x & 7) + 8 * (g / tiles); }
-    else { tile = blockIdx.x % tiles; z = blockIdx.x / tiles; }
-    const int m0 = (tile % gx) * 128, k0 = (tile / gx) * 128;
-    const int64_t r_lo = (int64_t)z * rper, r_hi = min(rows, r_lo + rper);
-    const int wm = ((wave >> 1) & 1) * 64, wk = (wave & 1) * 64, ws = wave >> 2;   // ws: which two of the four contraction slices
-    f32x16b acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-    // staging: 64 rows x 16 pieces of 16 bytes per operand = 1024 pieces -> 2 per thread (16 lanes read one 256-byte row segment)
-    bf16x8w ra[2], rb[2];
-    auto load_stage = [&](int64_t r0) {
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            const int q = p * kTnThreads + tid, row = q >> 4, c = (q & 15) * 8;
-            ra[p] = (bf16x8w)((__bf16)0.f); rb[p] = (bf16x8w)((__bf16)0.f);
-            if (r0 + row < r_hi) {   // M, Kc, lda, ldb are multiples of 8: a piece is wholly inside or outside
-                if (m0 + c < M) ra[p] = *(const bf16x8w *)(A_ + (r0 + row) * lda + m0 + c);
-                if (k0 + c < Kc) rb[p] = *(const bf16x8w *)(B_ + (r0 + row) * ldb + k0 + c);
-            }
-        }
-    };
-    auto store_stage = [&](int buf) {
-        __bf16 *sA = lds_tn + buf * 2 * kTile, *sB = sA + kTile;
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            const int q = p * kTnThreads + tid, row = q >> 4, c = (q & 15) * 8;
-            *(bf16x8w *)(sA + row * kTnLd + c) = ra[p];
-            *(bf16x8w *)(sB + row * kTnLd + c) = rb[p];
-        }
-    };
-    // transposed fragment: lane 4 q + p of a 16-lane group g addresses row (r0 + q), columns c0 + 4 p .. + 3 of the group's 4 x 16 block;
-    // lane i of the group receives column c0 + i.  Group g: contraction half h = g >> 1, columns 16 (g & 1) .. + 15 of the 32-wide tile.
-    const int grp = lane >> 4, gi = lane & 15;
-    const int tr_off = ((gi >> 2) + 8 * (grp >> 1)) * kTnLd + 16 * (grp & 1) + 4 * (gi & 3);   // elements, inside a 16-row x 32-column operand block
-    auto frag = [&](const __bf16 *tile, int s16, int col0) {   // rows 16 s16 .. + 15 (contraction), columns col0 .. + 31
-        const __bf16 *p = tile + (16 * s16) * kTnLd + col0 + tr_off;
-        const s16x4w lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4w *)p);
-        const s16x4w hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4w *)(p + 4 * kTnLd));
-        typedef short s16x8w __attribute__((ext_vector_type(8)));
-        const s16x8w v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-        return __builtin_bit_cast(bf16x8w, v);
-    };
-    if (r_lo < r_hi) {
-        load_stage(r_lo);
-        store_stage(0);
-    }
-    __syncthreads();
-    int buf = 0;
-    for (int64_t r0 = r_lo; r0 < r_hi; r0 += kTnRows, buf ^= 1) {
-        const bool more = r0 + kTnRows < r_hi;
-        if (more) load_stage(r0 + kTnRows);
-        const __bf16 *sA = lds_tn + buf * 2 * kTile, *sB = sA + kTile;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int s16 = 2 * ws + j;
-            bf16x8w af[2], bf[2];
-#pragma unroll
-            for (int a = 0; a < 2; ++a) af[a] = frag(sA, s16, wm + 32 * a);
-#pragma unroll
-            for (int b = 0; b < 2; ++b) bf[b] = frag(sB, s16, wk + 32 * b);
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int b = 0; b < 2; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[a], bf[b], acc[a][b], 0, 0, 0);
-        }
-        if (more) store_stage(buf ^ 1);
-        __syncthreads();
-    }
-    // the second wave group's partial tile joins the first's through LDS (64 KB: the stage buffers are free now)
-    float *red = (float *)lds_tn + (size_t)(wave & 3) * 64 * 64;   // [a][b][r][lane] of one 64 x 64 sub-tile
-    if (ws == 1) {
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) red[((a * 2 + b) * 16 + r) * 64 + lane] = acc[a][b][r];
-    }
-    __syncthreads();
-    if (ws == 1) return;
-    // D[i][j]: lane -> j (B column = output column k), registers -> i (A column = output row m)
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * h, k = k0 + wk + b * 32 + li;
-                if (m < M && k < Kc) atomicAdd(C + (int64_t)m * ldc + k, acc[a][b][r] + red[((a * 2 + b) * 16 + r) * 64 + lane]);
-            }
-}
-
-// A, B: 16-byte aligned, lda / ldb / M / Kc multiples of 8
-int launch_gemm_tn_bf16(const __bf16 *A_, int lda, int M, const __bf16 *B_, int ldb, int Kc, int64_t rows, float *C, int ldc, hipStream_t stream) {
-    if (M <= 0 || Kc <= 0 || rows <= 0) return MOT_OK;
-    // (the kernel loads whole 16-byte pieces and guards a piece by its first column only)
-    if ((lda & 7) || (ldb & 7) || (M & 7) || (Kc & 7) || ((uintptr_t)A_ & 15) || ((uintptr_t)B_ & 15))
-        return set_error(MOT_EUNSUPPORTED, "gemm_tn_bf16: rows must be 16-byte aligned, lda / ldb / M / Kc multiples of 8 (lda %d, ldb %d, M %d, Kc %d)", lda,
-                         ldb, M, Kc);
-    const int tiles = ((M + 127) / 128) * ((Kc + 127) / 128);
-    // contraction slices: two workgroups per CU (80 KB of LDS each), a multiple of 8 for the XCD mapping, few enough to keep the
-    // atomic volume (slices x M x Kc x 4 bytes) small
-    int64_t splits = (512 / tiles) & ~7;
-    if (splits < 8) splits = 8;
-    if (splits > 32) splits = 32;
-    int64_t rper = ((rows + splits - 1) / splits + kTnRows - 1) / kTnRows * kTnRows;
-    if (rper < 4 * kTnRows) rper = 4 * kTnRows;
-    splits = (rows + rper - 1) / rper;
-    if ((int64_t)tiles * splits > 0x7fffffffLL) return set_error(MOT_EUNSUPPORTED, "gemm_tn_bf16: too many tiles");
-    const size_t lds = (size_t)4 * kTnRows * kTnLd * sizeof(__bf16);
-    static std::atomic<uint64_t> lds_ok{0};
-    if (int rc = ensure_max_dyn_lds((const void *)gemm_tn_bf16_kernel, lds_ok, "gemm_tn_bf16_kernel")) return rc;
-    hipLaunchKernelGGL(gemm_tn_bf16_kernel, dim3((unsigned)(tiles * splits)), dim3(kTnThreads), lds, stream, A_, lda, M, B_, ldb, Kc, rows, rper, (int)splits,
-                       C, ldc);
-    return check_launch("gemm_tn_bf16_kernel");
-}
-
-// dst[c][r] = src[r][c]   (rows x cols -> cols x rows), bf16, 32 x 32 tiles through LDS
-__global__ __launch_bounds__(kThreads) void transpose_bf16_kernel(const __bf16 *__restrict__ src, int rows, int cols, __bf16 *__restrict__ dst) {
-    __shared__ __bf16 tile[32][33];
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
-    const int c0 = blockIdx.x * 32, r0 = blockIdx.y * 32;
-    for (int r = ty; r < 32; r += 8)
-        tile[r][tx] = (r0 + r < rows && c0 + tx < cols) ? src[(int64_t)(r0 + r) * cols + c0 + tx] : (__bf16)0.f;
-    __syncthreads();
-    for (int c = ty; c < 32; c += 8)
-        if (c0 + c < cols && r0 + tx < rows) dst[(int64_t)(c0 + c) * rows + r0 + tx] = tile[tx][c];
-}
-
-// dst[c][r] = bf16(src[r][c])   (fp32 rows x cols -> bf16 cols x rows): the k-major copy of a weight for gemm_rows_bf16
-__global__ __launch_bounds__(kThreads) void narrow_transpose_kernel(const float *__restrict__ src, int rows, int cols, __bf16 *__restrict__ dst) {
-    __shared__ float tile[32][33];
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
-    const int c0 = blockIdx.x * 32, r0 = blockIdx.y * 32;
-    for (int r = ty; r < 32; r += 8)
-        tile[r][tx] = (r0 + r < rows && c0 + tx < cols) ? src[(int64_t)(r0 + r) * cols + c0 + tx] : 0.f;
-    __syncthreads();
-    for (int c = ty; c < 32; c += 8)
-        if (c0 + c < cols && r0 + tx < rows) dst[(int64_t)(c0 + c) * rows + r0 + tx] = (__bf16)tile[tx][c];
-}
-// dst[c][r] = src[r][c]   (fp32 rows x cols -> cols x rows): a k-major weight as the row-major operand of the LDS-DMA product kernel
-__global__ __launch_bounds__(kThreads) void transpose_f32_kernel(const float *__restrict__ src, int rows, int cols, float *__restrict__ dst) {
-    __shared__ float tile[32][33];
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
-    const int c0 = blockIdx.x * 32, r0 = blockIdx.y * 32;
-    for (int r = ty; r < 32; r += 8)
-        tile[r][tx] = (r0 + r < rows && c0 + tx < cols) ? src[(int64_t)(r0 + r) * cols + c0 + tx] : 0.f;
-    __syncthreads();
-    for (int c = ty; c < 32; c += 8)
-        if (c0 + c < cols && r0 + tx < rows) dst[(int64_t)(c0 + c) * rows + r0 + tx] = tile[tx][c];
-}
-int launch_transpose_f32(const float *src, int rows, int cols, float *dst, hipStream_t stream) {
-    if (rows <= 0 || cols <= 0) return MOT_OK;
-    hipLaunchKernelGGL(transpose_f32_kernel, dim3((unsigned)((cols + 31) / 32), (unsigned)((rows + 31) / 32)), dim3(kThreads), 0, stream, src, rows, cols, dst);
-    return check_launch("transpose_f32_kernel");
-}
-int launch_narrow_transpose(const float *src, int rows, int cols, void *dst, hipStream_t stream) {
-    if (rows <= 0 || cols <= 0) return MOT_OK;
-    hipLaunchKernelGGL(narrow_transpose_kernel, dim3((unsigned)((cols + 31) / 32), (unsigned)((rows + 31) / 32)), dim3(kThreads), 0, stream, src, rows, cols,
-                       (__bf16 *)dst);
-    return check_launch("narrow_transpose_kernel");
-}
-// dst[i] = bf16(src[i]); both 16-byte aligned
-int launch_narrow(const float *src, int64_t n, void *dst, hipStream_t stream) {
-    if (n <= 0) return MOT_OK;
-    size_t nb = ((size_t)n / 8 + kThreads) / kThreads;
-    if (nb > 4096) nb = 4096;
-    hipLaunchKernelGGL(narrow_kernel, dim3((unsigned)nb), dim3(kThreads), 0, stream, src, n, (__bf16 *)dst);
-    return check_launch("narrow_kernel");
-}
-
-// out[n] = ids[n * bpt + k] as int32 (out-of-range ids flagged and clamped to 0, as the forward does): one byte slot's ids as the
-// "tokens" of a plain embedding backward (the slot-wise scatter of wide concat rows, below)
-__global__ __launch_bounds__(kThreads) void ids_column_i32_kernel(const int64_t *__restrict__ ids, int64_t n, int bpt, int k, int64_t rows, int32_t *__restrict__ out,
-                                                                  uint32_t *status) {
-    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads) {
-        int64_t v = ids[i * bpt + k];
-        if ((uint64_t)v >= (uint64_t)rows) { if (status) atomicOr(status, kStatusByteOor); v = 0; }
-        out[i] = (int32_t)v;
-    }
-}
-
 static size_t bwd_rnorm_floats(const MotEmbedMixDesc &d) { return mixes_bytes(d.mode) ? ((size_t)d.byte_rows + 3) & ~(size_t)3 : 0; }
-size_t embed_mix_bwd_mean_workspace_bytes(const MotEmbedMixDesc &d);
 size_t embed_mix_bwd_workspace_bytes(const MotEmbedMixDesc &d) {
     if (d.mode == MOT_MIX_MEAN) return embed_mix_bwd_mean_workspace_bytes(d);
-    if (d.mode == MOT_MIX_CONCAT_LINEAR) {
-        return (lin_bwd_layout(d).total + (d.dtype == MOT_BF16 ? up_layout(d).total : 0)) * 4 + 256 + (du16_usable(d) ? du16_layout(d).total : 0);
-    }
+    if (d.mode == MOT_MIX_CONCAT_LINEAR) return embed_mix_bwd_linear_workspace_bytes(d);
     return (bwd_rnorm_floats(d) + scatter_ws_ints(d)) * 4;
 }
-
-// `w16` / `ws16` (optional): the bf16 weight and the Du16Layout scratch -- then du and dW run on the bf16 MFMA; `g16` / `x16`
-// (optional with them): the bf16 upstream gradient and forward output -- then dy is produced in bf16 directly and
-// gr.grad_out / d.out (fp32) are never read; `d16`: the caller's descriptor with the bf16 tables (the concat operand of dW is then
-// gathered from them directly, as the forward's was)
-static int launch_embed_mix_bwd_linear(const MotEmbedMixDesc &d, const MotEmbedMixGrads &gr, hipStream_t stream, const void *w16 = nullptr,
-                                       char *ws16 = nullptr, const void *g16 = nullptr, const void *x16 = nullptr, const MotEmbedMixDesc *d16 = nullptr) {
-    if (d.id_source != MOT_IDS_GIVEN) return set_error(MOT_EUNSUPPORTED, "embed_mix_bwd: pass the byte ids the forward returned (MOT_IDS_GIVEN)");
-    if (!gr.d_weight) return set_error(MOT_EINVAL, "embed_mix_bwd concat_linear: d_weight missing");
-    if (d.norm_out && (!d.out || !d.out_row_rnorm)) return set_error(MOT_EINVAL, "embed_mix_bwd concat_linear: needs the forward's out and out_row_rnorm");
-    const int64_t N = d.n_rows * d.tokens_per_row;
-    const int Dm = d.model_dim, Dt = d.tok_dim, nbk = d.bpt * d.byte_dim, K = Dt + nbk;
-    // rows wider than 1024 (mathblations' defaults: 768 + 3 x 768, model.py:21-24, 256-268) only where the table gradients can be
-    // scattered part by part on the lane-contiguous kernel: token part and every byte slot a multiple of 256 columns, <= 1024 each
-    // (rows up to 2048 columns: the strided kernels take them whole; wider ones -- the reference's dimension sweeps reach 1024 + 16 x
-    //  128 = 3072, experiments100_000steps.sh, mathblations' defaults 768 + 3 x 768 -- only where the part-wise scatter below applies)
-    if (Dm > 2048) return set_error(MOT_EUNSUPPORTED, "embed_mix_bwd concat_linear: model_dim %d > 2048", Dm);
-    const LinBwdLayout L = lin_bwd_layout(d);
-    if (d.dtype == MOT_BF16) {
-        const UpLayout U = up_layout(d);
-        if (!d.workspace || d.workspace_bytes < (U.total + L.total) * 4)
-            return set_error(MOT_EWORKSPACE, "embed_mix_bwd: needs %zu workspace bytes, got %zu", (U.total + L.total) * 4, d.workspace_bytes);
-        float *up = (float *)d.workspace;
-        const size_t Nn = (size_t)N * Dm;
-        int rc;
-        if ((rc = launch_widen(d.tok_table, (size_t)d.tok_rows * Dt, up + U.tok, stream))) return rc;
-        if ((rc = launch_widen(d.byte_table, (size_t)d.byte_rows * d.byte_dim, up + U.byte, stream))) return rc;
-        if ((rc = launch_widen(d.weight, (size_t)Dm * K, up + U.w, stream))) return rc;
-        if (d.bias && (rc = launch_widen(d.bias, Dm, up + U.bias, stream))) return rc;
-        const bool route16 = du16_usable(d);
-        const bool dy_in_bf16 = route16 && !d.bias && Dm <= 4096;   // the bias gradient is a column sum of an fp32 dy
-        if (!dy_in_bf16) {
-            if ((rc = launch_widen(gr.grad_out, Nn, up + U.g, stream))) return rc;
-            if (d.norm_out && (rc = launch_widen(d.out, Nn, up + U.x, stream))) return rc;
-        }
-        MotEmbedMixDesc d32 = d;
-        MotEmbedMixGrads g32 = gr;
-        d32.dtype = MOT_F32;
-        d32.tok_table = up + U.tok; d32.byte_table = up + U.byte; d32.weight = up + U.w; d32.bias = d.bias ? up + U.bias : nullptr;
-        d32.out = d.norm_out ? (void *)(up + U.x) : nullptr;
-        d32.eps = d.eps > 0.f ? d.eps : kBf16Eps;   // the forward normalised with the bf16 epsilon
-        d32.workspace = up + U.total; d32.workspace_bytes = d.workspace_bytes - U.total * 4;
-        g32.grad_out = up + U.g;
-        if (route16) {
-            const size_t off = ((U.total + L.total) * 4 + 255) & ~(size_t)255;
-            if (d.workspace_bytes < off + du16_layout(d).total)
-                return set_error(MOT_EWORKSPACE, "embed_mix_bwd: needs %zu workspace bytes, got %zu", off + du16_layout(d).total, d.workspace_bytes);
-            return launch_embed_mix_bwd_linear(d32, g32, stream, d.weight, (char *)d.workspace + off, dy_in_bf16 ? gr.grad_out : nullptr,
-                                               dy_in_bf16 ? d.out : nullptr, &d);
-        }
-        return launch_embed_mix_bwd_linear(d32, g32, stream);
-    }
-    if (!d.workspace || d.workspace_bytes < L.total * 4)
-        return set_error(MOT_EWORKSPACE, "embed_mix_bwd: needs %zu workspace bytes, got %zu", L.total * 4, d.workspace_bytes);
-    float *ws = (float *)d.workspace;
-    float *rn = ws + L.rnorm, *dy = ws + L.dy, *du = ws + L.du, *utok = ws + L.utok, *ubyte = ws + L.ubyte, *wk = ws + L.wk, *byte0 = ws + L.byte0;
-    int32_t *iota = (int32_t *)(ws + L.iota), *sort_ints = (int32_t *)(ws + L.sort);
-    (void)wk; (void)byte0; (void)ubyte;   // slots of the layout the fp32 du product no longer uses (u is built in place: utok .. ubyte)
-    const float eps = d.eps > 0.f ? d.eps : FLT_EPSILON;
-    int rc;
-    // 1. dy
-    const float *dyp = (const float *)gr.grad_out;
-    const __bf16 *dy16p = nullptr;   // bf16 route with bf16 inputs: dy exists in bf16 only
-    if (g16) {
-        const Du16Layout U = du16_layout(d);
-        dy16p = (const __bf16 *)g16;
-        if (d.norm_out) {
-            __bf16 *dy16 = (__bf16 *)(ws16 + U.dy16);
-            hipLaunchKernelGGL(dy16_kernel, dim3((unsigned)((N + kWaves - 1) / kWaves)), dim3(kThreads), 0, stream, (const __bf16 *)g16, (const __bf16 *)x16,
-                               d.out_row_rnorm, N, Dm, dy16);
-            if ((rc = check_launch("dy16_kernel"))) return rc;
-            dy16p = dy16;
-        }
-        dyp = nullptr;
-    } else if (d.norm_out) {
-        hipLaunchKernelGGL(dy_kernel, dim3((unsigned)((N + kWaves - 1) / kWaves)), dim3(kThreads), 0, stream, (const float *)gr.grad_out,
-                           (const float *)d.out, d.out_row_rnorm, N, Dm, dy);
-        if ((rc = check_launch("dy_kernel"))) return rc;
-        dyp = dy;
-    }
-    if (gr.d_bias) {
-        hipLaunchKernelGGL(colsum_kernel, dim3(256), dim3(kThreads), 0, stream, dyp, N, Dm, (float *)gr.d_bias);
-        if ((rc = check_launch("colsum_kernel"))) return rc;
-    }
-    // 2. u = the seam tensors (norms and scalars applied), and dW += dy^T u
-    const int64_t blk = 2048;
-    (void)blk;
-    const int tok_lo = d.bytes_first ? nbk : 0, byte_lo = d.bytes_first ? 0 : Dt;
-    float *dW = (float *)gr.d_weight;
-    // (w16: the concat operand goes straight to bf16, below)
-    if (!w16) {  // fp32: the concat operand u [N, K] itself, in the two (adjacent) scratch regions, so dW is ONE contraction
-        if ((rc = launch_gather_rows_placed(d.tokens, nullptr, 4, N, d.tok_table, d.tok_rows, Dt, d.norm_tok, eps, d.scale_tok, utok + tok_lo, 1, K,
-                                            d.status, kStatusTokenOor, MOT_F32, stream))) return rc;
-        if ((rc = launch_gather_rows_placed(d.ids_a, d.ids_b, 8, N * d.bpt, d.byte_table, d.byte_rows, d.byte_dim, d.norm_byte, eps, d.scale_byte,
-                                            utok + byte_lo, d.bpt, K, d.status, kStatusByteOor, MOT_F32, stream))) return rc;
-        if ((rc = launch_gemm_tn(dyp, Dm, Dm, utok, K, K, N, dW, K, stream))) return rc;
-    } else {
-        // 2'. dW on the bf16 MFMA: dy [N, Dm] and u [N, K] in bf16, ROW-major as they are, contracted over the tokens by
-        // gemm_tn_bf16_kernel (transposing LDS reads).  u is the forward's operand: gathered from the bf16 tables by the forward's
-        // own concat_rows_kernel when that applies (one id tensor, no learned scalars, 16-byte pieces), else gathered in fp32 from
-        // the widened tables and narrowed.
-        const Du16Layout U = du16_layout(d);
-        __bf16 *dy16 = (__bf16 *)(ws16 + U.dy16), *u16 = (__bf16 *)(ws16 + U.uT);
-        const __bf16 *dyr = dy16p;
-        if (!dyr) {
-            size_t nb = ((size_t)N * Dm / 8 + kThreads) / kThreads;
-            if (nb > 4096) nb = 4096;
-            hipLaunchKernelGGL(narrow_kernel, dim3((unsigned)nb), dim3(kThreads), 0, stream, dyp, (int64_t)N * Dm, dy16);
-            if ((rc = check_launch("narrow_kernel"))) return rc;
-            dyr = dy16;
-        }
-        if (d16 && !d.ids_b && !d.scale_tok && !d.scale_byte && (Dt & 7) == 0 && (d.byte_dim & 7) == 0) {
-            if (d.norm_byte && (rc = launch_rows_rnorm(d16->byte_table, d.byte_rows, d.byte_dim, eps, rn, MOT_BF16, stream))) return rc;
-            if ((rc = launch_concat_rows(d.tokens, d.ids_a, N, d16->tok_table, d.tok_rows, Dt, d16->byte_table, d.byte_rows, d.byte_dim, d.bpt, d.norm_tok,
-                                         d.norm_byte ? rn : nullptr, eps, u16, K, tok_lo, byte_lo, d.status, MOT_BF16, stream))) return rc;
-        } else {
-            if ((rc = launch_gather_rows_placed(d.tokens, nullptr, 4, N, d.tok_table, d.tok_rows, Dt, d.norm_tok, eps, d.scale_tok, utok + tok_lo, 1, K,
-                                                d.status, kStatusTokenOor, MOT_F32, stream))) return rc;
-            if ((rc = launch_gather_rows_placed(d.ids_a, d.ids_b, 8, N * d.bpt, d.byte_table, d.byte_rows, d.byte_dim, d.norm_byte, eps, d.scale_byte,
-                                                utok + byte_lo, d.bpt, K, d.status, kStatusByteOor, MOT_F32, stream))) return rc;
-            size_t nb = ((size_t)N * K / 8 + kThreads) / kThreads;
-            if (nb > 4096) nb = 4096;
-            hipLaunchKernelGGL(narrow_kernel, dim3((unsigned)nb), dim3(kThreads), 0, stream, utok, (int64_t)N * K, u16);
-            if ((rc = check_launch("narrow_kernel"))) return rc;
-        }
-        if ((rc = launch_gemm_tn_bf16(dyr, Dm, Dm, u16, K, K, N, dW, K, stream))) return rc;
-    }
-    hipLaunchKernelGGL(iota_kernel, dim3(256), dim3(kThreads), 0, stream, iota, N);
-    if (w16) {
-        // 3'. du on the bf16 MFMA: bf16(dy) rows x W^T on the dense bf16 kernel
-        const Du16Layout U = du16_layout(d);
-        __bf16 *dy16 = (__bf16 *)(ws16 + U.dy16), *wt16 = (__bf16 *)(ws16 + U.wt16);
-        size_t nb = ((size_t)N * Dm / 8 + kThreads) / kThreads;
-        if (nb > 4096) nb = 4096;
-        if (dy16p) dy16 = const_cast<__bf16 *>(dy16p);   // (else narrowed for dW above)
-        (void)nb;
-        hipLaunchKernelGGL(transpose_bf16_kernel, dim3((unsigned)((K + 31) / 32), (unsigned)((Dm + 31) / 32)), dim3(kThreads), 0, stream,
-                           (const __bf16 *)w16, Dm, K, wt16);
-        if ((rc = check_launch("narrow/transpose"))) return rc;
-        // du[n][k] = sum_m dy16[n][m] * wt16[k][m], accumulated and written in fp32 (no bf16 round trip before the scatter)
-        if ((rc = launch_gemm_rows_bf16(dy16, Dm, N, wt16, Dm, Dm, K, du, K, false, nullptr, stream))) return rc;
-    } else {
-    // 3. du = dy . W   (N x Dm) @ (Dm x K): both row-major as they are (nn.Linear keeps W as [Dm][K])
-    //    (W transposed once and the product on the LDS-DMA kernel, as the cross-attention backward does with its k-major products:
-    //     measured, 2.625 against 2.63 ms for forward + backward -- not kept here)
-    if ((rc = launch_gemm_rows(dyp, Dm, N, (const float *)d.weight, K, Dm, K, du, K, false, stream))) return rc;
-    }
-    // 4. table gradients from du (its row layout is the concat layout)
-    BwdArgs A;
-    fill_bwd_args(A, d, gr);
-    A.grad_out = du; A.D = K; A.norm_out = 0;
-    A.Dt = Dt; A.tok_lo = tok_lo; A.byte_lo = byte_lo; A.nbk = nbk;
-    // The two halves of a du row are two embedding backwards: the token part a plain one (NOOP) over Dt columns, the byte part a SUM
-    // over byte slots with no token table -- both on the lane-contiguous kernel, reading their columns of du in place (row stride K),
-    // sharing one grouping of the positions.  (The strided kernel of round 1 took 242 us of the 870 us the bf16 concat forward +
-    // backward takes at 65 536 tokens.)  One id tensor only: norm_byte over two id tensors normalises the SUM of two rows.
-    if (!d.ids_b) {
-        BwdArgs At = A, Ab = A;
-        At.D = At.Dt = Dt; At.tok_lo = At.byte_lo = 0; At.nbk = 0; At.grad_out = du + tok_lo; At.g_ld = K; At.d_byte = nullptr;
-        Ab.D = Ab.Dt = nbk; Ab.tok_lo = Ab.byte_lo = 0; Ab.nbk = nbk; Ab.grad_out = du + byte_lo; Ab.g_ld = K; Ab.no_tok = 1; Ab.d_tok = nullptr;
-        Ab.norm_tok = 0; Ab.tok_table = nullptr;
-        // the byte part in blocks of whole slots, <= 1024 columns each (16 x 128-wide slots are two blocks of 8)
-        int per = d.bpt;
-        while (per > 1 && per * d.byte_dim > 1024) per = (per + 1) / 2;
-        Ab.D = Ab.Dt = Ab.nbk = per * d.byte_dim;
-        // (the token part: the lane-contiguous kernel, or -- 896 columns -- the general one, which knows the row stride too)
-        bool split = d.bpt % per == 0 && lc_layout<MOT_MIX_SUM>(Ab) && (lc_layout<MOT_MIX_NOOP>(At) || K > 2048);
-#ifdef MOT_DEV_ABLATION
-        if (getenv("MOT_CONCAT_SCATTER_OLD")) split = false;
-#endif
-        if (split) {
-            if ((rc = run_scatter<MOT_MIX_NOOP>(At, d, sort_ints, rn, stream))) return rc;
-            for (int s0 = 0; s0 < d.bpt; s0 += per) {
-                BwdArgs Ac = Ab;
-                Ac.pos_sorted = At.pos_sorted; Ac.tok_sorted = At.tok_sorted;
-                Ac.slot0 = s0; Ac.grad_out = du + byte_lo + s0 * d.byte_dim;
-                if ((rc = run_scatter<MOT_MIX_SUM>(Ac, d, sort_ints, rn, stream))) return rc;
-            }
-            return MOT_OK;
-        }
-        // Wide byte slots (a slot is a whole embedding row: the digit mixin): every slot is a plain embedding backward of its own, the
-        // slot's ids as the "tokens", the byte table as the table, its columns of du as the gradient rows
-        if (lc_layout<MOT_MIX_NOOP>(At) && (d.byte_dim & 255) == 0 && d.byte_dim <= 1024 && !d.scale_tok && !d.scale_byte) {
-            if ((rc = run_scatter<MOT_MIX_NOOP>(At, d, sort_ints, rn, stream))) return rc;
-            for (int k = 0; k < d.bpt; ++k) {
-                hipLaunchKernelGGL(ids_column_i32_kernel, dim3(256), dim3(kThreads), 0, stream, d.ids_a, N, d.bpt, k, d.byte_rows, iota, d.status);
-                if ((rc = check_launch("ids_column_i32_kernel"))) return rc;
-                BwdArgs As = A;
-                As.tokens = iota; As.tok_table = A.byte_table; As.tok_rows = d.byte_rows; As.norm_tok = d.norm_byte;
-                As.D = As.Dt = d.byte_dim; As.tok_lo = As.byte_lo = 0; As.nbk = 0; As.grad_out = du + byte_lo + k * d.byte_dim; As.g_ld = K;
-                As.d_tok = A.d_byte; As.d_byte = nullptr; As.pos_sorted = As.tok_sorted = nullptr;
-                if (!lc_layout<MOT_MIX_NOOP>(As)) return set_error(MOT_EUNSUPPORTED, "embed_mix_bwd concat_linear: byte slots of %d columns", d.byte_dim);
-                MotEmbedMixDesc ds = d;   // (run_scatter reads the table height from the descriptor)
-                ds.tok_rows = d.byte_rows;
-                if ((rc = run_scatter<MOT_MIX_NOOP>(As, ds, sort_ints, rn, stream))) return rc;
-            }
-            return MOT_OK;
-        }
-    }
-    if (K > 2048)
-        return set_error(MOT_EUNSUPPORTED, "embed_mix_bwd concat_linear: K %d > 2048 needs the part-wise scatter (one id tensor, no learned scalars, "
-                         "byte slots that tile blocks of <= 1024 columns)", K);
-    return run_scatter<MOT_MIX_CONCAT_LINEAR>(A, d, sort_ints, rn, stream);
-}
-
-// ==========================================================================================
-// MEAN backward:  x = s_t a + s_c mean_k v_k,  v = rms_norm?(E_c[id])      (inference/inference.py:266-267 under autograd)
-// The character table has a few hundred rows at most (132), so its gradient is a dense product instead of a scatter:
-//   cnt[n][r] = number of slots of token n holding character r                  (mean_counts_kernel)
-//   M1 = cnt^T G   [rows, D]                                                    (gemm_tn: fp32 MFMA, split over the tokens)
-//   S  = G V^T     [N, rows],   w_r = sum_n cnt[n][r] S[n][r]                   (gemm_rows + mean_colsum_kernel)
-//   d E_c[r] += (s_c / bpt) rn_r (M1[r] - v_r w_r / D)   (no norm: (s_c / bpt) M1[r]);   d s_c += sum_r w_r / bpt
-// S and w are only needed for the norm's backward and for d s_c.  The token side is the tokens-only backward with a scale.
-// ==========================================================================================
-__global__ __launch_bounds__(kThreads) void mean_counts_kernel(const int64_t *__restrict__ ids, int64_t n, int bpt, int rows, int ld,
-                                                               float *__restrict__ cnt, uint32_t *status) {
-    const int lane = threadIdx.x & 63;
-    const int64_t t = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
-    if (t >= n) return;
-    int64_t v = lane < bpt ? ids[t * bpt + lane] : -1;
-    if (lane < bpt && (uint64_t)v >= (uint64_t)rows) { if (status) atomicOr(status, kStatusByteOor); v = 0; }
-    const int id = (int)v;
-    for (int r0 = 0; r0 < ld; r0 += 64) {
-        const int r = r0 + lane;
-        float c = 0.f;
-        for (int k = 0; k < bpt; ++k) c += __builtin_amdgcn_readlane(id, k) == r ? 1.f : 0.f;
-        if (r < ld) cnt[t * ld + r] = c;
-    }
-}
-
-// w[r] += sum_n cnt[n][r] * S[n][r]: a workgroup takes a stretch of tokens, a thread a column (rows <= 1024)
-__global__ __launch_bounds__(kThreads) void mean_colsum_kernel(const float *__restrict__ cnt, const float *__restrict__ S, int64_t n, int rows, int ld,
-                                                               int64_t per_block, float *__restrict__ w) {
-    const int64_t n0 = (int64_t)blockIdx.x * per_block, n1 = min(n, n0 + per_block);
-    for (int r = threadIdx.x; r < rows; r += kThreads) {
-        float acc = 0.f;
-        for (int64_t t = n0; t < n1; ++t) acc += cnt[t * ld + r] * S[t * ld + r];
-        if (acc != 0.f) atomicAdd(w + r, acc);
-    }
-}
-
-__global__ __launch_bounds__(kThreads) void mean_finalize_kernel(const float *__restrict__ M1, const float *__restrict__ table, const float *__restrict__ rn,
-                                                                 const float *__restrict__ w, int rows, int D, int bpt, const float *scale_byte,
-                                                                 float *__restrict__ d_table, float *d_scale) {
-    const float c = (scale_byte ? *scale_byte : 1.0f) / (float)bpt;
-    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < (int64_t)rows * D; i += (int64_t)gridDim.x * kThreads) {
-        const int r = (int)(i / D);
-        float g = M1[i];
-        if (rn) g = rn[r] * (g - (table[i] * rn[r]) * (w[r] / (float)D));
-        d_table[i] += c * g;
-    }
-    if (d_scale && blockIdx.x == 0 && threadIdx.x < 64) {
-        float sacc = 0.f;
-        for (int r = threadIdx.x; r < rows; r += 64) sacc += w[r];
-        sacc = wave_sum(sacc);
-        if (threadIdx.x == 0) atomicAdd(d_scale, sacc / (float)bpt);
-    }
-}
-
-constexpr int64_t kMeanSlab = 65536;
-struct MeanBwdLayout { size_t rn, vn, m1, w, cnt, s, scatter, tab32, g32, total; int ld; };
-static MeanBwdLayout mean_bwd_layout(const MotEmbedMixDesc &d) {
-    MeanBwdLayout L;
-    const int64_t N = d.n_rows * d.tokens_per_row, slab = N < kMeanSlab ? N : kMeanSlab;
-    L.ld = (int)((d.byte_rows + 3) & ~3);
-    size_t o = 0;
-    auto take = [&](size_t n) { size_t at = o; o += (n + 63) & ~(size_t)63; return at; };
-    L.rn = take(d.byte_rows); L.vn = take((size_t)d.byte_rows * d.byte_dim); L.m1 = take((size_t)d.byte_rows * d.byte_dim); L.w = take(d.byte_rows);
-    L.cnt = take((size_t)slab * L.ld); L.s = take((size_t)slab * L.ld); L.scatter = take(scatter_ws_ints(d));
-    // bf16 tables / gradient rows: the character side runs on fp32 copies -- the 132-row table once, the gradient rows a slab at a time
-    L.tab32 = L.g32 = 0;
-    if (d.dtype == MOT_BF16) { L.tab32 = take((size_t)d.byte_rows * d.byte_dim); L.g32 = take((size_t)slab * d.byte_dim); }
-    L.total = o;
-    return L;
-}
-
-__global__ __launch_bounds__(kThreads) void scale_rows_kernel(const float *__restrict__ src, const float *__restrict__ rn, int rows, int D, float *__restrict__ dst) {
-    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < (int64_t)rows * D; i += (int64_t)gridDim.x * kThreads) dst[i] = src[i] * rn[i / D];
-}
-
-static int launch_embed_mix_bwd_mean(const MotEmbedMixDesc &d, const MotEmbedMixGrads &gr, hipStream_t stream) {
-    // bf16 (round 3): the token side reads bf16 rows natively (the NOOP scatter kernel); the character side -- dense products over
-    // the token axis on the fp32 MFMA -- runs on operands widened once (the table) or slab by slab (the gradient rows); sums fp32.
-    const bool bf = d.dtype == MOT_BF16;
-    if (d.norm_out) return set_error(MOT_EUNSUPPORTED, "embed_mix_bwd: MEAN with an output norm has no backward (the reference's residual, inference.py:267, has none)");
-    if (d.id_source != MOT_IDS_GIVEN || d.ids_b) return set_error(MOT_EUNSUPPORTED, "embed_mix_bwd MEAN: one given id tensor");
-    if (d.byte_rows > 1024) return set_error(MOT_EUNSUPPORTED, "embed_mix_bwd MEAN: %lld character rows (> 1024): the dense formulation is for small tables", (long long)d.byte_rows);
-    if (!gr.d_byte_table) return set_error(MOT_EINVAL, "embed_mix_bwd: d_byte_table missing");
-    const MeanBwdLayout L = mean_bwd_layout(d);
-    if (!d.workspace || d.workspace_bytes < L.total * 4) return set_error(MOT_EWORKSPACE, "embed_mix_bwd: needs %zu workspace bytes, got %zu", L.total * 4, d.workspace_bytes);
-    float *ws = (float *)d.workspace;
-    const int64_t N = d.n_rows * d.tokens_per_row, slab = N < kMeanSlab ? N : kMeanSlab;
-    const int rows = (int)d.byte_rows, D = d.byte_dim;
-    const float eps = d.eps > 0.f ? d.eps : (d.dtype == MOT_BF16 ? kBf16Eps : FLT_EPSILON);   // F.rms_norm(eps=None): finfo of the input dtype
-    int rc;
-    // ---- token side: x = s_t * norm?(E_t[tok]) + (...) is the tokens-only mix as far as the token table and s_t are concerned
-    {
-        MotEmbedMixDesc t = d;
-        t.mode = MOT_MIX_NOOP; t.bpt = 0; t.id_source = MOT_IDS_NONE; t.ids_a = nullptr; t.byte_table = nullptr; t.norm_byte = 0; t.scale_byte = nullptr;
-        MotEmbedMixGrads gt = gr;
-        gt.d_byte_table = nullptr; gt.d_scale_byte = nullptr;
-        BwdArgs A;
-        fill_bwd_args(A, t, gt);
-        if ((rc = run_scatter<MOT_MIX_NOOP>(A, t, (int32_t *)(ws + L.scatter), nullptr, stream))) return rc;
-    }
-    // ---- character side
-    const float *tab = (const float *)d.byte_table;
-    if (bf) {
-        if ((rc = launch_widen(d.byte_table, (size_t)rows * D, ws + L.tab32, stream))) return rc;
-        tab = ws + L.tab32;
-    }
-    const float *V = tab, *rn = nullptr;
-    const bool need_s = d.norm_byte || gr.d_scale_byte;
-    if (d.norm_byte) {
-        if ((rc = launch_rows_rnorm(tab, rows, D, eps, ws + L.rn, MOT_F32, stream))) return rc;
-        hipLaunchKernelGGL(scale_rows_kernel, dim3(256), dim3(kThreads), 0, stream, tab, ws + L.rn, rows, D, ws + L.vn);
-        V = ws + L.vn; rn = ws + L.rn;
-    }
-    if ((rc = launch_zero_words(ws + L.m1, (int64_t)rows * D, stream))) return rc;
-    if ((rc = launch_zero_words(ws + L.w, rows, stream))) return rc;
-    for (int64_t n0 = 0; n0 < N; n0 += slab) {
-        const int64_t nn = N - n0 < slab ? N - n0 : slab;
-        const float *G = (const float *)gr.grad_out + n0 * D;
-        if (bf) {
-            if ((rc = launch_widen((const __bf16 *)gr.grad_out + n0 * D, (size_t)nn * D, ws + L.g32, stream))) return rc;
-            G = ws + L.g32;
-        }
-        hipLaunchKernelGGL(mean_counts_kernel, dim3((unsigned)((nn + kWaves - 1) / kWaves)), dim3(kThreads), 0, stream, d.ids_a + n0 * d.bpt, nn, d.bpt, rows,
-                           L.ld, ws + L.cnt, d.status);
-        if ((rc = check_launch("mean_counts_kernel"))) return rc;
-        if ((rc = launch_gemm_tn(ws + L.cnt, L.ld, rows, G, D, D, nn, ws + L.m1, D, stream))) return rc;
-        if (need_s) {
-            if ((rc = launch_gemm_rows(G, D, nn, V, D, D, rows, ws + L.s, L.ld, true, stream))) return rc;
-            const int64_t per = 256;
-            hipLaunchKernelGGL(mean_colsum_kernel, dim3((unsigned)((nn + per - 1) / per)), dim3(kThreads), 0, stream, ws + L.cnt, ws + L.s, nn, rows, L.ld, per,
-                               ws + L.w);
-            if ((rc = check_launch("mean_colsum_kernel"))) return rc;
-        }
-    }
-    hipLaunchKernelGGL(mean_finalize_kernel, dim3(256), dim3(kThreads), 0, stream, ws + L.m1, tab, rn, ws + L.w, rows, D, d.bpt,
-                       d.scale_byte, (float *)gr.d_byte_table, gr.d_scale_byte);
-    return check_launch("mean_finalize_kernel");
-}
-
-size_t embed_mix_bwd_mean_workspace_bytes(const MotEmbedMixDesc &d) { return mean_bwd_layout(d).total * 4; }
 
 int launch_embed_mix_bwd(const MotEmbedMixDesc &d, const MotEmbedMixGrads &gr, hipStream_t stream) {
     if (d.n_rows * d.tokens_per_row > 0x7fffffffLL) return set_error(MOT_EUNSUPPORTED, "embed_mix_bwd: more than 2^31 tokens");
@@ -2771,9 +1552,7 @@ int launch_embed_mix_bwd(const MotEmbedMixDesc &d, const MotEmbedMixGrads &gr, h
         return set_error(MOT_EWORKSPACE, "embed_mix_bwd: needs %zu workspace bytes, got %zu", need, d.workspace_bytes);
     float *rn = (float *)d.workspace;
     int32_t *ints = (int32_t *)(rn + bwd_rnorm_floats(d));
-    if (d.mode == MOT_MIX_SUM) return run_scatter<MOT_MIX_SUM>(A, d, ints, rn, stream);
-    if (d.mode == MOT_MIX_CONCAT) return run_scatter<MOT_MIX_CONCAT>(A, d, ints, rn, stream);
-    return run_scatter<MOT_MIX_NOOP>(A, d, ints, rn, stream);
+    return run_scatter(d.mode, A, d, ints, rn, stream);
 }
 
 }  // namespace mot

@@ -7,6 +7,8 @@
 // the minimum for 512 bytes), the next step's global loads in flight while the current one is multiplied.
 // Used by the composed bf16 concat + linear forward (mot_linear.hip) -- the fused tile kernel of mot_linear_bf16.hip spends
 // its time gathering and staging, not multiplying.
+// At the end: gemm_tn_bf16_kernel, the contraction over the ROWS of two row-major bf16 operands (weight gradients: the
+// CONCAT_LINEAR backward, cross-attention, the byte head).
 #include <type_traits>
 #include <atomic>
 #include <stdlib.h>
@@ -159,7 +161,7 @@ __device__ __forceinline__ void static_for_g(F &&f) {
 // register e of the fragment contracts k = 8 kk + e and 8 kk + 4 + e: any pairing serves as long as both operands use it).
 // A 64-cycle MFMA leaves the LDS pipe idle whatever the tile, so the fp32 form takes 64 x 64 per wave (8 waves as 4 x 2: 256 x 128
 // per workgroup) and spends the registers on a second accumulator set: `acc` collects 8 steps (128 products), then is folded into
-// `sum` with vector adds -- blocked summation like the 128 x 128 kernel of mot_backward.hip and the reference's BLAS, which the
+// `sum` with vector adds -- blocked summation like the 128 x 128 kernel of mot_gemm_f32.hip and the reference's BLAS, which the
 // concat parity bar (twice the reference's own fp32 error) needs at K = 768.
 template <typename E, bool OUT_BF16, int MT, int NT, int WC>
 __global__ __launch_bounds__(kG2Threads) void gemm_rows_256_kernel(const E *__restrict__ A_, int lda, int64_t n, const E *__restrict__ B_, int ldb,
@@ -381,6 +383,154 @@ int launch_gemm_rows_bf16(const void *A_, int lda, int64_t n, const void *B_, in
         hipLaunchKernelGGL((gemm_rows_bf16_kernel<false, WM>), dim3((unsigned)blocks), dim3(128 * WM), 0, stream, (const __bf16 *)A_, lda, n,
                            (const __bf16 *)B_, ldb, R, Nc, C, ldc, (const __bf16 *)bias, addend);
     return check_launch("gemm_rows_bf16_kernel");
+}
+
+// C[m][k] += sum_n A[n][m] * B[n][k]   (A: rows x M, B: rows x Kc, both bf16 ROW-major as the forward and dy_kernel leave them;
+// C fp32, leading dimension ldc) on v_mfma_f32_32x32x16_bf16: dW = dy^T u with the token index as the contraction index.
+// Both MFMA operands want 8 consecutive CONTRACTION elements per lane, i.e. a column of the row-major tiles: the tiles go into
+// LDS as they are (64 token rows x 128 columns, rows padded to 320 bytes) and are read back with ds_read_b64_tr_b16, the
+// transposing LDS read of gfx950 -- a 16-lane group fetches 4 rows x 16 columns and every lane receives ONE column's 4 rows;
+// two reads make a lane's 8 contraction elements.  (Round 1 transposed dy and u in HBM first -- narrow_transpose /
+// transpose_bf16, 0.2 ms at 65 536 x 768 -- and contracted the token-minor copies: 0.30 ms more, with 85-fold split-k atomics.)
+// With 320-byte rows the four rows of a read sit 80 dwords apart: a 32-lane half (two groups, 32 columns) covers all 64 banks once.
+// Workgroup tile 128 x 128, 2 x 4 waves as 2 x 2, each 64 x 64; contraction split over blockIdx.z; partial tiles are added with
+// float atomics (128-byte contiguous segments).  128 x 128 keeps the split count -- and with it the atomic volume
+// (splits x M x Kc x 4 bytes) -- at 8 for 768 x 768 (two workgroups per CU).
+typedef float f32x16b __attribute__((ext_vector_type(16)));
+typedef __bf16 bf16x8w __attribute__((ext_vector_type(8)));
+typedef short s16x4w __attribute__((ext_vector_type(4)));
+constexpr int kTnRows = 64, kTnLd = 160;   // token rows per step; elements per staged row (128 data + 32 pad)
+constexpr int kTnThreads = 512;            // 8 waves: two per SIMD.  Waves 0-3 and 4-7 are the same 2 x 2 grid of 64 x 64 sub-tiles and split the
+                                           // step's four 16-row contraction slices between them; the two partial tiles meet in LDS at the end
+__global__ __launch_bounds__(kTnThreads) void gemm_tn_bf16_kernel(const __bf16 *__restrict__ A_, int lda, int M, const __bf16 *__restrict__ B_, int ldb, int Kc,
+                                                                  int64_t rows, int64_t rper, int nz, float *__restrict__ C, int ldc) {
+    extern __shared__ __attribute__((aligned(16))) __bf16 lds_tn[];   // [2][A | B][kTnRows][kTnLd]
+    constexpr int kTile = kTnRows * kTnLd;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, li = lane & 31;
+    // 1-D grid, XCD-aware: workgroup ids go round-robin over the 8 XCDs, so ids 8 g .. 8 g + 7 take the SAME output tile and the
+    // contraction slices z = 0 .. 7: all tiles of one slice then run on one XCD and its rows of A and B come out of that XCD's L2
+    // (every row is wanted by gx + gy tiles; without this they were fetched once per XCD and tile: 1.2 GB instead of 0.2 at 65 536 x 768)
+    const int gx = (M + 127) / 128, tiles = gx * ((Kc + 127) / 128);
+    int tile, z;
+    if ((nz & 7) == 0) { const int g = blockIdx.x >> 3; tile = g % tiles; z = (blockIdx.x & 7) + 8 * (g / tiles); }
+    else { tile = blockIdx.x % tiles; z = blockIdx.x / tiles; }
+    const int m0 = (tile % gx) * 128, k0 = (tile / gx) * 128;
+    const int64_t r_lo = (int64_t)z * rper, r_hi = min(rows, r_lo + rper);
+    const int wm = ((wave >> 1) & 1) * 64, wk = (wave & 1) * 64, ws = wave >> 2;   // ws: which two of the four contraction slices
+    f32x16b acc[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+    // staging: 64 rows x 16 pieces of 16 bytes per operand = 1024 pieces -> 2 per thread (16 lanes read one 256-byte row segment)
+    bf16x8w ra[2], rb[2];
+    auto load_stage = [&](int64_t r0) {
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const int q = p * kTnThreads + tid, row = q >> 4, c = (q & 15) * 8;
+            ra[p] = (bf16x8w)((__bf16)0.f); rb[p] = (bf16x8w)((__bf16)0.f);
+            if (r0 + row < r_hi) {   // M, Kc, lda, ldb are multiples of 8: a piece is wholly inside or outside
+                if (m0 + c < M) ra[p] = *(const bf16x8w *)(A_ + (r0 + row) * lda + m0 + c);
+                if (k0 + c < Kc) rb[p] = *(const bf16x8w *)(B_ + (r0 + row) * ldb + k0 + c);
+            }
+        }
+    };
+    auto store_stage = [&](int buf) {
+        __bf16 *sA = lds_tn + buf * 2 * kTile, *sB = sA + kTile;
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const int q = p * kTnThreads + tid, row = q >> 4, c = (q & 15) * 8;
+            *(bf16x8w *)(sA + row * kTnLd + c) = ra[p];
+            *(bf16x8w *)(sB + row * kTnLd + c) = rb[p];
+        }
+    };
+    // transposed fragment: lane 4 q + p of a 16-lane group g addresses row (r0 + q), columns c0 + 4 p .. + 3 of the group's 4 x 16 block;
+    // lane i of the group receives column c0 + i.  Group g: contraction half h = g >> 1, columns 16 (g & 1) .. + 15 of the 32-wide tile.
+    const int grp = lane >> 4, gi = lane & 15;
+    const int tr_off = ((gi >> 2) + 8 * (grp >> 1)) * kTnLd + 16 * (grp & 1) + 4 * (gi & 3);   // elements, inside a 16-row x 32-column operand block
+    auto frag = [&](const __bf16 *tile, int s16, int col0) {   // rows 16 s16 .. + 15 (contraction), columns col0 .. + 31
+        const __bf16 *p = tile + (16 * s16) * kTnLd + col0 + tr_off;
+        const s16x4w lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4w *)p);
+        const s16x4w hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4w *)(p + 4 * kTnLd));
+        typedef short s16x8w __attribute__((ext_vector_type(8)));
+        const s16x8w v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+        return __builtin_bit_cast(bf16x8w, v);
+    };
+    if (r_lo < r_hi) {
+        load_stage(r_lo);
+        store_stage(0);
+    }
+    __syncthreads();
+    int buf = 0;
+    for (int64_t r0 = r_lo; r0 < r_hi; r0 += kTnRows, buf ^= 1) {
+        const bool more = r0 + kTnRows < r_hi;
+        if (more) load_stage(r0 + kTnRows);
+        const __bf16 *sA = lds_tn + buf * 2 * kTile, *sB = sA + kTile;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int s16 = 2 * ws + j;
+            bf16x8w af[2], bf[2];
+#pragma unroll
+            for (int a = 0; a < 2; ++a) af[a] = frag(sA, s16, wm + 32 * a);
+#pragma unroll
+            for (int b = 0; b < 2; ++b) bf[b] = frag(sB, s16, wk + 32 * b);
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int b = 0; b < 2; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[a], bf[b], acc[a][b], 0, 0, 0);
+        }
+        if (more) store_stage(buf ^ 1);
+        __syncthreads();
+    }
+    // the second wave group's partial tile joins the first's through LDS (64 KB: the stage buffers are free now)
+    float *red = (float *)lds_tn + (size_t)(wave & 3) * 64 * 64;   // [a][b][r][lane] of one 64 x 64 sub-tile
+    if (ws == 1) {
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) red[((a * 2 + b) * 16 + r) * 64 + lane] = acc[a][b][r];
+    }
+    __syncthreads();
+    if (ws == 1) return;
+    // D[i][j]: lane -> j (B column = output column k), registers -> i (A column = output row m)
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int m = m0 + wm + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * h, k = k0 + wk + b * 32 + li;
+                if (m < M && k < Kc) atomicAdd(C + (int64_t)m * ldc + k, acc[a][b][r] + red[((a * 2 + b) * 16 + r) * 64 + lane]);
+            }
+}
+
+// A, B: 16-byte aligned, lda / ldb / M / Kc multiples of 8
+int launch_gemm_tn_bf16(const __bf16 *A_, int lda, int M, const __bf16 *B_, int ldb, int Kc, int64_t rows, float *C, int ldc, hipStream_t stream) {
+    if (M <= 0 || Kc <= 0 || rows <= 0) return MOT_OK;
+    // (the kernel loads whole 16-byte pieces and guards a piece by its first column only)
+    if ((lda & 7) || (ldb & 7) || (M & 7) || (Kc & 7) || ((uintptr_t)A_ & 15) || ((uintptr_t)B_ & 15))
+        return set_error(MOT_EUNSUPPORTED, "gemm_tn_bf16: rows must be 16-byte aligned, lda / ldb / M / Kc multiples of 8 (lda %d, ldb %d, M %d, Kc %d)", lda,
+                         ldb, M, Kc);
+    const int tiles = ((M + 127) / 128) * ((Kc + 127) / 128);
+    // contraction slices: two workgroups per CU (80 KB of LDS each), a multiple of 8 for the XCD mapping, few enough to keep the
+    // atomic volume (slices x M x Kc x 4 bytes) small
+    int64_t splits = (512 / tiles) & ~7;
+    if (splits < 8) splits = 8;
+    if (splits > 32) splits = 32;
+    int64_t rper = ((rows + splits - 1) / splits + kTnRows - 1) / kTnRows * kTnRows;
+    if (rper < 4 * kTnRows) rper = 4 * kTnRows;
+    splits = (rows + rper - 1) / rper;
+    if ((int64_t)tiles * splits > 0x7fffffffLL) return set_error(MOT_EUNSUPPORTED, "gemm_tn_bf16: too many tiles");
+    const size_t lds = (size_t)4 * kTnRows * kTnLd * sizeof(__bf16);
+    static std::atomic<uint64_t> lds_ok{0};
+    if (int rc = ensure_max_dyn_lds((const void *)gemm_tn_bf16_kernel, lds_ok, "gemm_tn_bf16_kernel")) return rc;
+    hipLaunchKernelGGL(gemm_tn_bf16_kernel, dim3((unsigned)(tiles * splits)), dim3(kTnThreads), lds, stream, A_, lda, M, B_, ldb, Kc, rows, rper, (int)splits,
+                       C, ldc);
+    return check_launch("gemm_tn_bf16_kernel");
 }
 
 }  // namespace mot

@@ -49,8 +49,10 @@ int launch_embed_mix_linear_ex(const MotEmbedMixDesc &d, const float *wt_prebuil
 size_t embed_mix_linear_workspace_bytes(const MotEmbedMixDesc &d);
 size_t embed_mix_linear_bf16_workspace_bytes(const MotEmbedMixDesc &d);
 int launch_embed_mix_linear_bf16(const MotEmbedMixDesc &d, hipStream_t stream);
+// the front-end backward, every mode (mot_backward.hip; CONCAT_LINEAR and MEAN continue in mot_bwd_linear.hip / mot_bwd_mean.hip)
 size_t embed_mix_bwd_workspace_bytes(const MotEmbedMixDesc &d);
 int launch_embed_mix_bwd(const MotEmbedMixDesc &d, const MotEmbedMixGrads &g, hipStream_t stream);
+// the shared fp32 matrix products (mot_gemm_f32.hip)
 // C[j][k] += sum_n A[n][j] * B[n][k]  (A: n x M, B: n x Nc; fp32 MFMA, atomic accumulate)
 int launch_gemm_tn(const float *A, int lda, int M, const float *B, int ldb, int Nc, int64_t n, float *C, int ldc, hipStream_t stream);
 // C[n][c] = sum_r A[n][r] * (b_transposed ? B[c][r] : B[r][c]) (+ bias[c]), fp32 MFMA, plain stores
@@ -80,17 +82,19 @@ bool gemm_rows_bf16_256_usable(const void *A, int lda, int64_t n, const void *B,
 bool gemm_rows_f32_256_usable(const float *A, int lda, int64_t n, const float *B, int ldb, int R, int Nc);
 int launch_gemm_rows_f32_256(const float *A, int lda, int64_t n, const float *B, int ldb, int R, int Nc, float *C, int ldc, const float *bias, bool accumulate,
                              hipStream_t stream);
-// C[m][k] += sum_n A[n][m] * B[n][k]  (bf16 row-major operands, fp32 atomics into C; mot_backward.hip); lda / ldb / M / Kc multiples of 8
+// C[m][k] += sum_n A[n][m] * B[n][k]  (bf16 row-major operands, fp32 atomics into C; mot_gemm_bf16.hip); lda / ldb / M / Kc multiples of 8
 int launch_gemm_tn_bf16(const __bf16 *A, int lda, int M, const __bf16 *B, int ldb, int Kc, int64_t rows, float *C, int ldc, hipStream_t stream);
+int launch_transpose_f32(const float *src, int rows, int cols, float *dst, hipStream_t stream);                        // dst[c][r] = src[r][c]  (mot_gemm_f32.hip)
+// conversions between the fp32 and bf16 sides (mot_convert.hip)
+int launch_widen(const void *src_bf16, size_t n, float *dst, hipStream_t stream);                                    // dst[i] = float(src[i])
 int launch_narrow(const float *src, int64_t n, void *dst_bf16, hipStream_t stream);                                  // dst[i] = bf16(src[i])
-int launch_transpose_f32(const float *src, int rows, int cols, float *dst, hipStream_t stream);                        // dst[c][r] = src[r][c]
+int launch_transpose_bf16(const void *src_bf16, int rows, int cols, void *dst_bf16, hipStream_t stream);             // dst[c][r] = src[r][c]
 int launch_narrow_transpose(const float *src, int rows, int cols, void *dst_bf16, hipStream_t stream);               // dst[c][r] = bf16(src[r][c])
-int launch_pad_copy(const float *src, int rows, int cols, float *dst, int rows_pad, int cols_pad, hipStream_t stream);
-// counting sort of positions 0..n-1 by ids[position] (mot_backward.hip); ws_ints: group_positions_ws_ints(n, rows) int32
+// counting sort of positions 0..n-1 by ids[position] (mot_group.hip); ws_ints: group_positions_ws_ints(n, rows) int32
 size_t group_positions_ws_ints(int64_t n, int64_t rows);
 int launch_group_positions(const int32_t *ids, int64_t n, int64_t rows, int32_t *ws_ints, const int32_t **pos_sorted, const int32_t **id_sorted,
                            uint32_t *status, hipStream_t stream);
-// zero n 32-bit words with a kernel (not hipMemsetAsync: a memset node aborts on graph replay with this runtime)
+// zero n 32-bit words with a kernel (not hipMemsetAsync: a memset node aborts on graph replay with this runtime; mot_group.hip)
 int launch_zero_words(void *p, int64_t n_words, hipStream_t stream);
 size_t cross_attn_bwd_workspace_bytes(const MotCrossAttnDesc &d);
 int launch_cross_attn_bwd(const MotCrossAttnDesc &d, const MotCrossAttnGrads &g, hipStream_t stream);
