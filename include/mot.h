@@ -555,6 +555,88 @@ size_t mot_byte_self_attn_workspace_bytes(const MotByteSelfAttnDesc *desc /* hos
 int mot_byte_self_attn_fwd(const MotByteSelfAttnDesc *desc /* host */, mot_stream_t stream);
 int mot_byte_self_attn_bwd(const MotByteSelfAttnDesc *fwd /* host */, const MotByteSelfAttnGrads *grads /* host */, mot_stream_t stream);
 
+/*
+ * Linear-on-bytes mixin, forward: replaces
+ *   mixin_bytes(token_embs, byte_embs, byte_fc)         modded-nanogpt/runs/71051_mot-in_toks-valemb.py:225-229 (norm 130-131)
+ *   on embed_tokens / embed_bytes at its call site      :312-314  (byte_fc: the parameter of :253, handed to Muon at :571)
+ * Per token n of row-major (B, T), with K = bpt * byte_dim:
+ *   u_n = cat_k byte_table[ids[n, k]]                   (the token's bpt byte rows side by side)
+ *   x_n = rms_norm?(tok_table[tokens[n]] + byte_fc u_n)  byte_fc [model_dim, K], nn.Linear layout, no bias
+ * tok_dim == model_dim; K need not equal model_dim.  No per-embedding norms, no learned scalars, one id tensor: the ids are
+ * given (MOT_IDS_GIVEN, `ids`) or come from the token->byte table (MOT_IDS_FROM_TTB: tokens_to_bytes, then pull_dir), with the
+ * int64 id outputs, counters and status word of MotEmbedMixDesc; out-of-range ids are clamped to row 0 and flagged.
+ * MOT_F32: everything fp32, the product on the blocked fp32 MFMA summation of the other mixins.
+ * MOT_BF16: tables, byte_fc, `out` and grad_out bf16, arithmetic fp32, rounded where the reference's bf16 run rounds:
+ *   p = bf16(byte_fc u) (fp32 sums), s = bf16(tok + p), r = rsqrt(mean(s^2) + eps) in fp32, x = bf16(r s).
+ * eps <= 0 means FLT_EPSILON for BOTH dtypes: F.rms_norm(eps=None) takes the epsilon of its fp32 opmath type on bf16 rows too (as
+ * MotByteHeadDesc.eps); pass 2^-7 explicitly for torch.finfo(bfloat16).eps.
+ * model_dim and K at most 2048; model_dim and byte_dim multiples of the 16-byte vector (4 fp32 / 8 bf16 elements).
+ */
+#define MOT_BYTE_FC_COMPOSED 1u /* MotByteFcMixDesc.flags, bf16 forward: the separate gather / product / row-pass kernels even where the one gather-GEMM qualifies */
+
+typedef struct MotByteFcMixDesc {
+    uint32_t struct_size;   /* sizeof(MotByteFcMixDesc), checked */
+    int32_t dtype;          /* MotDType of tables / byte_fc / out */
+    int64_t n_rows;         /* B */
+    int64_t tokens_per_row; /* T */
+    int32_t bpt;            /* byte slots per token */
+    int32_t id_source;      /* MOT_IDS_FROM_TTB | MOT_IDS_GIVEN */
+    const int32_t *tokens;  /* [B, T] */
+    int32_t pull_dir;       /* MotPullDir           (FROM_TTB) */
+    int32_t ttb_elem_bytes; /* 2 | 4                (FROM_TTB) */
+    const void *ttb;        /* [ttb_rows, bpt]      (FROM_TTB) */
+    int64_t ttb_rows;
+    int32_t pad_byte, eot_byte;
+    const int64_t *ids;     /* [B, T*bpt]           (GIVEN) */
+    const void *tok_table;  /* [tok_rows, tok_dim] */
+    int64_t tok_rows;
+    int32_t tok_dim;        /* == model_dim */
+    int32_t byte_dim;
+    const void *byte_table; /* [byte_rows, byte_dim] */
+    int64_t byte_rows;
+    int32_t model_dim;
+    int32_t norm_out;       /* 0: x = tok + byte_fc u */
+    const void *byte_fc;    /* [model_dim, bpt*byte_dim] */
+    float eps;              /* <= 0 -> FLT_EPSILON, both dtypes */
+    uint32_t flags;         /* MOT_BYTE_FC_*; unknown bits are refused */
+    void *out;              /* [B, T, model_dim] */
+    float *out_row_rnorm;   /* optional [B, T] fp32: r of every row (1 without the norm); the fp32 backward needs it when norm_out */
+    int64_t *out_ids_padded; /* optional [B, T*bpt] (FROM_TTB) */
+    int64_t *out_ids_pulled; /* optional [B, T*bpt] (FROM_TTB) */
+    int64_t *counters;      /* optional int64[4], as MotEmbedMixDesc.counters */
+    uint32_t *status;       /* optional device word, see MOT_STATUS_* */
+    void *workspace;        /* >= mot_byte_fc_mix_workspace_bytes (forward) / mot_byte_fc_mix_bwd_workspace_bytes (backward) */
+    size_t workspace_bytes;
+} MotByteFcMixDesc;
+
+/*
+ * Backward: `fwd` is the forward's descriptor with id_source == MOT_IDS_GIVEN (the ids the forward used); the id outputs and
+ * counters are ignored.  With x = r s:
+ *   ds = r (g - x (g.x) / model_dim)   (ds = g without the norm)
+ *   d_tok[tokens[n]] += ds_n;   d_byte_fc += sum_n ds_n^T u_n;   du = ds byte_fc;   d_byte[ids[n,k]] += du_n[k*byte_dim ..]
+ * u is gathered again.  MOT_F32 with norm_out reads the forward's x (`out`) and `out_row_rnorm`.  MOT_BF16 reads neither: a bf16 x
+ * is three roundings away from the exact row, which would leave ds, and with it the token-table gradient, 2e-4 .. 8e-4 off; there
+ * the product byte_fc u is formed again with its fp32 sums kept and s, r and x come from it in fp32 (one more product of the
+ * forward's size; `out` and `out_row_rnorm` may be NULL).  Every gradient buffer is FP32 and ACCUMULATED into (+=), also with bf16
+ * tables (there ds stays fp32 for the token table, and du and d_byte_fc run on the bf16 MFMA from bf16(ds) with fp32 sums).  Sums
+ * use float atomics.
+ */
+typedef struct MotByteFcMixGrads {
+    uint32_t struct_size;  /* sizeof(MotByteFcMixGrads) */
+    uint32_t reserved;
+    const void *grad_out;  /* [B, T, model_dim] in dtype */
+    void *d_tok;           /* [tok_rows, model_dim]     fp32 */
+    void *d_byte;          /* [byte_rows, byte_dim]     fp32 */
+    void *d_byte_fc;       /* [model_dim, bpt*byte_dim] fp32 */
+    const int32_t *token_order; /* optional: what mot_token_order wrote for fwd->tokens (same n_tokens, tok_rows) */
+} MotByteFcMixGrads;
+
+size_t mot_byte_fc_mix_desc_size(void);
+size_t mot_byte_fc_mix_workspace_bytes(const MotByteFcMixDesc *desc /* host */);     /* 0 for a descriptor the call would refuse */
+size_t mot_byte_fc_mix_bwd_workspace_bytes(const MotByteFcMixDesc *fwd /* host */);  /* likewise */
+int mot_byte_fc_mix_fwd(const MotByteFcMixDesc *desc /* host */, mot_stream_t stream);
+int mot_byte_fc_mix_bwd(const MotByteFcMixDesc *fwd /* host */, const MotByteFcMixGrads *grads /* host */, mot_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,7 @@ ABI_VERSION = 13
 HEAD_COPY, HEAD_SPLIT = 0, 1
 HEAD_VOCAB = 512
 FLAG_LINEAR_ONE_LAUNCH, FLAG_MEAN_GENERIC, FLAG_BWD_DU_FP32, FLAG_LINEAR_COMPOSED = 1, 2, 4, 8
+BYTE_FC_COMPOSED = 1
 HEADS_AS_VIEWED, HEADS_PER_TOKEN = 0, 1
 
 
@@ -55,6 +56,8 @@ EXPORTS = (
     "mot_byte_head_desc_size", "mot_byte_head_workspace_bytes", "mot_byte_head_fwd", "mot_byte_head_bwd",
     "mot_byte_self_attn_desc_size", "mot_byte_self_attn_saved_bytes", "mot_byte_self_attn_workspace_bytes",
     "mot_byte_self_attn_fwd", "mot_byte_self_attn_bwd",
+    "mot_byte_fc_mix_desc_size", "mot_byte_fc_mix_workspace_bytes", "mot_byte_fc_mix_bwd_workspace_bytes",
+    "mot_byte_fc_mix_fwd", "mot_byte_fc_mix_bwd",
 )
 SWA_NO_RESIDUAL, SWA_ONE_RESIDUAL, SWA_TWO_RESIDUAL = 0, 1, 2
 
@@ -158,6 +161,28 @@ class MotByteSelfAttnGrads(C.Structure):
     ]
 
 
+class MotByteFcMixDesc(C.Structure):
+    """Mirror of struct MotByteFcMixDesc (include/mot.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("dtype", C.c_int32), ("n_rows", C.c_int64), ("tokens_per_row", C.c_int64),
+        ("bpt", C.c_int32), ("id_source", C.c_int32), ("tokens", C.c_void_p), ("pull_dir", C.c_int32), ("ttb_elem_bytes", C.c_int32),
+        ("ttb", C.c_void_p), ("ttb_rows", C.c_int64), ("pad_byte", C.c_int32), ("eot_byte", C.c_int32), ("ids", C.c_void_p),
+        ("tok_table", C.c_void_p), ("tok_rows", C.c_int64), ("tok_dim", C.c_int32), ("byte_dim", C.c_int32),
+        ("byte_table", C.c_void_p), ("byte_rows", C.c_int64), ("model_dim", C.c_int32), ("norm_out", C.c_int32),
+        ("byte_fc", C.c_void_p), ("eps", C.c_float), ("flags", C.c_uint32),
+        ("out", C.c_void_p), ("out_row_rnorm", C.c_void_p), ("out_ids_padded", C.c_void_p), ("out_ids_pulled", C.c_void_p),
+        ("counters", C.c_void_p), ("status", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
+class MotByteFcMixGrads(C.Structure):
+    """Mirror of struct MotByteFcMixGrads (include/mot.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("grad_out", C.c_void_p), ("d_tok", C.c_void_p), ("d_byte", C.c_void_p),
+        ("d_byte_fc", C.c_void_p), ("token_order", C.c_void_p),
+    ]
+
+
 def _load() -> C.CDLL:
     if not LIB_PATH.exists():
         raise ImportError(
@@ -212,6 +237,14 @@ def _load() -> C.CDLL:
     lib.mot_byte_self_attn_fwd.restype = C.c_int
     lib.mot_byte_self_attn_bwd.argtypes = [C.POINTER(MotByteSelfAttnDesc), C.POINTER(MotByteSelfAttnGrads), vp]
     lib.mot_byte_self_attn_bwd.restype = C.c_int
+    lib.mot_byte_fc_mix_desc_size.restype = C.c_size_t
+    for name in ("mot_byte_fc_mix_workspace_bytes", "mot_byte_fc_mix_bwd_workspace_bytes"):
+        getattr(lib, name).restype = C.c_size_t
+        getattr(lib, name).argtypes = [C.POINTER(MotByteFcMixDesc)]
+    lib.mot_byte_fc_mix_fwd.argtypes = [C.POINTER(MotByteFcMixDesc), vp]
+    lib.mot_byte_fc_mix_fwd.restype = C.c_int
+    lib.mot_byte_fc_mix_bwd.argtypes = [C.POINTER(MotByteFcMixDesc), C.POINTER(MotByteFcMixGrads), vp]
+    lib.mot_byte_fc_mix_bwd.restype = C.c_int
     for name in ("mot_tokens_to_bytes", "mot_pull_bytes", "mot_create_batch", "mot_char_matrix", "mot_gather_rows", "mot_embed_mix_fwd",
                  "mot_embed_mix_bwd"):
         getattr(lib, name).restype = C.c_int
@@ -227,6 +260,8 @@ def _load() -> C.CDLL:
         raise ImportError("MotByteHeadDesc layout mismatch between include/mot.h and _capi.py")
     if lib.mot_byte_self_attn_desc_size() != C.sizeof(MotByteSelfAttnDesc):
         raise ImportError("MotByteSelfAttnDesc layout mismatch between include/mot.h and _capi.py")
+    if lib.mot_byte_fc_mix_desc_size() != C.sizeof(MotByteFcMixDesc):
+        raise ImportError("MotByteFcMixDesc layout mismatch between include/mot.h and _capi.py")
     return lib
 
 

@@ -1,6 +1,7 @@
 // mot_bwd.hpp -- what the three units of the front-end backward share: mot_backward.hip (the table-gradient scatter, SUM / NOOP /
 // CONCAT and the entry launch_embed_mix_bwd), mot_bwd_linear.hip (CONCAT_LINEAR) and mot_bwd_mean.hip (MEAN).  The two
-// latter compute their dense parts and hand the table gradients to the scatter through run_scatter().  No other unit includes it.
+// latter compute their dense parts and hand the table gradients to the scatter through run_scatter().  One unit outside the
+// front-end backward includes it: mot_bytefc.hip, whose gradient rows [ds | du] are the split rows of the CONCAT_LINEAR scatter.
 #pragma once
 #include "mot_mix.hpp"
 

@@ -428,4 +428,22 @@ int mot_byte_self_attn_bwd(const MotByteSelfAttnDesc *desc, const MotByteSelfAtt
     return launch_byte_self_attn_bwd(*desc, *grads, (hipStream_t)stream);
 }
 
+size_t mot_byte_fc_mix_desc_size(void) { return sizeof(MotByteFcMixDesc); }
+
+size_t mot_byte_fc_mix_workspace_bytes(const MotByteFcMixDesc *desc) { return byte_fc_mix_workspace_bytes(desc); }
+
+size_t mot_byte_fc_mix_bwd_workspace_bytes(const MotByteFcMixDesc *desc) { return byte_fc_mix_bwd_workspace_bytes(desc); }
+
+int mot_byte_fc_mix_fwd(const MotByteFcMixDesc *desc, mot_stream_t stream) {
+    if (int rc = byte_fc_check(desc, nullptr, false)) return rc;
+    if (desc->n_rows == 0 || desc->tokens_per_row == 0) return MOT_OK;
+    return launch_byte_fc_mix_fwd(*desc, (hipStream_t)stream);
+}
+
+int mot_byte_fc_mix_bwd(const MotByteFcMixDesc *desc, const MotByteFcMixGrads *grads, mot_stream_t stream) {
+    if (int rc = byte_fc_check(desc, grads, true)) return rc;
+    if (desc->n_rows == 0 || desc->tokens_per_row == 0) return MOT_OK;
+    return launch_byte_fc_mix_bwd(*desc, *grads, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -96,7 +96,11 @@ __device__ __forceinline__ void c16_barrier() {
 // passes of 512 (the tile's ids, rms factors and token-row norms are made once; the gathered operand is walked twice, out of L2):
 // pass 0 stores y un-normalised and keeps each row's sum of squares, pass 1 completes the sum, stores its half normalised and
 // rescales the first half in place (every lane re-reads exactly the pieces it wrote).
-template <int MT, int NT, int NS, int NH = 1>
+// RES: the residual form for the linear-on-bytes mixin (mot_bytefc.hip, runs/71051_*.py:225-229), x = norm(tok + W . cat(bytes)): the
+// caller passes Dt = 0, so the K loop walks the byte part only and the token row never enters the contraction; it is added in the
+// epilogue's row pass instead, where 32 lanes hold a row in 16-byte pieces -- after the product was rounded to bf16, and the sum is
+// rounded before the squares are taken (the reference's bf16 tensors: F.linear's result, the add).  Rows are Dm wide there.
+template <int MT, int NT, int NS, int NH = 1, bool RES = false>
 __global__ __launch_bounds__(kC16Threads) void concat16_gemm_kernel(const C16Args P) {
     constexpr int BM = 64 * MT, BN = 128 * NT, WMR = 32 * MT, WNR = 32 * NT, PD = NS - 1;
     constexpr int kStageB = BN * 64, kStageA = BM * 64, kDma = BN * 4 / kC16Threads;
@@ -405,9 +409,20 @@ __global__ __launch_bounds__(kC16Threads) void concat16_gemm_kernel(const C16Arg
             const int row = half * WMR + lr;
             bf16x8c v[PP];
             float ss = 0.f;
+            const __bf16 *res_row = nullptr;
+            if constexpr (RES) {   // the row's token (rows past the batch repeat the last one: computed, never stored)
+                int tk = P.tokens[j0 + min(row, nrows - 1)];
+                if ((uint64_t)(uint32_t)tk >= (uint64_t)P.tok_rows) tk = 0;   // (flagged in the prologue)
+                res_row = P.tok_table + (int64_t)tk * P.Dm + cb;
+            }
 #pragma unroll
             for (int p = 0; p < PP; ++p) {
                 v[p] = *(const bf16x8c *)(stage + lr * BN + 8 * (li + 32 * p));
+                if constexpr (RES) {
+                    const bf16x8c t = *(const bf16x8c *)(res_row + 8 * (li + 32 * p));
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) v[p][e] = (__bf16)((float)v[p][e] + (float)t[e]);
+                }
 #pragma unroll
                 for (int e = 0; e < 8; ++e) ss += (float)v[p][e] * (float)v[p][e];
             }
@@ -460,17 +475,17 @@ __global__ __launch_bounds__(kC16Threads) void concat16_gemm_kernel(const C16Arg
 }
 
 static size_t c16_lds_base(int MT, int NT, int NS, int bpt);
-template <int MT, int NT, int NS, int NH = 1>
+template <int MT, int NT, int NS, int NH = 1, bool RES = false>
 static int launch_c16(const C16Args &P0, hipStream_t stream) {
     constexpr int BM = 64 * MT;
     const C16Args &P = P0;
     const size_t lds = c16_lds_base(MT, NT, NS, P.bpt) + (size_t)P.byte_rows * 4 + (NH > 1 ? BM * 4 : 0);
     if (lds > 160 * 1024) return set_error(MOT_EUNSUPPORTED, "concat16: needs %zu B of LDS", lds);
     static std::atomic<uint64_t> ok{0};
-    if (int rc = ensure_max_dyn_lds((const void *)concat16_gemm_kernel<MT, NT, NS, NH>, ok, "concat16_gemm_kernel")) return rc;
+    if (int rc = ensure_max_dyn_lds((const void *)concat16_gemm_kernel<MT, NT, NS, NH, RES>, ok, "concat16_gemm_kernel")) return rc;
     const int64_t blocks = (P.n + BM - 1) / BM;
     if (blocks > 0x7fffffffLL) return set_error(MOT_EUNSUPPORTED, "concat16: too many rows");
-    hipLaunchKernelGGL((concat16_gemm_kernel<MT, NT, NS, NH>), dim3((unsigned)blocks), dim3(kC16Threads), lds, stream, P);
+    hipLaunchKernelGGL((concat16_gemm_kernel<MT, NT, NS, NH, RES>), dim3((unsigned)blocks), dim3(kC16Threads), lds, stream, P);
 #ifdef C16_STAMPS
     static int calls = 0;
     if (++calls == 60) {
@@ -587,10 +602,19 @@ bool concat16_usable(const MotEmbedMixDesc &d) {
     return c16_lds_base(sh.MT, sh.NT, sh.NS, d.bpt) + (size_t)d.byte_rows * 4 + (sh.NH > 1 ? 64 * sh.MT * 4 : 0) <= 160 * 1024;
 }
 
+// the residual form (RES above) takes the same family with the token part out of the contraction: tok_dim == model_dim, K = bpt * byte_dim
+bool concat16_residual_usable(const MotEmbedMixDesc &d) {
+    if (d.tok_dim != d.model_dim || d.norm_tok || d.norm_byte || d.bias || d.bytes_first) return false;
+    MotEmbedMixDesc b = d;
+    b.tok_dim = 0;
+    return concat16_usable(b);
+}
+
 // rn_byte: per-row rms factors of the byte table (launch_rows_rnorm); null when the byte part is not normalised or the table is
 // small enough for the workgroups to compute them (concat16_norm_in_kernel)
+// residual: d.weight is [model_dim, bpt * byte_dim] and the token row is added behind the product (concat16_residual_usable)
 int launch_concat16(const MotEmbedMixDesc &d, const int32_t *tokens, const int64_t *ids, const uint16_t *ids16, int64_t n, const float *rn_byte,
-                    void *out, float *row_rnorm, hipStream_t stream) {
+                    void *out, float *row_rnorm, hipStream_t stream, bool residual) {
     C16Args P;
     P.tokens = tokens; P.ids = ids; P.ids16 = ids16; P.n = n;
     P.tok_table = (const __bf16 *)d.tok_table; P.tok_rows = d.tok_rows; P.Dt = d.tok_dim;
@@ -601,6 +625,15 @@ int launch_concat16(const MotEmbedMixDesc &d, const int32_t *tokens, const int64
     P.tok_lo = d.bytes_first ? d.bpt * d.byte_dim : 0; P.byte_lo = d.bytes_first ? 0 : d.tok_dim;
     P.norm_out = d.norm_out; P.eps = d.eps > 0.f ? d.eps : kBf16Eps;
     P.out = (__bf16 *)out; P.row_rnorm = d.norm_out ? row_rnorm : nullptr; P.status = d.status;
+    if (residual) {
+        P.Dt = 0; P.K = d.bpt * d.byte_dim; P.tok_lo = P.byte_lo = 0;
+        switch (d.model_dim) {
+            case 256: return launch_c16<2, 2, 3, 1, true>(P, stream);
+            case 512: return launch_c16<2, 4, 3, 1, true>(P, stream);
+            case 768: return launch_c16<2, 6, 3, 1, true>(P, stream);
+            default: return launch_c16<2, 4, 3, 2, true>(P, stream);
+        }
+    }
     switch (d.model_dim) {
         case 256: return launch_c16<2, 2, 3>(P, stream);
         case 512: return launch_c16<2, 4, 3>(P, stream);

@@ -72,8 +72,9 @@ int launch_embed_mix_linear_composed(const MotEmbedMixDesc &d, hipStream_t strea
 // mot_concat16.hip: gather + contraction + bias + output norm of the bf16 concat + linear mixin in one kernel
 bool concat16_usable(const MotEmbedMixDesc &d);
 bool concat16_norm_in_kernel(const MotEmbedMixDesc &d);   // the byte rows' rms factors need no table from the caller
+bool concat16_residual_usable(const MotEmbedMixDesc &d);   // the residual form: the token row (tok_dim == model_dim) added behind the product of the byte part
 int launch_concat16(const MotEmbedMixDesc &d, const int32_t *tokens, const int64_t *ids, const uint16_t *ids16, int64_t n, const float *rn_byte,
-                    void *out, float *row_rnorm, hipStream_t stream);
+                    void *out, float *row_rnorm, hipStream_t stream, bool residual = false);
 int launch_wave_ids16(const MotEmbedMixDesc &d, uint16_t *ids16, hipStream_t stream);   // ids from the token->byte table, 16-bit, + parity outputs
 int launch_gemm_rows_bf16(const void *A, int lda, int64_t n, const void *B, int ldb, int R, int Nc, void *C, int ldc, bool out_bf16,
                           const void *bias, hipStream_t stream, bool accumulate = false, const float *addend = nullptr);   // addend: fp32 [n][ldc] added before the store
@@ -112,5 +113,11 @@ size_t byte_self_attn_saved_bytes(const MotByteSelfAttnDesc &d);
 size_t byte_self_attn_workspace_bytes(const MotByteSelfAttnDesc &d);
 int launch_byte_self_attn_fwd(const MotByteSelfAttnDesc &d, hipStream_t stream);
 int launch_byte_self_attn_bwd(const MotByteSelfAttnDesc &d, const MotByteSelfAttnGrads &g, hipStream_t stream);
+// the linear-on-bytes mixin (mot_bytefc.hip): validation before any HIP call (g: backward only), then the launches
+int byte_fc_check(const MotByteFcMixDesc *d, const MotByteFcMixGrads *g, bool backward);
+size_t byte_fc_mix_workspace_bytes(const MotByteFcMixDesc *d);       // 0 for a descriptor the call would refuse
+size_t byte_fc_mix_bwd_workspace_bytes(const MotByteFcMixDesc *d);   // likewise
+int launch_byte_fc_mix_fwd(const MotByteFcMixDesc &d, hipStream_t stream);
+int launch_byte_fc_mix_bwd(const MotByteFcMixDesc &d, const MotByteFcMixGrads &g, hipStream_t stream);
 
 }  // namespace mot

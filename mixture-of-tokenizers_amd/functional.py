@@ -1023,3 +1023,195 @@ def byte_self_attn(x: torch.Tensor, qkv_w: torch.Tensor, proj_w: torch.Tensor, l
     `window` is in bytes (sliding_window_tokens * bpt, at most 256); block_causal = mix_byte_in_tok.  float32; differentiable in x,
     qkv_w, proj_w and lambdas.  A non-contiguous x is copied."""
     return _ByteSelfAttnFn.apply(x, qkv_w, proj_w, lambdas, cos, sin, int(bpt), int(window), bool(block_causal))
+
+
+# ------------------------------------------------------------------------------------------------
+# linear-on-bytes mixin (modded-nanogpt/runs/71051_*.py:225-229): x = norm(E_tok[tok] + byte_fc . cat_k E_byte[id_k])
+# ------------------------------------------------------------------------------------------------
+_BYTE_FC_COMPOSED = bool(os.environ.get("MOT_BYTE_FC_COMPOSED"))   # kernel-selection switch, read once at import like _ENV_FLAGS above
+
+
+def _byte_fc_desc(tokens, tok_table, byte_table, byte_fc, bpt, norm_out, eps):
+    """The descriptor's problem part, checked: tokens (B, T) int32 contiguous, the three float tensors of one dtype."""
+    if tokens.ndim == 1:
+        tokens = tokens[None]
+    if tokens.ndim != 2:
+        raise ValueError("tokens must be (B, T) or (T,)")
+    tok = tokens.to(torch.int32) if tokens.dtype != torch.int32 else tokens
+    tok = tok if tok.is_contiguous() else tok.contiguous()
+    tt = _table(tok_table, "tok_table")
+    bt = _table(byte_table, "byte_table", tt.dtype)
+    w = _table(byte_fc, "byte_fc", tt.dtype)
+    if tt.ndim != 2 or bt.ndim != 2 or w.ndim != 2 or tuple(w.shape) != (tt.shape[1], int(bpt) * bt.shape[1]):
+        raise ValueError(f"byte_fc must be (model_dim, bpt*byte_dim) = ({tt.shape[1]}, {int(bpt)}*{bt.shape[1]}), got {tuple(w.shape)}")
+    B, T = tok.shape
+    d = capi.MotByteFcMixDesc()
+    d.struct_size = C.sizeof(capi.MotByteFcMixDesc)
+    d.dtype = capi.dtype_code(tt.dtype)
+    d.n_rows, d.tokens_per_row, d.bpt = B, T, int(bpt)
+    d.tokens = capi.ptr(tok)
+    d.tok_table, d.tok_rows, d.tok_dim, d.model_dim = capi.ptr(tt), tt.shape[0], tt.shape[1], tt.shape[1]
+    d.byte_table, d.byte_rows, d.byte_dim = capi.ptr(bt), bt.shape[0], bt.shape[1]
+    d.byte_fc = capi.ptr(w)
+    d.norm_out, d.eps = int(bool(norm_out)), float(eps or 0.0)
+    return d, tok, [tok, tt, bt, w]
+
+
+@torch.compiler.disable
+def _byte_fc_mix_fwd(tokens, tok_table, byte_table, byte_fc, *, bpt, ids=None, ttb=None, pull=None, pad_byte=456, eot_byte=457,
+                     norm_out=True, eps=None, return_ids=False, counters=None, row_rnorm=None, composed=None):
+    dev = capi.require_device(tokens, tok_table, byte_table, byte_fc, ids, ttb)
+    d, tok, keep = _byte_fc_desc(tokens, tok_table, byte_table, byte_fc, bpt, norm_out, eps)
+    d.flags = capi.BYTE_FC_COMPOSED if (_BYTE_FC_COMPOSED if composed is None else composed) else 0
+    B, T = tok.shape
+    ids_padded = ids_pulled = None
+    if ttb is not None:
+        tab = _int_table(ttb, "byte_fc_mix")
+        if tab.shape[1] != bpt:
+            raise ValueError(f"ttb has {tab.shape[1]} slots per token, bpt={bpt}")
+        keep.append(tab)
+        d.id_source, d.pull_dir = capi.IDS_FROM_TTB, _PULLS[pull]
+        d.ttb, d.ttb_rows, d.ttb_elem_bytes = capi.ptr(tab), tab.shape[0], tab.element_size()
+        if return_ids:
+            ids_padded = torch.empty((B, T * bpt), dtype=torch.int64, device=dev)
+            ids_pulled = torch.empty((B, T * bpt), dtype=torch.int64, device=dev)
+            d.out_ids_padded, d.out_ids_pulled = capi.ptr(ids_padded), capi.ptr(ids_pulled)
+    else:
+        if ids is None:
+            raise ValueError("either ttb or ids must be given")
+        ia = _contig(ids, torch.int64, "ids")
+        if ia.numel() != B * T * bpt:
+            raise ValueError("byte ids must hold bytes_per_token ids per token")
+        keep.append(ia)
+        d.id_source, d.ids = capi.IDS_GIVEN, capi.ptr(ia)
+    d.pad_byte, d.eot_byte = int(pad_byte), int(eot_byte)
+    out = torch.empty((B, T, d.model_dim), dtype=tok_table.dtype, device=dev)
+    if B * T == 0:   # an empty batch: nothing to launch (torch hands out null pointers for empty tensors, which the C validation refuses)
+        return MixResult(out, ids_padded, ids_pulled) if return_ids else out
+    d.out = capi.ptr(out)
+    if counters is not None:
+        if counters.dtype != torch.int64 or counters.numel() < 4 or counters.device != dev:
+            raise ValueError("counters must be an int64[4] tensor on the inputs' device")
+        d.counters = capi.ptr(counters)
+    if row_rnorm is not None:
+        assert row_rnorm.dtype == torch.float32 and row_rnorm.numel() == B * T and row_rnorm.is_contiguous()
+        d.out_row_rnorm = capi.ptr(row_rnorm)
+    d.status = capi.ptr(capi.status_word(dev))
+    ws = _workspace(dev, capi.lib.mot_byte_fc_mix_workspace_bytes(C.byref(d)))
+    if ws is not None:
+        d.workspace, d.workspace_bytes = capi.ptr(ws), ws.numel()
+    capi.check(capi.lib.mot_byte_fc_mix_fwd(C.byref(d), capi.stream_of(dev)))
+    capi.after_call(dev)
+    return MixResult(out, ids_padded, ids_pulled) if return_ids else out
+
+
+@torch.compiler.disable
+def byte_fc_mix_backward(grad_out, tokens, tok_table, byte_table, byte_fc, *, bpt, ids, norm_out=True, eps=None, out=None, row_rnorm=None,
+                         token_order=None, into=None) -> dict:
+    """One call of mot_byte_fc_mix_bwd.  Returns dense fp32 gradients {tok_table, byte_table, byte_fc} -- fp32 also for bfloat16
+    parameters (the autograd node rounds once); `into` (same keys, fp32) accumulates into existing buffers.  With norm_out the
+    float32 backward needs the forward's output `out` and its `row_rnorm`; the bfloat16 backward forms the pre-norm row again
+    and reads neither (include/mot.h).  `token_order` as in :func:`embed_mix_backward`."""
+    dev = capi.require_device(grad_out, tokens, tok_table, byte_table, byte_fc, ids, out, row_rnorm)
+    d, tok, keep = _byte_fc_desc(tokens, tok_table, byte_table, byte_fc, bpt, norm_out, eps)
+    B, T = tok.shape
+    dt = tok_table.dtype
+    g = _contig(grad_out, dt, "grad_out")
+    ia = _contig(ids, torch.int64, "ids")
+    if g.numel() != B * T * d.model_dim or ia.numel() != B * T * bpt:
+        raise ValueError("grad_out must be (B, T, model_dim) and ids (B, T*bpt)")
+    keep += [g, ia]
+    d.id_source, d.ids = capi.IDS_GIVEN, capi.ptr(ia)
+    if norm_out and dt == torch.float32:
+        if out is None or row_rnorm is None:
+            raise ValueError("byte_fc_mix backward with norm_out needs the forward's output and row_rnorm")
+        xo = _contig(out, dt, "out")
+        keep.append(xo)
+        d.out, d.out_row_rnorm = capi.ptr(xo), capi.ptr(row_rnorm)
+    into = into or {}
+    res = {}
+    for k, p in (("tok_table", tok_table), ("byte_table", byte_table), ("byte_fc", byte_fc)):
+        res[k] = into[k] if into.get(k) is not None else torch.zeros(p.shape, dtype=torch.float32, device=dev)
+    if B * T == 0:   # an empty batch adds nothing
+        return res
+    gr = capi.MotByteFcMixGrads()
+    gr.struct_size = C.sizeof(capi.MotByteFcMixGrads)
+    gr.grad_out, gr.d_tok, gr.d_byte, gr.d_byte_fc = capi.ptr(g), capi.ptr(res["tok_table"]), capi.ptr(res["byte_table"]), capi.ptr(res["byte_fc"])
+    if token_order is not None:
+        need = capi.lib.mot_token_order_ints(B * T, tok_table.shape[0])
+        if token_order.dtype != torch.int32 or token_order.numel() != need or token_order.device != dev or not token_order.is_contiguous():
+            raise ValueError(f"token_order must be the contiguous int32[{need}] tensor token_order(tokens, {tok_table.shape[0]}) returned")
+        gr.token_order = capi.ptr(token_order)
+        keep.append(token_order)
+    d.status = capi.ptr(capi.status_word(dev))
+    ws = _workspace(dev, capi.lib.mot_byte_fc_mix_bwd_workspace_bytes(C.byref(d)))
+    if ws is not None:
+        d.workspace, d.workspace_bytes = capi.ptr(ws), ws.numel()
+    capi.check(capi.lib.mot_byte_fc_mix_bwd(C.byref(d), C.byref(gr), capi.stream_of(dev)))
+    capi.after_call(dev)
+    return res
+
+
+class _ByteFcMixFn(torch.autograd.Function):
+    """Autograd node of the linear-on-bytes mixin: one mot_byte_fc_mix_fwd call forward, one mot_byte_fc_mix_bwd call backward for
+    the two tables and byte_fc.  Saved: the byte ids and, for float32 tensors, the output and the per-row factor (4 bytes per token);
+    u is gathered again."""
+
+    @staticmethod
+    def forward(ctx, tok_table, byte_table, byte_fc, tokens, kw):
+        kw = dict(kw)
+        user_return_ids = kw.pop("return_ids", False)
+        from_ttb = kw.get("ttb") is not None
+        t2 = tokens if tokens.ndim == 2 else tokens[None]
+        saves_x = kw.get("norm_out", True) and tok_table.dtype == torch.float32
+        rn = torch.empty(t2.shape, dtype=torch.float32, device=tok_table.device) if saves_x else None
+        r = _byte_fc_mix_fwd(tokens, tok_table.detach(), byte_table.detach(), byte_fc.detach(), return_ids=from_ttb or user_return_ids,
+                             row_rnorm=rn, **kw)
+        x = r.x if isinstance(r, MixResult) else r
+        ids = kw.get("ids")
+        if from_ttb:
+            ids = r.ids_pulled if kw.get("pull") not in (None, "none") else r.ids_padded
+        ctx.order = _token_orders.get(tokens, tok_table.shape[0]) if _HOIST_SORT else None
+        ctx.save_for_backward(tok_table, byte_table, byte_fc, tokens, ids, x if rn is not None else None, rn)
+        ctx.kw = dict(bpt=kw["bpt"], norm_out=kw.get("norm_out", True), eps=kw.get("eps"))
+        if user_return_ids:
+            ctx.mark_non_differentiable(r.ids_padded, r.ids_pulled)
+            return x, r.ids_padded, r.ids_pulled
+        return x
+
+    @staticmethod
+    def backward(ctx, gx, *_):
+        tok_table, byte_table, byte_fc, tokens, ids, x, rn = ctx.saved_tensors
+        order = None
+        if ctx.order is not None:
+            order, ev = ctx.order
+            if ev is not None:
+                torch.cuda.current_stream(gx.device).wait_event(ev)
+            order.record_stream(torch.cuda.current_stream(gx.device))
+        g = byte_fc_mix_backward(gx, tokens, tok_table.detach(), byte_table.detach(), byte_fc.detach(), ids=ids,
+                                 out=None if x is None else x.detach(), row_rnorm=rn, token_order=order, **ctx.kw)
+        like = lambda k, p: g[k].to(p.dtype).reshape(p.shape)   # bf16 parameters get their gradient rounded once, from the fp32 sums
+        return like("tok_table", tok_table), like("byte_table", byte_table), like("byte_fc", byte_fc), None, None
+
+
+def byte_fc_mix(tokens: torch.Tensor, tok_table: torch.Tensor, byte_table: torch.Tensor, byte_fc: torch.Tensor, *, bpt: int,
+                ids: torch.Tensor | None = None, ttb: torch.Tensor | None = None, pull: str | None = None, pad_byte: int = 456,
+                eot_byte: int = 457, norm_out: bool = True, eps: float | None = None, return_ids: bool = False, composed: bool | None = None):
+    """The linear-on-bytes mixin of modded-nanogpt/runs/71051_*.py:225-229: ``x = norm(tok_table[tokens] + cat_k byte_table[ids[:, k]] @
+    byte_fc.T)`` with byte_fc (model_dim, bpt * byte_dim) in nn.Linear layout, no bias; float32 or bfloat16 throughout (bf16: fp32
+    arithmetic, rounded where the reference's bf16 run rounds).  tokens (B, T) or (T,); the byte ids are given as `ids` (B, T*bpt)
+    int64 or come from the token->byte table `ttb` (+ `pull` = "left" | "right" | None) inside the call.  `eps` None is the float32
+    epsilon for both dtypes, which is what F.rms_norm(eps=None) applies to bfloat16 rows as well; pass ``2.0 ** -7`` for
+    torch.finfo(bfloat16).eps.  One autograd node covers the two tables and byte_fc; `return_ids` returns a MixResult.  `composed`
+    (bfloat16 forward: the separate gather / product / row-pass kernels instead of the one gather-GEMM) overrides the import-time
+    default (MotByteFcMixDesc.flags)."""
+    kw = dict(bpt=bpt, ids=ids, ttb=ttb, pull=pull, pad_byte=pad_byte, eot_byte=eot_byte, norm_out=norm_out, eps=eps, return_ids=return_ids,
+              composed=composed)
+    if not (tok_table.dtype == byte_table.dtype == byte_fc.dtype):
+        raise TypeError(f"byte_fc_mix: tok_table {tok_table.dtype}, byte_table {byte_table.dtype} and byte_fc {byte_fc.dtype} must share one dtype")
+    capi.dtype_code(tok_table.dtype)
+    capi.require_device(tokens, tok_table, byte_table, byte_fc, ids, ttb)
+    if torch.is_grad_enabled() and any(p.requires_grad for p in (tok_table, byte_table, byte_fc)):
+        r = _ByteFcMixFn.apply(tok_table, byte_table, byte_fc, tokens, kw)
+        return MixResult(*r) if return_ids else r
+    return _byte_fc_mix_fwd(tokens, tok_table, byte_table, byte_fc, **kw)

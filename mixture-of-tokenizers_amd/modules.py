@@ -701,6 +701,38 @@ class ConcatFrontEnd(nn.Module):
                                _f32(self.embed_bytes.weight, "byte table"), mode="concat", bpt=self.bpt, **kw)
 
 
+class ByteFcFrontEnd(nn.Module):
+    """``x = norm(embed_tokens(tok) + F.linear(cat_k embed_bytes(byte_k), byte_fc))``: the linear-on-bytes mixin of
+    runs/71051_*.py:225-229 (parameter at 253, call site 312-314), one forward and one backward call of the library.  byte_fc is
+    (model_dim, bytes_per_token * byte_dim), initialised as the run's init_linear does (uniform, bound sqrt(3) * 0.5 / sqrt(K));
+    bytes_per_token * byte_dim need not equal model_dim.  Per-token byte semantics as in SumFrontEnd (SURVEY section 7, quirk iii).
+    The attribute names, and so the state-dict keys, are run 71051's."""
+
+    def __init__(self, token_vocab_size: int, byte_vocab_size: int, model_dim: int, byte_dim: int, bytes_per_token: int = 16,
+                 ttb=None, pad_byte: int = 456, eot_byte: int = 457):
+        super().__init__()
+        self.embed_tokens = nn.Embedding(token_vocab_size, model_dim)
+        self.embed_bytes = nn.Embedding(byte_vocab_size, byte_dim)
+        K = bytes_per_token * byte_dim
+        bound = (3 ** 0.5) * 0.5 * (K ** -0.5)
+        self.byte_fc = nn.Parameter(torch.empty(model_dim, K).uniform_(-bound, bound))
+        self.bpt, self.pad_byte, self.eot_byte, self.model_dim = bytes_per_token, pad_byte, eot_byte, model_dim
+        self.register_buffer("ttb", _table_of(ttb).clone() if ttb is not None else None, persistent=False)
+
+    def forward(self, token_inputs: Tensor, byte_inputs: Tensor | None = None) -> Tensor:
+        """token_inputs (T,) or (B,T); byte_inputs (.., T*bpt) per-token-ordered pulled ids, or None to
+        produce them in-kernel from the attached token->byte table."""
+        kw = dict(norm_out=True)
+        if byte_inputs is None:
+            if self.ttb is None:
+                raise ValueError("ByteFcFrontEnd: pass byte_inputs or construct the module with a token->byte table (ttb)")
+            kw.update(ttb=self.ttb, pull="left", pad_byte=self.pad_byte, eot_byte=self.eot_byte)
+        else:
+            kw.update(ids=byte_inputs.to(torch.int64).reshape(1 if token_inputs.ndim == 1 else token_inputs.shape[0], -1))
+        return F_mot.byte_fc_mix(token_inputs, _f32(self.embed_tokens.weight, "token table"), _f32(self.embed_bytes.weight, "byte table"),
+                                 _f32(self.byte_fc, "byte_fc"), bpt=self.bpt, **kw)
+
+
 # ------------------------------------------------------------------------------------------------
 # Llama character mixer (inference/inference.py): BASELINE config 5's front-end
 # ------------------------------------------------------------------------------------------------
