@@ -637,6 +637,84 @@ size_t mot_byte_fc_mix_bwd_workspace_bytes(const MotByteFcMixDesc *fwd /* host *
 int mot_byte_fc_mix_fwd(const MotByteFcMixDesc *desc /* host */, mot_stream_t stream);
 int mot_byte_fc_mix_bwd(const MotByteFcMixDesc *fwd /* host */, const MotByteFcMixGrads *grads /* host */, mot_stream_t stream);
 
+/*
+ * Bytes-only front-end and byte value embeddings, forward: replaces, in ONE launch for up to four tables indexed by one id stream,
+ *   x = x0 = norm(reshape_bytes(embed_bytes(byte_inputs)))        modded-nanogpt/runs/5_bytes-in_bytes-valemb.py:225-232, 314 (runs 4, 6)
+ *   ve = [reshape_bytes(value_embed(byte_inputs)) for value_embed in self.value_embeds_bytes]           :248, 305 (runs 2, 8)
+ * There is no token row.  For every used slot j (n_out of them) and token n of row-major (B, T), with model_dim = bpt * byte_dim:
+ *   out_j[n, k*byte_dim + c] = s_j[n] * table_j[ids[n, k], c],   s_j[n] = rsqrt(mean over the row of cat^2 + eps) if norm_j else 1
+ * fp32 arithmetic, one rounding at the store for bf16; without a norm the row is a copy of the table rows, bit for bit.
+ * The ids are given (MOT_IDS_GIVEN, `ids`; `tokens` may be NULL) or come from the token->byte table (MOT_IDS_FROM_TTB:
+ * tokens_to_bytes, then pull_dir), with the int64 id outputs, counters and status word of MotEmbedMixDesc; an id outside a slot's
+ * table reads that table's row 0 and raises MOT_STATUS_BYTE_OOR.
+ * eps <= 0 means FLT_EPSILON for BOTH dtypes, as in MotByteFcMixDesc.
+ * byte_dim a multiple of the 16-byte vector (4 fp32 / 8 bf16 elements), model_dim at most 2048, n_out in 1..4; every slot's dtype
+ * equals the descriptor's.  The forward needs no workspace.
+ */
+#define MOT_BYTE_CAT_MAX_OUT 4
+
+typedef struct MotByteCatSlot {
+    const void *table; /* [rows, byte_dim] */
+    int64_t rows;
+    void *out;         /* [B, T, bpt*byte_dim]; ignored by the backward */
+    int32_t norm;      /* 1: the row is rms-normalised over its model_dim columns */
+    int32_t dtype;     /* MotDType of table and out: must equal MotByteCatDesc.dtype */
+} MotByteCatSlot;
+
+typedef struct MotByteCatDesc {
+    uint32_t struct_size;   /* sizeof(MotByteCatDesc), checked */
+    int32_t dtype;          /* MotDType of every table / out / grad_out */
+    int64_t n_rows;         /* B */
+    int64_t tokens_per_row; /* T */
+    int32_t bpt;            /* byte slots per token */
+    int32_t byte_dim;
+    int32_t n_out;          /* used slots: 1 .. MOT_BYTE_CAT_MAX_OUT */
+    int32_t id_source;      /* MOT_IDS_FROM_TTB | MOT_IDS_GIVEN */
+    const int32_t *tokens;  /* [B, T]               (FROM_TTB) */
+    const void *ttb;        /* [ttb_rows, bpt]      (FROM_TTB) */
+    int64_t ttb_rows;
+    int32_t ttb_elem_bytes; /* 2 | 4                (FROM_TTB) */
+    int32_t pull_dir;       /* MotPullDir           (FROM_TTB) */
+    int32_t pad_byte, eot_byte;
+    const int64_t *ids;     /* [B, T*bpt]           (GIVEN) */
+    float eps;              /* <= 0 -> FLT_EPSILON, both dtypes */
+    uint32_t reserved0;     /* must be 0 */
+    MotByteCatSlot slot[MOT_BYTE_CAT_MAX_OUT];
+    int64_t *out_ids_padded; /* optional [B, T*bpt] (FROM_TTB) */
+    int64_t *out_ids_pulled; /* optional [B, T*bpt] (FROM_TTB) */
+    int64_t *counters;      /* optional int64[4], as MotEmbedMixDesc.counters */
+    uint32_t *status;       /* optional device word, see MOT_STATUS_* */
+    void *workspace;        /* backward only: >= mot_byte_cat_bwd_workspace_bytes */
+    size_t workspace_bytes;
+} MotByteCatDesc;
+
+/*
+ * Backward: `fwd` is the forward's descriptor with id_source == MOT_IDS_GIVEN (the ids the forward used or wrote); `out` and the id
+ * outputs are ignored.  `counters`, when non-null, is a measurement aid here: int64[2], incremented by the number of non-zero
+ * gradient terms added and by how many of them took the exact global path instead of the LDS sums.  Per used slot j whose grad_out is non-null (a null grad_out skips the slot):
+ *   dcat = g                                  without the norm
+ *   dcat = s (g - x (g.x) / model_dim)         with it, x = s cat gathered again and s recomputed
+ *   d_table[ids[n, k], :] += dcat[n, k*byte_dim : (k+1)*byte_dim]
+ * d_table is FP32 for both dtypes and ACCUMULATED into (+=).  Sums are privatised per workgroup in LDS as 64-bit fixed point and
+ * flushed once per workgroup with float atomics: results depend on the order of those flushes in the last bits.
+ */
+typedef struct MotByteCatGradSlot {
+    const void *grad_out; /* [B, T, bpt*byte_dim] in dtype, or NULL */
+    void *d_table;        /* [rows, byte_dim] fp32 */
+} MotByteCatGradSlot;
+
+typedef struct MotByteCatGrads {
+    uint32_t struct_size; /* sizeof(MotByteCatGrads) */
+    uint32_t reserved;
+    MotByteCatGradSlot slot[MOT_BYTE_CAT_MAX_OUT];
+} MotByteCatGrads;
+
+size_t mot_byte_cat_desc_size(void);
+size_t mot_byte_cat_workspace_bytes(const MotByteCatDesc *desc /* host */);     /* 0: the forward needs none (and for a descriptor the call would refuse) */
+size_t mot_byte_cat_bwd_workspace_bytes(const MotByteCatDesc *fwd /* host */);  /* 0 for a descriptor the call would refuse */
+int mot_byte_cat_fwd(const MotByteCatDesc *desc /* host */, mot_stream_t stream);
+int mot_byte_cat_bwd(const MotByteCatDesc *fwd /* host */, const MotByteCatGrads *grads /* host */, mot_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

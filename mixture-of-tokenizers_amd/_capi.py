@@ -36,6 +36,7 @@ HEAD_COPY, HEAD_SPLIT = 0, 1
 HEAD_VOCAB = 512
 FLAG_LINEAR_ONE_LAUNCH, FLAG_MEAN_GENERIC, FLAG_BWD_DU_FP32, FLAG_LINEAR_COMPOSED = 1, 2, 4, 8
 BYTE_FC_COMPOSED = 1
+BYTE_CAT_MAX_OUT = 4
 HEADS_AS_VIEWED, HEADS_PER_TOKEN = 0, 1
 
 
@@ -58,6 +59,7 @@ EXPORTS = (
     "mot_byte_self_attn_fwd", "mot_byte_self_attn_bwd",
     "mot_byte_fc_mix_desc_size", "mot_byte_fc_mix_workspace_bytes", "mot_byte_fc_mix_bwd_workspace_bytes",
     "mot_byte_fc_mix_fwd", "mot_byte_fc_mix_bwd",
+    "mot_byte_cat_desc_size", "mot_byte_cat_workspace_bytes", "mot_byte_cat_bwd_workspace_bytes", "mot_byte_cat_fwd", "mot_byte_cat_bwd",
 )
 SWA_NO_RESIDUAL, SWA_ONE_RESIDUAL, SWA_TWO_RESIDUAL = 0, 1, 2
 
@@ -183,6 +185,34 @@ class MotByteFcMixGrads(C.Structure):
     ]
 
 
+class MotByteCatSlot(C.Structure):
+    """Mirror of struct MotByteCatSlot (include/mot.h)."""
+    _fields_ = [("table", C.c_void_p), ("rows", C.c_int64), ("out", C.c_void_p), ("norm", C.c_int32), ("dtype", C.c_int32)]
+
+
+class MotByteCatDesc(C.Structure):
+    """Mirror of struct MotByteCatDesc (include/mot.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("dtype", C.c_int32), ("n_rows", C.c_int64), ("tokens_per_row", C.c_int64),
+        ("bpt", C.c_int32), ("byte_dim", C.c_int32), ("n_out", C.c_int32), ("id_source", C.c_int32),
+        ("tokens", C.c_void_p), ("ttb", C.c_void_p), ("ttb_rows", C.c_int64), ("ttb_elem_bytes", C.c_int32), ("pull_dir", C.c_int32),
+        ("pad_byte", C.c_int32), ("eot_byte", C.c_int32), ("ids", C.c_void_p), ("eps", C.c_float), ("reserved0", C.c_uint32),
+        ("slot", MotByteCatSlot * BYTE_CAT_MAX_OUT),
+        ("out_ids_padded", C.c_void_p), ("out_ids_pulled", C.c_void_p), ("counters", C.c_void_p), ("status", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
+class MotByteCatGradSlot(C.Structure):
+    """Mirror of struct MotByteCatGradSlot (include/mot.h)."""
+    _fields_ = [("grad_out", C.c_void_p), ("d_table", C.c_void_p)]
+
+
+class MotByteCatGrads(C.Structure):
+    """Mirror of struct MotByteCatGrads (include/mot.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("slot", MotByteCatGradSlot * BYTE_CAT_MAX_OUT)]
+
+
 def _load() -> C.CDLL:
     if not LIB_PATH.exists():
         raise ImportError(
@@ -245,6 +275,14 @@ def _load() -> C.CDLL:
     lib.mot_byte_fc_mix_fwd.restype = C.c_int
     lib.mot_byte_fc_mix_bwd.argtypes = [C.POINTER(MotByteFcMixDesc), C.POINTER(MotByteFcMixGrads), vp]
     lib.mot_byte_fc_mix_bwd.restype = C.c_int
+    lib.mot_byte_cat_desc_size.restype = C.c_size_t
+    for name in ("mot_byte_cat_workspace_bytes", "mot_byte_cat_bwd_workspace_bytes"):
+        getattr(lib, name).restype = C.c_size_t
+        getattr(lib, name).argtypes = [C.POINTER(MotByteCatDesc)]
+    lib.mot_byte_cat_fwd.argtypes = [C.POINTER(MotByteCatDesc), vp]
+    lib.mot_byte_cat_fwd.restype = C.c_int
+    lib.mot_byte_cat_bwd.argtypes = [C.POINTER(MotByteCatDesc), C.POINTER(MotByteCatGrads), vp]
+    lib.mot_byte_cat_bwd.restype = C.c_int
     for name in ("mot_tokens_to_bytes", "mot_pull_bytes", "mot_create_batch", "mot_char_matrix", "mot_gather_rows", "mot_embed_mix_fwd",
                  "mot_embed_mix_bwd"):
         getattr(lib, name).restype = C.c_int
@@ -262,6 +300,8 @@ def _load() -> C.CDLL:
         raise ImportError("MotByteSelfAttnDesc layout mismatch between include/mot.h and _capi.py")
     if lib.mot_byte_fc_mix_desc_size() != C.sizeof(MotByteFcMixDesc):
         raise ImportError("MotByteFcMixDesc layout mismatch between include/mot.h and _capi.py")
+    if lib.mot_byte_cat_desc_size() != C.sizeof(MotByteCatDesc):
+        raise ImportError("MotByteCatDesc layout mismatch between include/mot.h and _capi.py")
     return lib
 
 

@@ -446,4 +446,22 @@ int mot_byte_fc_mix_bwd(const MotByteFcMixDesc *desc, const MotByteFcMixGrads *g
     return launch_byte_fc_mix_bwd(*desc, *grads, (hipStream_t)stream);
 }
 
+size_t mot_byte_cat_desc_size(void) { return sizeof(MotByteCatDesc); }
+
+size_t mot_byte_cat_workspace_bytes(const MotByteCatDesc *desc) { return byte_cat_workspace_bytes(desc); }
+
+size_t mot_byte_cat_bwd_workspace_bytes(const MotByteCatDesc *desc) { return byte_cat_bwd_workspace_bytes(desc); }
+
+int mot_byte_cat_fwd(const MotByteCatDesc *desc, mot_stream_t stream) {
+    if (int rc = byte_cat_check(desc, nullptr, false)) return rc;
+    if (desc->n_rows == 0 || desc->tokens_per_row == 0) return MOT_OK;
+    return launch_byte_cat_fwd(*desc, (hipStream_t)stream);
+}
+
+int mot_byte_cat_bwd(const MotByteCatDesc *desc, const MotByteCatGrads *grads, mot_stream_t stream) {
+    if (int rc = byte_cat_check(desc, grads, true)) return rc;
+    if (desc->n_rows == 0 || desc->tokens_per_row == 0) return MOT_OK;
+    return launch_byte_cat_bwd(*desc, *grads, (hipStream_t)stream);
+}
+
 }  // extern "C"

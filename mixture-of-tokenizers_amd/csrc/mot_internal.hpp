@@ -119,5 +119,11 @@ size_t byte_fc_mix_workspace_bytes(const MotByteFcMixDesc *d);       // 0 for a 
 size_t byte_fc_mix_bwd_workspace_bytes(const MotByteFcMixDesc *d);   // likewise
 int launch_byte_fc_mix_fwd(const MotByteFcMixDesc &d, hipStream_t stream);
 int launch_byte_fc_mix_bwd(const MotByteFcMixDesc &d, const MotByteFcMixGrads &g, hipStream_t stream);
+// the bytes-only front-end and the byte value embeddings (mot_bytecat.hip): validation before any HIP call (g: backward only), then the launches
+int byte_cat_check(const MotByteCatDesc *d, const MotByteCatGrads *g, bool backward);
+size_t byte_cat_workspace_bytes(const MotByteCatDesc *d);       // 0: the forward needs none
+size_t byte_cat_bwd_workspace_bytes(const MotByteCatDesc *d);   // 0 for a descriptor the call would refuse
+int launch_byte_cat_fwd(const MotByteCatDesc &d, hipStream_t stream);
+int launch_byte_cat_bwd(const MotByteCatDesc &d, const MotByteCatGrads &g, hipStream_t stream);
 
 }  // namespace mot

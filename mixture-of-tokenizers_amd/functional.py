@@ -1215,3 +1215,207 @@ def byte_fc_mix(tokens: torch.Tensor, tok_table: torch.Tensor, byte_table: torch
         r = _ByteFcMixFn.apply(tok_table, byte_table, byte_fc, tokens, kw)
         return MixResult(*r) if return_ids else r
     return _byte_fc_mix_fwd(tokens, tok_table, byte_table, byte_fc, **kw)
+
+
+# ------------------------------------------------------------------------------------------------
+# bytes-only front-end and byte value embeddings (modded-nanogpt/runs/5_bytes-in_bytes-valemb.py:225-232, 248, 305, 314):
+# out_j = norm_j?(cat_k table_j[id_k]) for up to four tables over one id stream, no token row
+# ------------------------------------------------------------------------------------------------
+def _byte_cat_desc(tables, norm, bpt, eps, tokens, ids, what):
+    """The descriptor's problem part, checked: 1..4 contiguous (rows, byte_dim) tables of one dtype, a bool per table, and the
+    batch shape (B, T) from the tokens or, without them, from the ids."""
+    tables = list(tables)
+    norm = [bool(x) for x in norm]
+    if not 1 <= len(tables) <= capi.BYTE_CAT_MAX_OUT:
+        raise ValueError(f"{what}: {len(tables)} tables, 1..{capi.BYTE_CAT_MAX_OUT} are built")
+    if len(norm) != len(tables):
+        raise ValueError(f"{what}: norm needs one bool per table ({len(tables)}), got {len(norm)}")
+    dt = tables[0].dtype
+    tabs = [_table(t, f"{what}: table {j}") for j, t in enumerate(tables)]
+    for j, t in enumerate(tabs):
+        if t.dtype != dt:
+            raise TypeError(f"{what}: table {j} is {t.dtype} but table 0 is {dt}: all tables share one dtype")
+        if t.ndim != 2 or t.shape[1] != tabs[0].shape[1]:
+            raise ValueError(f"{what}: table {j} must be (rows, byte_dim = {tabs[0].shape[1]}), got {tuple(t.shape)}")
+    bpt = int(bpt)
+    keep = list(tabs)
+    tok = None
+    if tokens is not None:
+        tok = tokens[None] if tokens.ndim == 1 else tokens
+        if tok.ndim != 2:
+            raise ValueError("tokens must be (B, T) or (T,)")
+        tok = tok.to(torch.int32) if tok.dtype != torch.int32 else tok
+        tok = tok if tok.is_contiguous() else tok.contiguous()
+        B, T = tok.shape
+        keep.append(tok)
+    else:
+        if ids is None:
+            raise ValueError(f"{what}: pass tokens (with ttb) or ids")
+        i2 = ids[None] if ids.ndim == 1 else ids.reshape(ids.shape[0], -1)
+        if i2.shape[1] % bpt:
+            raise AssertionError(f"{what}: {i2.shape[1]} byte ids per row are not a multiple of bpt {bpt}")
+        B, T = i2.shape[0], i2.shape[1] // bpt
+    d = capi.MotByteCatDesc()
+    d.struct_size = C.sizeof(capi.MotByteCatDesc)
+    d.dtype = capi.dtype_code(dt)
+    d.n_rows, d.tokens_per_row, d.bpt, d.byte_dim, d.n_out = B, T, bpt, tabs[0].shape[1], len(tabs)
+    d.tokens = capi.ptr(tok)
+    d.eps = float(eps or 0.0)
+    for j, t in enumerate(tabs):
+        d.slot[j].table, d.slot[j].rows, d.slot[j].norm, d.slot[j].dtype = capi.ptr(t), t.shape[0], int(norm[j]), d.dtype
+    return d, tabs, keep, (B, T)
+
+
+@torch.compiler.disable
+def _byte_cat_fwd(tables, *, bpt, norm, tokens=None, ids=None, ttb=None, pull=None, pad_byte=456, eot_byte=457, eps=None, return_ids=False,
+                  counters=None):
+    dev = capi.require_device(*tables, tokens, ids, ttb)
+    d, tabs, keep, (B, T) = _byte_cat_desc(tables, norm, bpt, eps, tokens, None if ttb is not None else ids, "byte_cat")
+    ids_padded = ids_pulled = None
+    if ttb is not None:
+        if tokens is None:
+            raise ValueError("byte_cat: ids from the token->byte table need the tokens")
+        tab = _int_table(ttb, "byte_cat")
+        if tab.shape[1] != bpt:
+            raise ValueError(f"ttb has {tab.shape[1]} slots per token, bpt={bpt}")
+        keep.append(tab)
+        d.id_source, d.pull_dir = capi.IDS_FROM_TTB, _PULLS[pull]
+        d.ttb, d.ttb_rows, d.ttb_elem_bytes = capi.ptr(tab), tab.shape[0], tab.element_size()
+        used_only = return_ids == "used"   # the autograd node: only the tensor the gathers index (8 * bpt bytes per token, written once)
+        if return_ids and not (used_only and d.pull_dir != capi.PULL_NONE):
+            ids_padded = torch.empty((B, T * bpt), dtype=torch.int64, device=dev)
+            d.out_ids_padded = capi.ptr(ids_padded)
+        if return_ids and not (used_only and d.pull_dir == capi.PULL_NONE):
+            ids_pulled = torch.empty((B, T * bpt), dtype=torch.int64, device=dev)
+            d.out_ids_pulled = capi.ptr(ids_pulled)
+    else:
+        if ids is None:
+            raise ValueError("either ttb or ids must be given")
+        ia = _contig(ids, torch.int64, "ids")
+        if ia.numel() != B * T * bpt:
+            raise ValueError("byte ids must hold bytes_per_token ids per token")
+        keep.append(ia)
+        d.id_source, d.ids = capi.IDS_GIVEN, capi.ptr(ia)
+    d.pad_byte, d.eot_byte = int(pad_byte), int(eot_byte)
+    outs = tuple(torch.empty((B, T, bpt * d.byte_dim), dtype=tabs[0].dtype, device=dev) for _ in tabs)
+    if B * T == 0:   # an empty batch: nothing to launch
+        return outs, ids_padded, ids_pulled
+    for j, o in enumerate(outs):
+        d.slot[j].out = capi.ptr(o)
+    if counters is not None:
+        if counters.dtype != torch.int64 or counters.numel() < 4 or counters.device != dev:
+            raise ValueError("counters must be an int64[4] tensor on the inputs' device")
+        d.counters = capi.ptr(counters)
+    d.status = capi.ptr(capi.status_word(dev))
+    capi.check(capi.lib.mot_byte_cat_fwd(C.byref(d), capi.stream_of(dev)))
+    capi.after_call(dev)
+    return outs, ids_padded, ids_pulled
+
+
+@torch.compiler.disable
+def byte_cat_backward(grad_outs, tables, *, bpt, norm, ids, eps=None, into=None, counters=None) -> list:
+    """One call of mot_byte_cat_bwd.  `grad_outs` holds one upstream gradient (B, T, bpt*byte_dim) or None per table; a table
+    whose entry is None is skipped and gets None back.  Returns the dense fp32 table gradients -- fp32 also for bfloat16 tables
+    (the autograd node rounds once); `into` (a list, fp32 tensors or None) accumulates into existing buffers.  Nothing of the
+    forward is needed but the ids it used.  `counters` (int64[2] on the device, a measurement aid) is incremented by the number of
+    non-zero gradient terms and by how many of them took the exact global path instead of the LDS sums."""
+    grad_outs = list(grad_outs)
+    dev = capi.require_device(*tables, ids, *[g for g in grad_outs if g is not None])
+    d, tabs, keep, (B, T) = _byte_cat_desc(tables, norm, bpt, eps, None, ids, "byte_cat_backward")
+    if len(grad_outs) != len(tabs):
+        raise ValueError(f"byte_cat_backward: {len(grad_outs)} gradients for {len(tabs)} tables")
+    ia = _contig(ids, torch.int64, "ids")
+    keep.append(ia)
+    d.id_source, d.ids = capi.IDS_GIVEN, capi.ptr(ia)
+    gr = capi.MotByteCatGrads()
+    gr.struct_size = C.sizeof(capi.MotByteCatGrads)
+    into = list(into) if into is not None else [None] * len(tabs)
+    res = []
+    for j, (g, t) in enumerate(zip(grad_outs, tabs)):
+        if g is None:
+            res.append(None)
+            continue
+        gc = _contig(g, t.dtype, f"grad_outs[{j}]")
+        if gc.numel() != B * T * bpt * d.byte_dim:
+            raise ValueError(f"grad_outs[{j}] must be (B, T, bpt*byte_dim)")
+        keep.append(gc)
+        acc = into[j] if into[j] is not None else torch.zeros(t.shape, dtype=torch.float32, device=dev)
+        if acc.dtype != torch.float32 or acc.shape != t.shape or not acc.is_contiguous():
+            raise ValueError(f"into[{j}] must be a contiguous float32 tensor of the table's shape")
+        res.append(acc)
+        gr.slot[j].grad_out, gr.slot[j].d_table = capi.ptr(gc), capi.ptr(acc)
+    if B * T == 0 or all(g is None for g in grad_outs):   # an empty batch adds nothing
+        return res
+    if counters is not None:
+        if counters.dtype != torch.int64 or counters.numel() < 2 or counters.device != dev:
+            raise ValueError("counters must be an int64[2] tensor on the inputs' device")
+        d.counters = capi.ptr(counters)
+    d.status = capi.ptr(capi.status_word(dev))
+    ws = _workspace(dev, capi.lib.mot_byte_cat_bwd_workspace_bytes(C.byref(d)))
+    if ws is not None:
+        d.workspace, d.workspace_bytes = capi.ptr(ws), ws.numel()
+    capi.check(capi.lib.mot_byte_cat_bwd(C.byref(d), C.byref(gr), capi.stream_of(dev)))
+    capi.after_call(dev)
+    return res
+
+
+class _ByteCatFn(torch.autograd.Function):
+    """Autograd node of byte_cat: one mot_byte_cat_fwd call forward, one mot_byte_cat_bwd call backward for all tables.  Saved: the
+    tables and the int64 byte ids (given, or written once by the forward); every row is gathered again."""
+
+    @staticmethod
+    def forward(ctx, kw, *tables):
+        kw = dict(kw)
+        user_return_ids = kw.pop("return_ids", False)
+        from_ttb = kw.get("ttb") is not None
+        outs, ids_padded, ids_pulled = _byte_cat_fwd([t.detach() for t in tables], return_ids=True if user_return_ids else ("used" if from_ttb else False),
+                                                     **kw)
+        ids = kw.get("ids")
+        if from_ttb:
+            ids = ids_pulled if kw.get("pull") not in (None, "none") else ids_padded
+        ctx.save_for_backward(ids, *tables)
+        ctx.set_materialize_grads(False)   # an output nothing depends on arrives as None and its table is skipped
+        ctx.kw = dict(bpt=kw["bpt"], norm=tuple(kw["norm"]), eps=kw.get("eps"))
+        ctx.n_out = len(tables)
+        if user_return_ids and from_ttb:
+            ctx.mark_non_differentiable(ids_padded, ids_pulled)
+            return (*outs, ids_padded, ids_pulled)
+        return outs
+
+    @staticmethod
+    def backward(ctx, *grads):
+        ids, *tables = ctx.saved_tensors
+        gs = [g if ctx.needs_input_grad[1 + j] else None for j, g in enumerate(grads[:ctx.n_out])]
+        if all(g is None for g in gs):
+            return (None,) * (1 + ctx.n_out)
+        res = byte_cat_backward(gs, [t.detach() for t in tables], ids=ids, **ctx.kw)
+        # bf16 parameters get their gradient rounded once, from the fp32 sums
+        return (None, *[None if r is None else r.to(t.dtype) for r, t in zip(res, tables)])
+
+
+def byte_cat(tables, *, bpt: int, norm, tokens: torch.Tensor | None = None, ids: torch.Tensor | None = None, ttb: torch.Tensor | None = None,
+             pull: str | None = None, pad_byte: int = 456, eot_byte: int = 457, eps: float | None = None, return_ids: bool = False):
+    """The bytes-only front-end and the byte value embeddings of modded-nanogpt/runs/5_bytes-in_bytes-valemb.py:225-232, 248, 305,
+    314: for each of the 1..4 `tables` (rows_j, byte_dim), all of one dtype (float32 or bfloat16), ``out_j = table_j[ids].reshape(B,
+    T, bpt * byte_dim)``, rms-normalised over the last dimension where ``norm[j]`` is set (fp32 arithmetic, one rounding at the
+    store; without the norm a bit-exact copy).  One launch serves every table.  The byte ids are given as `ids` (B, T*bpt) int64,
+    or come from `tokens` (B, T) and the token->byte table `ttb` (+ `pull` = "left" | "right" | None) inside the call.  `eps` None
+    is the float32 epsilon for both dtypes, which is what F.rms_norm(eps=None) applies to bfloat16 rows as well.  Returns a tuple
+    of len(tables) tensors (B, T, bpt*byte_dim); with `return_ids` (ids from the table) the tuple, ids_padded and ids_pulled.  One
+    autograd node covers all tables."""
+    tables = list(tables)
+    norm = tuple(bool(x) for x in norm)
+    kw = dict(bpt=int(bpt), norm=norm, tokens=tokens, ids=ids, ttb=ttb, pull=pull, pad_byte=pad_byte, eot_byte=eot_byte, eps=eps,
+              return_ids=return_ids)
+    for j, t in enumerate(tables):
+        if t.dtype != tables[0].dtype:
+            raise TypeError(f"byte_cat: table {j} is {t.dtype} but table 0 is {tables[0].dtype}: all tables share one dtype")
+    if tables:
+        capi.dtype_code(tables[0].dtype)
+    capi.require_device(*tables, tokens, ids, ttb)
+    n = len(tables)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tables):
+        r = _ByteCatFn.apply(kw, *tables)
+        return (tuple(r[:n]), r[n], r[n + 1]) if return_ids and ttb is not None else tuple(r[:n])
+    outs, ids_padded, ids_pulled = _byte_cat_fwd(tables, **kw)
+    return (outs, ids_padded, ids_pulled) if return_ids and ttb is not None else outs

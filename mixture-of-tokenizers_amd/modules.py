@@ -733,6 +733,55 @@ class ByteFcFrontEnd(nn.Module):
                                  _f32(self.byte_fc, "byte_fc"), bpt=self.bpt, **kw)
 
 
+class BytesFrontEnd(nn.Module):
+    """The bytes-only front-end and the byte value embeddings of runs/5_bytes-in_bytes-valemb.py, one forward and one backward
+    call of the library for all of them: ``x0 = norm(reshape_bytes(embed_bytes(byte_inputs)))`` (lines 225-232, 314; runs 4 and 6
+    have only this) and ``ve = [reshape_bytes(value_embed(byte_inputs)) for value_embed in value_embeds_bytes]`` (248, 305; runs 2
+    and 8 have only these, beside their own front-end).  model_dim = bytes_per_token * byte_dim; there is no token table.  The
+    runs allocate their value tables with token_vocab_size rows although only byte ids index them: `value_rows` keeps such a
+    checkpoint loadable, the library sees the leading byte_vocab_size rows as a view and autograd pads the gradient with zeros.
+    The attribute names, and so the state-dict keys, are the runs'."""
+
+    def __init__(self, byte_vocab_size: int, byte_dim: int, bytes_per_token: int = 16, n_value_embeds: int = 0, value_rows: int | None = None,
+                 ttb=None, pad_byte: int = 456, eot_byte: int = 457):
+        super().__init__()
+        if not 0 <= n_value_embeds <= 3:
+            raise ValueError("BytesFrontEnd: n_value_embeds is 0 (runs 4, 6) up to 3 (runs 2, 5, 8): one call serves four tables")
+        value_rows = byte_vocab_size if value_rows is None else value_rows
+        if value_rows < byte_vocab_size:
+            raise ValueError(f"BytesFrontEnd: value_rows {value_rows} < byte_vocab_size {byte_vocab_size}")
+        self.embed_bytes = nn.Embedding(byte_vocab_size, byte_dim)
+        if n_value_embeds:
+            self.value_embeds_bytes = nn.ModuleList([nn.Embedding(value_rows, byte_dim) for _ in range(n_value_embeds)])
+        self.n_value_embeds, self.byte_vocab_size = n_value_embeds, byte_vocab_size
+        self.bpt, self.pad_byte, self.eot_byte, self.model_dim = bytes_per_token, pad_byte, eot_byte, bytes_per_token * byte_dim
+        self.register_buffer("ttb", _table_of(ttb).clone() if ttb is not None else None, persistent=False)
+
+    def forward(self, token_inputs: Tensor | None = None, byte_inputs: Tensor | None = None, x0: bool = True):
+        """byte_inputs (.., T*bpt) per-token-ordered byte ids, or None to produce them in-kernel from token_inputs (T,) or (B, T)
+        and the attached token->byte table.  Returns (x0, [ve_0, ve_1, ve_2]): x0 is None with ``x0=False``, the list is empty
+        with n_value_embeds = 0."""
+        tables, norm = [], []
+        if x0:
+            tables.append(_f32(self.embed_bytes.weight, "byte table"))
+            norm.append(True)
+        if self.n_value_embeds:
+            tables += [_f32(e.weight, "value table")[:self.byte_vocab_size] for e in self.value_embeds_bytes]
+            norm += [False] * self.n_value_embeds
+        if not tables:
+            raise ValueError("BytesFrontEnd: x0=False on a module without value embeddings produces nothing")
+        kw = {}
+        if byte_inputs is None:
+            if self.ttb is None or token_inputs is None:
+                raise ValueError("BytesFrontEnd: pass byte_inputs, or token_inputs to a module built with a token->byte table (ttb)")
+            kw.update(tokens=token_inputs, ttb=self.ttb, pull="left", pad_byte=self.pad_byte, eot_byte=self.eot_byte)
+        else:
+            rows = 1 if byte_inputs.ndim == 1 else byte_inputs.shape[0]
+            kw.update(ids=byte_inputs.to(torch.int64).reshape(rows, -1))
+        outs = list(F_mot.byte_cat(tables, bpt=self.bpt, norm=norm, **kw))
+        return (outs.pop(0) if x0 else None), outs
+
+
 # ------------------------------------------------------------------------------------------------
 # Llama character mixer (inference/inference.py): BASELINE config 5's front-end
 # ------------------------------------------------------------------------------------------------
