@@ -715,6 +715,59 @@ size_t mot_byte_cat_bwd_workspace_bytes(const MotByteCatDesc *fwd /* host */);  
 int mot_byte_cat_fwd(const MotByteCatDesc *desc /* host */, mot_stream_t stream);
 int mot_byte_cat_bwd(const MotByteCatDesc *fwd /* host */, const MotByteCatGrads *grads /* host */, mot_stream_t stream);
 
+/*
+ * Token value embeddings: one to four tables of equal shape and dtype indexed by ONE token stream, which replaces
+ *   self.value_embeds = nn.ModuleList([nn.Embedding(vocab_size, model_dim) for _ in range(3)])    scaled-pre-train/train_gpt.py:566
+ *   ve = [value_embed(toks_in) for value_embed in self.value_embeds]                              scaled-pre-train/train_gpt.py:600
+ * (modded-nanogpt/runs/71_*_toks-valemb.py:247 and :303, and every other *_toks-valemb.py run), forward and backward.
+ * Forward, ONE launch for all tables: outs[j][n, :] = tables[j][tokens[n], :], a copy bit for bit; a position's id is read once;
+ * no workspace.  An id outside [0, tok_rows) raises MOT_STATUS_TOKEN_OOR and reads row 0, as everywhere in the library.
+ * dim a multiple of the 16-byte vector (4 fp32 / 8 bf16 elements) and at most 2048, tok_rows < 2^21 - 1 (the token order's limit),
+ * n_tables in 1..MOT_VALUE_EMBEDS_MAX_TABLES: anything else is refused with MOT_EUNSUPPORTED before any launch.  Null pointers are
+ * MOT_EINVAL; n_tokens == 0 is a no-op that returns MOT_OK.  Both calls are asynchronous on `stream` and never synchronise.
+ */
+#define MOT_VALUE_EMBEDS_MAX_TABLES 4
+
+typedef struct MotValueEmbedsDesc {
+    uint32_t struct_size;   /* sizeof(MotValueEmbedsDesc), checked */
+    int32_t dtype;          /* MOT_F32 | MOT_BF16: every table, out, grad_out and d_table */
+    int64_t n_tokens;       /* positions of the (flattened) token tensor, < 2^31 */
+    const int32_t *tokens;  /* [n_tokens] */
+    int64_t tok_rows;       /* rows of every table */
+    int32_t dim;            /* columns of every table */
+    int32_t n_tables;       /* 1 .. MOT_VALUE_EMBEDS_MAX_TABLES */
+    const void *tables[MOT_VALUE_EMBEDS_MAX_TABLES]; /* [tok_rows, dim] each; the backward does not read them (may be NULL there) */
+    void *outs[MOT_VALUE_EMBEDS_MAX_TABLES];         /* [n_tokens, dim] each; ignored by the backward */
+    uint32_t *status;       /* optional device word, see MOT_STATUS_* */
+    void *workspace;        /* backward only: >= mot_value_embeds_bwd_workspace_bytes, 16-byte aligned */
+    size_t workspace_bytes;
+} MotValueEmbedsDesc;
+
+/*
+ * Backward: the dense gradient of every table j whose grad_outs[j] is non-null (a null entry skips the table: its d_tables[j] is
+ * not touched), in ONE call over one token order -- the caller's `token_order` (what mot_token_order wrote for the same tokens and
+ * tok_rows) or one made inside the workspace:
+ *   d_tables[j][r, :] = round_to_dtype(fp32 sum over the positions n with tokens[n] == r of grad_outs[j][n, :]),  +0 where r is absent.
+ * Every element of every requested d_tables[j] is WRITTEN exactly once, in the tables' dtype, with plain stores: the caller zeroes
+ * nothing (uninitialised memory is fine) and nothing is accumulated.  No atomic touches a gradient element.  The positions of an id
+ * are summed in ascending position order, cut at fixed 64-position boundaries of the sorted stream; the pieces of a group that
+ * crosses a boundary go to the workspace in fp32 and are added in ascending order by four waves, wave 0's share first.  The result
+ * is the same bits on every run, with or without `token_order`.  All zeroing is done by kernels, so forward + backward capture
+ * into a hipGraph.
+ */
+typedef struct MotValueEmbedsGrads {
+    uint32_t struct_size; /* sizeof(MotValueEmbedsGrads) */
+    uint32_t reserved;
+    const void *grad_outs[MOT_VALUE_EMBEDS_MAX_TABLES]; /* [n_tokens, dim] in dtype, or NULL */
+    void *d_tables[MOT_VALUE_EMBEDS_MAX_TABLES];        /* [tok_rows, dim] in dtype */
+    const int32_t *token_order; /* optional, as MotEmbedMixGrads.token_order */
+} MotValueEmbedsGrads;
+
+size_t mot_value_embeds_desc_size(void);
+size_t mot_value_embeds_bwd_workspace_bytes(const MotValueEmbedsDesc *fwd /* host */);   /* 0 for a descriptor the call would refuse */
+int mot_value_embeds_fwd(const MotValueEmbedsDesc *desc /* host */, mot_stream_t stream);
+int mot_value_embeds_bwd(const MotValueEmbedsDesc *fwd /* host */, const MotValueEmbedsGrads *grads /* host */, mot_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,7 @@ HEAD_VOCAB = 512
 FLAG_LINEAR_ONE_LAUNCH, FLAG_MEAN_GENERIC, FLAG_BWD_DU_FP32, FLAG_LINEAR_COMPOSED = 1, 2, 4, 8
 BYTE_FC_COMPOSED = 1
 BYTE_CAT_MAX_OUT = 4
+VALUE_EMBEDS_MAX_TABLES = 4
 HEADS_AS_VIEWED, HEADS_PER_TOKEN = 0, 1
 
 
@@ -60,6 +61,7 @@ EXPORTS = (
     "mot_byte_fc_mix_desc_size", "mot_byte_fc_mix_workspace_bytes", "mot_byte_fc_mix_bwd_workspace_bytes",
     "mot_byte_fc_mix_fwd", "mot_byte_fc_mix_bwd",
     "mot_byte_cat_desc_size", "mot_byte_cat_workspace_bytes", "mot_byte_cat_bwd_workspace_bytes", "mot_byte_cat_fwd", "mot_byte_cat_bwd",
+    "mot_value_embeds_desc_size", "mot_value_embeds_bwd_workspace_bytes", "mot_value_embeds_fwd", "mot_value_embeds_bwd",
 )
 SWA_NO_RESIDUAL, SWA_ONE_RESIDUAL, SWA_TWO_RESIDUAL = 0, 1, 2
 
@@ -213,6 +215,22 @@ class MotByteCatGrads(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("slot", MotByteCatGradSlot * BYTE_CAT_MAX_OUT)]
 
 
+class MotValueEmbedsDesc(C.Structure):
+    """Mirror of struct MotValueEmbedsDesc (include/mot.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("dtype", C.c_int32), ("n_tokens", C.c_int64), ("tokens", C.c_void_p), ("tok_rows", C.c_int64),
+        ("dim", C.c_int32), ("n_tables", C.c_int32),
+        ("tables", C.c_void_p * VALUE_EMBEDS_MAX_TABLES), ("outs", C.c_void_p * VALUE_EMBEDS_MAX_TABLES),
+        ("status", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
+class MotValueEmbedsGrads(C.Structure):
+    """Mirror of struct MotValueEmbedsGrads (include/mot.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("grad_outs", C.c_void_p * VALUE_EMBEDS_MAX_TABLES),
+                ("d_tables", C.c_void_p * VALUE_EMBEDS_MAX_TABLES), ("token_order", C.c_void_p)]
+
+
 def _load() -> C.CDLL:
     if not LIB_PATH.exists():
         raise ImportError(
@@ -283,6 +301,13 @@ def _load() -> C.CDLL:
     lib.mot_byte_cat_fwd.restype = C.c_int
     lib.mot_byte_cat_bwd.argtypes = [C.POINTER(MotByteCatDesc), C.POINTER(MotByteCatGrads), vp]
     lib.mot_byte_cat_bwd.restype = C.c_int
+    lib.mot_value_embeds_desc_size.restype = C.c_size_t
+    lib.mot_value_embeds_bwd_workspace_bytes.restype = C.c_size_t
+    lib.mot_value_embeds_bwd_workspace_bytes.argtypes = [C.POINTER(MotValueEmbedsDesc)]
+    lib.mot_value_embeds_fwd.argtypes = [C.POINTER(MotValueEmbedsDesc), vp]
+    lib.mot_value_embeds_fwd.restype = C.c_int
+    lib.mot_value_embeds_bwd.argtypes = [C.POINTER(MotValueEmbedsDesc), C.POINTER(MotValueEmbedsGrads), vp]
+    lib.mot_value_embeds_bwd.restype = C.c_int
     for name in ("mot_tokens_to_bytes", "mot_pull_bytes", "mot_create_batch", "mot_char_matrix", "mot_gather_rows", "mot_embed_mix_fwd",
                  "mot_embed_mix_bwd"):
         getattr(lib, name).restype = C.c_int
@@ -302,6 +327,8 @@ def _load() -> C.CDLL:
         raise ImportError("MotByteFcMixDesc layout mismatch between include/mot.h and _capi.py")
     if lib.mot_byte_cat_desc_size() != C.sizeof(MotByteCatDesc):
         raise ImportError("MotByteCatDesc layout mismatch between include/mot.h and _capi.py")
+    if lib.mot_value_embeds_desc_size() != C.sizeof(MotValueEmbedsDesc):
+        raise ImportError("MotValueEmbedsDesc layout mismatch between include/mot.h and _capi.py")
     return lib
 
 

@@ -464,4 +464,20 @@ int mot_byte_cat_bwd(const MotByteCatDesc *desc, const MotByteCatGrads *grads, m
     return launch_byte_cat_bwd(*desc, *grads, (hipStream_t)stream);
 }
 
+size_t mot_value_embeds_desc_size(void) { return sizeof(MotValueEmbedsDesc); }
+
+size_t mot_value_embeds_bwd_workspace_bytes(const MotValueEmbedsDesc *desc) { return value_embeds_bwd_workspace_bytes(desc); }
+
+int mot_value_embeds_fwd(const MotValueEmbedsDesc *desc, mot_stream_t stream) {
+    if (int rc = value_embeds_check(desc, nullptr, false)) return rc;
+    if (desc->n_tokens == 0) return MOT_OK;
+    return launch_value_embeds_fwd(*desc, (hipStream_t)stream);
+}
+
+int mot_value_embeds_bwd(const MotValueEmbedsDesc *desc, const MotValueEmbedsGrads *grads, mot_stream_t stream) {
+    if (int rc = value_embeds_check(desc, grads, true)) return rc;
+    if (desc->n_tokens == 0) return MOT_OK;
+    return launch_value_embeds_bwd(*desc, *grads, (hipStream_t)stream);
+}
+
 }  // extern "C"

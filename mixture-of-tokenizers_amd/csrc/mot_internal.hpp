@@ -95,6 +95,12 @@ int launch_narrow_transpose(const float *src, int rows, int cols, void *dst_bf16
 size_t group_positions_ws_ints(int64_t n, int64_t rows);
 int launch_group_positions(const int32_t *ids, int64_t n, int64_t rows, int32_t *ws_ints, const int32_t **pos_sorted, const int32_t **id_sorted,
                            uint32_t *status, hipStream_t stream);
+// what launch_group_positions leaves in its buffer, which is also what mot_token_order hands out:
+// [counts: rows][starts: rows][rank: n][pos_sorted: n][id_sorted: n].  Groups are complete; the order inside a group is the sort's own.
+struct GroupedPositions { const int32_t *counts, *starts, *pos_sorted, *id_sorted; };
+inline GroupedPositions grouped_positions_view(const int32_t *ws_ints, int64_t n, int64_t rows) {
+    return {ws_ints, ws_ints + rows, ws_ints + 2 * rows + n, ws_ints + 2 * rows + 2 * n};
+}
 // zero n 32-bit words with a kernel (not hipMemsetAsync: a memset node aborts on graph replay with this runtime; mot_group.hip)
 int launch_zero_words(void *p, int64_t n_words, hipStream_t stream);
 size_t cross_attn_bwd_workspace_bytes(const MotCrossAttnDesc &d);
@@ -125,5 +131,10 @@ size_t byte_cat_workspace_bytes(const MotByteCatDesc *d);       // 0: the forwar
 size_t byte_cat_bwd_workspace_bytes(const MotByteCatDesc *d);   // 0 for a descriptor the call would refuse
 int launch_byte_cat_fwd(const MotByteCatDesc &d, hipStream_t stream);
 int launch_byte_cat_bwd(const MotByteCatDesc &d, const MotByteCatGrads &g, hipStream_t stream);
+// token value embeddings (mot_values.hip): validation before any HIP call (g: backward only), then the launches
+int value_embeds_check(const MotValueEmbedsDesc *d, const MotValueEmbedsGrads *g, bool backward);
+size_t value_embeds_bwd_workspace_bytes(const MotValueEmbedsDesc *d);   // 0 for a descriptor the call would refuse
+int launch_value_embeds_fwd(const MotValueEmbedsDesc &d, hipStream_t stream);
+int launch_value_embeds_bwd(const MotValueEmbedsDesc &d, const MotValueEmbedsGrads &g, hipStream_t stream);
 
 }  // namespace mot

@@ -357,22 +357,24 @@ class _TokenOrderCache:
         self.keep, self.entries, self.side = keep, [], {}
 
     def get(self, tokens: torch.Tensor, tok_rows: int):
+        # Inside a graph capture the cache is neither read nor written: the sort is captured in line on the capturing stream.  An
+        # entry made eagerly would be replayed as it is after tokens.copy_(new batch) (the graph does not re-sort) and carries an
+        # event recorded outside the capture; an entry made here would hand later eager calls a buffer that only replays refresh.
+        if torch.cuda.is_current_stream_capturing():
+            return token_order(tokens, tok_rows), None
         for e in self.entries:
             if e[0] is tokens and e[1] == tokens._version and e[2] == tok_rows:
                 return e[3], e[4]
         dev = tokens.device
         cur = torch.cuda.current_stream(dev)
-        if torch.cuda.is_current_stream_capturing():          # inside a graph capture: no side stream, the sort is captured in line
-            order, ev = token_order(tokens, tok_rows), None
-        else:
-            side = self.side.get(dev.index)
-            if side is None:
-                side = self.side[dev.index] = torch.cuda.Stream(device=dev)
-            side.wait_stream(cur)                              # the tokens are ready when the current stream gets here
-            with torch.cuda.stream(side):
-                order = token_order(tokens, tok_rows)
-                ev = torch.cuda.Event()
-                ev.record(side)
+        side = self.side.get(dev.index)
+        if side is None:
+            side = self.side[dev.index] = torch.cuda.Stream(device=dev)
+        side.wait_stream(cur)                              # the tokens are ready when the current stream gets here
+        with torch.cuda.stream(side):
+            order = token_order(tokens, tok_rows)
+            ev = torch.cuda.Event()
+            ev.record(side)
         self.entries.insert(0, (tokens, tokens._version, tok_rows, order, ev))
         del self.entries[self.keep:]
         return order, ev
@@ -1419,3 +1421,168 @@ def byte_cat(tables, *, bpt: int, norm, tokens: torch.Tensor | None = None, ids:
         return (tuple(r[:n]), r[n], r[n + 1]) if return_ids and ttb is not None else tuple(r[:n])
     outs, ids_padded, ids_pulled = _byte_cat_fwd(tables, **kw)
     return (outs, ids_padded, ids_pulled) if return_ids and ttb is not None else outs
+
+
+# ------------------------------------------------------------------------------------------------
+# token value embeddings (scaled-pre-train/train_gpt.py:566, 600; modded-nanogpt/runs/71_*_toks-valemb.py:247, 303):
+# out_j = table_j[tokens] for up to four tables of one shape over one token stream
+# ------------------------------------------------------------------------------------------------
+def _value_embeds_tokens(tokens, what):
+    if tokens.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"{what}: tokens must be int32 or int64, got {tokens.dtype}")
+    if tokens.ndim not in (1, 2):
+        raise ValueError(f"{what}: tokens must be (T,) or (B, T), got {tuple(tokens.shape)}")
+    tok = tokens.to(torch.int32) if tokens.dtype != torch.int32 else tokens
+    return tok if tok.is_contiguous() else tok.contiguous()
+
+
+def _value_embeds_desc(tok, n_tables, rows, dim, dtype, what):
+    if not 1 <= n_tables <= capi.VALUE_EMBEDS_MAX_TABLES:
+        raise ValueError(f"{what}: {n_tables} tables, 1..{capi.VALUE_EMBEDS_MAX_TABLES} are built")
+    d = capi.MotValueEmbedsDesc()
+    d.struct_size = C.sizeof(capi.MotValueEmbedsDesc)
+    d.dtype = capi.dtype_code(dtype)
+    d.n_tokens, d.tokens, d.tok_rows, d.dim, d.n_tables = tok.numel(), capi.ptr(tok), int(rows), int(dim), n_tables
+    return d
+
+
+def _value_embeds_tables(tables, what):
+    """1..4 (rows, dim) tables of one shape and dtype; a contiguous table is used where it lives (no copy)."""
+    tables = list(tables)
+    if not tables:
+        raise ValueError(f"{what}: no tables")
+    dt = tables[0].dtype
+    for j, t in enumerate(tables):
+        if t.dtype != dt:
+            raise TypeError(f"{what}: table {j} is {t.dtype} but table 0 is {dt}: all tables share one dtype")
+        if t.ndim != 2 or t.shape != tables[0].shape:
+            raise ValueError(f"{what}: table {j} must be (rows, dim) = {tuple(tables[0].shape)}, got {tuple(t.shape)}")
+    return [_table(t, f"{what}: table {j}") for j, t in enumerate(tables)]
+
+
+@torch.compiler.disable
+def _value_embeds_fwd(tokens, tables):
+    dev = capi.require_device(tokens, *tables)
+    tabs = _value_embeds_tables(tables, "value_embeds")
+    tok = _value_embeds_tokens(tokens, "value_embeds")
+    rows, dim = tabs[0].shape
+    d = _value_embeds_desc(tok, len(tabs), rows, dim, tabs[0].dtype, "value_embeds")
+    outs = tuple(torch.empty(tuple(tokens.shape) + (dim,), dtype=tabs[0].dtype, device=dev) for _ in tabs)
+    if tok.numel() == 0:   # an empty batch: nothing to launch
+        return outs
+    for j, (t, o) in enumerate(zip(tabs, outs)):
+        d.tables[j], d.outs[j] = capi.ptr(t), capi.ptr(o)
+    d.status = capi.ptr(capi.status_word(dev))
+    capi.check(capi.lib.mot_value_embeds_fwd(C.byref(d), capi.stream_of(dev)))
+    capi.after_call(dev)
+    return outs
+
+
+@torch.compiler.disable
+def _value_embeds_bwd(grad_outs, tokens, rows, dim, dtype, token_order, out=None):
+    grad_outs = list(grad_outs)
+    out = list(out) if out is not None else [None] * len(grad_outs)
+    if len(out) != len(grad_outs):
+        raise ValueError(f"value_embeds_backward: {len(out)} buffers in `out` for {len(grad_outs)} tables")
+    dev = capi.require_device(tokens, token_order, *[g for g in grad_outs if g is not None])
+    tok = _value_embeds_tokens(tokens, "value_embeds_backward")
+    d = _value_embeds_desc(tok, len(grad_outs), rows, dim, dtype, "value_embeds_backward")
+    gr = capi.MotValueEmbedsGrads()
+    gr.struct_size = C.sizeof(capi.MotValueEmbedsGrads)
+    keep, res = [tok], []
+    n = tok.numel()
+    for j, g in enumerate(grad_outs):
+        if g is None:
+            res.append(None)
+            continue
+        gc = _contig(g, dtype, f"grad_outs[{j}]")
+        if gc.numel() != n * dim:
+            raise ValueError(f"grad_outs[{j}] must be tokens.shape + ({dim},), got {tuple(g.shape)}")
+        keep.append(gc)
+        # written once by the call, every element: nothing to zero (an empty batch launches nothing and is all zeros)
+        dt = out[j]
+        if dt is None:
+            dt = (torch.empty if n else torch.zeros)((rows, dim), dtype=dtype, device=dev)
+        elif dt.dtype != dtype or tuple(dt.shape) != (rows, dim) or not dt.is_contiguous() or dt.device != dev:
+            raise ValueError(f"out[{j}] must be a contiguous {dtype} tensor of the table's shape ({rows}, {dim}) on {dev}")
+        elif n == 0:
+            dt.zero_()
+        res.append(dt)
+        gr.grad_outs[j], gr.d_tables[j] = capi.ptr(gc), capi.ptr(dt)
+    if n == 0 or all(g is None for g in grad_outs):
+        return res
+    if token_order is not None:
+        need = capi.lib.mot_token_order_ints(n, int(rows))
+        if token_order.dtype != torch.int32 or token_order.numel() != need or not token_order.is_contiguous():
+            raise ValueError(f"token_order must be the int32[{need}] tensor token_order(tokens, {rows}) returned")
+        gr.token_order = capi.ptr(token_order)
+    d.status = capi.ptr(capi.status_word(dev))
+    ws = _workspace(dev, capi.lib.mot_value_embeds_bwd_workspace_bytes(C.byref(d)))
+    if ws is not None:
+        d.workspace, d.workspace_bytes = capi.ptr(ws), ws.numel()
+    capi.check(capi.lib.mot_value_embeds_bwd(C.byref(d), C.byref(gr), capi.stream_of(dev)))
+    capi.after_call(dev)
+    return res
+
+
+@torch.compiler.disable
+def value_embeds_backward(grad_outs, tokens: torch.Tensor, tables, *, token_order: torch.Tensor | None = None, out=None) -> list:
+    """One call of mot_value_embeds_bwd.  `grad_outs` holds one upstream gradient ``tokens.shape + (dim,)`` or None per table; a
+    table whose entry is None is skipped and gets None back.  Returns the dense table gradients in the TABLES' dtype: each is the
+    fp32 sum of its positions' rows rounded once, rows of absent ids are +0, and every element is written exactly once by the call
+    (nothing is zeroed first, nothing accumulated).  The same inputs give the same bits on every run, with or without
+    `token_order` (what :func:`token_order` returned for these tokens and this table height; the caller orders streams).  `out` (a
+    list: a tensor of the table's shape and dtype, or None, per table) names buffers to write the gradients INTO instead of fresh
+    ones -- overwritten, not accumulated, whatever they held; the buffer of a table whose gradient is None is not touched."""
+    tabs = _value_embeds_tables(tables, "value_embeds_backward")
+    grad_outs = list(grad_outs)
+    if len(grad_outs) != len(tabs):
+        raise ValueError(f"value_embeds_backward: {len(grad_outs)} gradients for {len(tabs)} tables")
+    capi.require_device(tokens, *tabs)
+    return _value_embeds_bwd(grad_outs, tokens, tabs[0].shape[0], tabs[0].shape[1], tabs[0].dtype, token_order, out)
+
+
+class _ValueEmbedsFn(torch.autograd.Function):
+    """Autograd node of value_embeds: one mot_value_embeds_fwd call forward, one mot_value_embeds_bwd call backward for all
+    tables.  Saved: the tokens only (the gradient does not read the tables); the token order comes from the cache the fused
+    front-end uses, so a step that feeds one token tensor to both sorts it once."""
+
+    @staticmethod
+    def forward(ctx, tokens, *tables):
+        outs = _value_embeds_fwd(tokens, [t.detach() for t in tables])
+        ctx.order = _token_orders.get(tokens, tables[0].shape[0]) if _HOIST_SORT and tokens.numel() else None
+        ctx.save_for_backward(tokens)
+        ctx.set_materialize_grads(False)   # an output nothing depends on arrives as None and its table is skipped
+        ctx.meta = (tables[0].shape[0], tables[0].shape[1], tables[0].dtype, len(tables))
+        return outs
+
+    @staticmethod
+    def backward(ctx, *grads):
+        tokens, = ctx.saved_tensors
+        rows, dim, dtype, n = ctx.meta
+        gs = [g if ctx.needs_input_grad[1 + j] else None for j, g in enumerate(grads[:n])]
+        if all(g is None for g in gs):
+            return (None,) * (1 + n)
+        order = None
+        if ctx.order is not None:
+            order, ev = ctx.order
+            cur = torch.cuda.current_stream(tokens.device)
+            if ev is not None:
+                cur.wait_event(ev)
+            order.record_stream(cur)
+        return (None, *_value_embeds_bwd(gs, tokens, rows, dim, dtype, order))
+
+
+def value_embeds(tokens: torch.Tensor, tables) -> tuple:
+    """The token value embeddings of scaled-pre-train/train_gpt.py:566 / 600 and modded-nanogpt/runs/71_*_toks-valemb.py:247 /
+    303, ``[value_embed(tokens) for value_embed in value_embeds]``, in one launch: for each of the 1..4 `tables` (vocab, dim), all
+    of one shape and dtype (float32 or bfloat16), ``out_j = table_j[tokens]``, a bit-exact copy.  `tokens` is (T,) or (B, T), int32
+    or int64; each output has shape ``tokens.shape + (dim,)``.  One autograd node covers all tables; its backward writes each table
+    gradient once, in the table's dtype, with the same bits on every run (see :func:`value_embeds_backward`)."""
+    tables = list(tables)
+    if isinstance(tokens, torch.Tensor) and all(isinstance(t, torch.Tensor) for t in tables):
+        capi.require_device(tokens, *tables)
+    _value_embeds_tables(tables, "value_embeds")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tables):
+        return tuple(_ValueEmbedsFn.apply(tokens, *tables))
+    return _value_embeds_fwd(tokens, tables)

@@ -782,6 +782,24 @@ class BytesFrontEnd(nn.Module):
         return (outs.pop(0) if x0 else None), outs
 
 
+class ValueEmbeds(nn.ModuleList):
+    """The token value embeddings of scaled-pre-train/train_gpt.py:566 / 600 and modded-nanogpt/runs/71_*_toks-valemb.py:247 /
+    303, ``nn.ModuleList([nn.Embedding(vocab_size, model_dim) for _ in range(3)])`` and ``[value_embed(toks_in) for value_embed in
+    self.value_embeds]``, as one forward and one backward call of the library for all tables.  It IS that ModuleList of
+    nn.Embedding: assigned to ``self.value_embeds`` the state-dict keys are ``value_embeds.{0,1,2}.weight``, and
+    ``model.value_embeds.parameters()`` and the ``isinstance(m, nn.Embedding): m.bfloat16()`` cast of the training scripts work as
+    before.  Every call reads the members' current ``weight``: tied, replaced or in-place-updated tables are honoured."""
+
+    def __init__(self, vocab_size: int, model_dim: int, n: int = 3):
+        if not 1 <= n <= 4:
+            raise ValueError(f"ValueEmbeds: n = {n}, one call serves 1..4 tables")
+        super().__init__([nn.Embedding(vocab_size, model_dim) for _ in range(n)])
+
+    def forward(self, tokens: Tensor) -> list[Tensor]:
+        """tokens (T,) or (B, T), int32 or int64 -> [ve_0, ..., ve_{n-1}], each ``tokens.shape + (model_dim,)``."""
+        return list(F_mot.value_embeds(tokens, [_f32(e.weight, "value table") for e in self]))
+
+
 # ------------------------------------------------------------------------------------------------
 # Llama character mixer (inference/inference.py): BASELINE config 5's front-end
 # ------------------------------------------------------------------------------------------------
