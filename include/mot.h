@@ -768,6 +768,97 @@ size_t mot_value_embeds_bwd_workspace_bytes(const MotValueEmbedsDesc *fwd /* hos
 int mot_value_embeds_fwd(const MotValueEmbedsDesc *desc /* host */, mot_stream_t stream);
 int mot_value_embeds_bwd(const MotValueEmbedsDesc *fwd /* host */, const MotValueEmbedsGrads *grads /* host */, mot_stream_t stream);
 
+/*
+ * Mixture-of-tokenizers value embeddings: one to four slots, each a token value table, a byte value table and a mixin weight, over ONE
+ * token stream and ONE byte-id stream, which replaces
+ *   ve_tokens = [value_embed(token_inputs)[None] for value_embed in self.value_embeds_toks]
+ *   ve_bytes = [value_embed(byte_inputs).squeeze()[None] for value_embed in self.value_embeds_bytes]
+ *   ve = [mixin_bytes(vet, veb, vbmw) for vet, veb, vbmw in zip(ve_tokens, ve_bytes, self.value_byte_mixin_weights)]
+ * of modded-nanogpt/runs/9_mot-in_mot-valemb.py:310-313 (mixin_bytes 225-235, parameters 252-254; runs 3 and 6 alike).
+ * Per slot j and token n of row-major (B, T), with K = token_dim + bpt * byte_dim:
+ *   u_j[n] = cat(tok_table_j[tokens[n]], byte_table_j[ids[n, 0]], ..., byte_table_j[ids[n, bpt-1]])
+ *   y_j[n] = weight_j u_j[n]                       weight_j [out_dim, K], nn.Linear layout, no bias
+ *   out_j[n] = rms_norm(y_j[n]) if norm_out else y_j[n]
+ * The ids are in per-token byte order [B, T*bpt], given (MOT_IDS_GIVEN) or made ONCE for all slots from the token->byte table
+ * (MOT_IDS_FROM_TTB: tokens_to_bytes, then pull_dir); an id outside a table reads row 0 and raises MOT_STATUS_TOKEN_OOR /
+ * MOT_STATUS_BYTE_OOR.  All tables and weights share one dtype.  MOT_BF16: fp32 sums, rounded where the reference's bf16 run
+ * rounds: y = bf16(W u), r = rsqrt(mean(y^2) + eps) in fp32, out = bf16(r y).  eps <= 0 means FLT_EPSILON for BOTH dtypes, as in
+ * MotByteFcMixDesc.
+ * Refused with MOT_EUNSUPPORTED before any launch: token_dim, byte_dim or out_dim not a multiple of the 16-byte vector (4 fp32 /
+ * 8 bf16 elements), K or out_dim above 2048, n_slots outside 1..MOT_VALUE_MIX_MAX_SLOTS.  A wrong struct_size or a null slot
+ * pointer is MOT_EINVAL.  An empty batch returns MOT_OK.  Every call is asynchronous on `stream`, allocates nothing and never
+ * synchronises; all zeroing is done by kernels, so forward + backward capture into a hipGraph.
+ */
+#define MOT_VALUE_MIX_MAX_SLOTS 4
+
+typedef struct MotValueMixSlot {
+    const void *tok_table;  /* [tok_rows, token_dim] */
+    const void *byte_table; /* [byte_rows, byte_dim] */
+    const void *weight;     /* [out_dim, token_dim + bpt*byte_dim] */
+    void *out;              /* [B, T, out_dim]; the backward reads it when norm_out */
+    float *out_row_rnorm;   /* [B, T] fp32: r of every row.  Optional in the forward; the backward needs it when norm_out */
+} MotValueMixSlot;
+
+typedef struct MotValueMixDesc {
+    uint32_t struct_size;   /* sizeof(MotValueMixDesc), checked */
+    int32_t dtype;          /* MotDType of every table / weight / out / grad_out */
+    int64_t n_rows;         /* B */
+    int64_t tokens_per_row; /* T */
+    int32_t bpt;            /* byte slots per token */
+    int32_t id_source;      /* MOT_IDS_FROM_TTB | MOT_IDS_GIVEN */
+    const int32_t *tokens;  /* [B, T] */
+    int32_t pull_dir;       /* MotPullDir           (FROM_TTB) */
+    int32_t ttb_elem_bytes; /* 2 | 4                (FROM_TTB) */
+    const void *ttb;        /* [ttb_rows, bpt]      (FROM_TTB) */
+    int64_t ttb_rows;
+    int32_t pad_byte, eot_byte;
+    const int64_t *ids;     /* [B, T*bpt]           (GIVEN) */
+    int64_t tok_rows;       /* rows of every token value table */
+    int64_t byte_rows;      /* rows of every byte value table */
+    int32_t token_dim, byte_dim, out_dim;
+    int32_t n_slots;        /* 1 .. MOT_VALUE_MIX_MAX_SLOTS */
+    int32_t norm_out;       /* 0: out = y */
+    float eps;              /* <= 0 -> FLT_EPSILON, both dtypes */
+    MotValueMixSlot slot[MOT_VALUE_MIX_MAX_SLOTS];
+    int64_t *out_ids;       /* optional [B, T*bpt] (FROM_TTB): the ids the tables were read with, what the backward wants as `ids` */
+    uint32_t *status;       /* optional device word, see MOT_STATUS_* */
+    void *workspace;        /* >= mot_value_mix_workspace_bytes(desc, backward), 16-byte aligned */
+    size_t workspace_bytes;
+} MotValueMixDesc;
+
+/*
+ * Backward: `fwd` is the forward's descriptor with id_source == MOT_IDS_GIVEN (the ids the forward used or wrote).  Per slot j
+ * whose grad_out is non-null (a null grad_out skips the slot and touches none of its buffers), with x = out_j and r = out_row_rnorm_j:
+ *   dy = r (g - x (g.x) / out_dim)        (dy = g without the norm)
+ *   du = dy weight_j;   d_weight += dy^T u_j        u_j gathered again, slab by slab
+ *   d_tok[r, :]  = round_to_dtype(fp32 sum of du[n, 0:token_dim] over the positions n with tokens[n] == r),  +0 where r is absent
+ *   d_byte[ids[n, k], :] += du[n, token_dim + k*byte_dim : token_dim + (k+1)*byte_dim]
+ * d_tok is WRITTEN exactly once, in the tables' dtype, with plain stores, under the contract of mot_value_embeds_bwd (the caller
+ * zeroes nothing, the same bits on every run, with or without `token_order`); all slots share one token order -- the caller's or
+ * one made in the workspace -- and one set of canonical positions.  d_byte and d_weight are FP32 for both dtypes and ACCUMULATED
+ * into (+=) with float atomics (the byte tables through the LDS fixed-point sums of mot_byte_cat_bwd).  MOT_BF16: du and
+ * d_weight run on the bf16 MFMA from bf16(dy) with fp32 sums; du stays fp32 on its way into the tables.  The workspace holds one
+ * slot's rows plus the shared order, whatever n_slots is.
+ */
+typedef struct MotValueMixGradSlot {
+    const void *grad_out; /* [B, T, out_dim] in dtype, or NULL */
+    void *d_tok;          /* [tok_rows, token_dim]   in dtype, written once */
+    void *d_byte;         /* [byte_rows, byte_dim]   fp32, += */
+    void *d_weight;       /* [out_dim, K]            fp32, += */
+} MotValueMixGradSlot;
+
+typedef struct MotValueMixGrads {
+    uint32_t struct_size; /* sizeof(MotValueMixGrads) */
+    uint32_t reserved;
+    MotValueMixGradSlot slot[MOT_VALUE_MIX_MAX_SLOTS];
+    const int32_t *token_order; /* optional, as MotEmbedMixGrads.token_order */
+} MotValueMixGrads;
+
+size_t mot_value_mix_desc_size(void);
+size_t mot_value_mix_workspace_bytes(const MotValueMixDesc *desc /* host */, int backward);   /* 0 for a descriptor the call would refuse */
+int mot_value_mix_fwd(const MotValueMixDesc *desc /* host */, mot_stream_t stream);
+int mot_value_mix_bwd(const MotValueMixDesc *fwd /* host */, const MotValueMixGrads *grads /* host */, mot_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,6 +62,7 @@ EXPORTS = (
     "mot_byte_fc_mix_fwd", "mot_byte_fc_mix_bwd",
     "mot_byte_cat_desc_size", "mot_byte_cat_workspace_bytes", "mot_byte_cat_bwd_workspace_bytes", "mot_byte_cat_fwd", "mot_byte_cat_bwd",
     "mot_value_embeds_desc_size", "mot_value_embeds_bwd_workspace_bytes", "mot_value_embeds_fwd", "mot_value_embeds_bwd",
+    "mot_value_mix_desc_size", "mot_value_mix_workspace_bytes", "mot_value_mix_fwd", "mot_value_mix_bwd",
 )
 SWA_NO_RESIDUAL, SWA_ONE_RESIDUAL, SWA_TWO_RESIDUAL = 0, 1, 2
 
@@ -231,6 +232,38 @@ class MotValueEmbedsGrads(C.Structure):
                 ("d_tables", C.c_void_p * VALUE_EMBEDS_MAX_TABLES), ("token_order", C.c_void_p)]
 
 
+VALUE_MIX_MAX_SLOTS = 4
+
+
+class MotValueMixSlot(C.Structure):
+    """Mirror of struct MotValueMixSlot (include/mot.h)."""
+    _fields_ = [("tok_table", C.c_void_p), ("byte_table", C.c_void_p), ("weight", C.c_void_p), ("out", C.c_void_p), ("out_row_rnorm", C.c_void_p)]
+
+
+class MotValueMixDesc(C.Structure):
+    """Mirror of struct MotValueMixDesc (include/mot.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("dtype", C.c_int32), ("n_rows", C.c_int64), ("tokens_per_row", C.c_int64),
+        ("bpt", C.c_int32), ("id_source", C.c_int32), ("tokens", C.c_void_p), ("pull_dir", C.c_int32), ("ttb_elem_bytes", C.c_int32),
+        ("ttb", C.c_void_p), ("ttb_rows", C.c_int64), ("pad_byte", C.c_int32), ("eot_byte", C.c_int32), ("ids", C.c_void_p),
+        ("tok_rows", C.c_int64), ("byte_rows", C.c_int64), ("token_dim", C.c_int32), ("byte_dim", C.c_int32), ("out_dim", C.c_int32),
+        ("n_slots", C.c_int32), ("norm_out", C.c_int32), ("eps", C.c_float),
+        ("slot", MotValueMixSlot * VALUE_MIX_MAX_SLOTS),
+        ("out_ids", C.c_void_p), ("status", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
+class MotValueMixGradSlot(C.Structure):
+    """Mirror of struct MotValueMixGradSlot (include/mot.h)."""
+    _fields_ = [("grad_out", C.c_void_p), ("d_tok", C.c_void_p), ("d_byte", C.c_void_p), ("d_weight", C.c_void_p)]
+
+
+class MotValueMixGrads(C.Structure):
+    """Mirror of struct MotValueMixGrads (include/mot.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("slot", MotValueMixGradSlot * VALUE_MIX_MAX_SLOTS),
+                ("token_order", C.c_void_p)]
+
+
 def _load() -> C.CDLL:
     if not LIB_PATH.exists():
         raise ImportError(
@@ -308,6 +341,13 @@ def _load() -> C.CDLL:
     lib.mot_value_embeds_fwd.restype = C.c_int
     lib.mot_value_embeds_bwd.argtypes = [C.POINTER(MotValueEmbedsDesc), C.POINTER(MotValueEmbedsGrads), vp]
     lib.mot_value_embeds_bwd.restype = C.c_int
+    lib.mot_value_mix_desc_size.restype = C.c_size_t
+    lib.mot_value_mix_workspace_bytes.restype = C.c_size_t
+    lib.mot_value_mix_workspace_bytes.argtypes = [C.POINTER(MotValueMixDesc), i32]
+    lib.mot_value_mix_fwd.argtypes = [C.POINTER(MotValueMixDesc), vp]
+    lib.mot_value_mix_fwd.restype = C.c_int
+    lib.mot_value_mix_bwd.argtypes = [C.POINTER(MotValueMixDesc), C.POINTER(MotValueMixGrads), vp]
+    lib.mot_value_mix_bwd.restype = C.c_int
     for name in ("mot_tokens_to_bytes", "mot_pull_bytes", "mot_create_batch", "mot_char_matrix", "mot_gather_rows", "mot_embed_mix_fwd",
                  "mot_embed_mix_bwd"):
         getattr(lib, name).restype = C.c_int
@@ -329,6 +369,8 @@ def _load() -> C.CDLL:
         raise ImportError("MotByteCatDesc layout mismatch between include/mot.h and _capi.py")
     if lib.mot_value_embeds_desc_size() != C.sizeof(MotValueEmbedsDesc):
         raise ImportError("MotValueEmbedsDesc layout mismatch between include/mot.h and _capi.py")
+    if lib.mot_value_mix_desc_size() != C.sizeof(MotValueMixDesc):
+        raise ImportError("MotValueMixDesc layout mismatch between include/mot.h and _capi.py")
     return lib
 
 

@@ -480,4 +480,20 @@ int mot_value_embeds_bwd(const MotValueEmbedsDesc *desc, const MotValueEmbedsGra
     return launch_value_embeds_bwd(*desc, *grads, (hipStream_t)stream);
 }
 
+size_t mot_value_mix_desc_size(void) { return sizeof(MotValueMixDesc); }
+
+size_t mot_value_mix_workspace_bytes(const MotValueMixDesc *desc, int backward) { return value_mix_workspace_bytes(desc, backward != 0); }
+
+int mot_value_mix_fwd(const MotValueMixDesc *desc, mot_stream_t stream) {
+    if (int rc = value_mix_check(desc, nullptr, false)) return rc;
+    if (desc->n_rows == 0 || desc->tokens_per_row == 0) return MOT_OK;
+    return launch_value_mix_fwd(*desc, (hipStream_t)stream);
+}
+
+int mot_value_mix_bwd(const MotValueMixDesc *desc, const MotValueMixGrads *grads, mot_stream_t stream) {
+    if (int rc = value_mix_check(desc, grads, true)) return rc;
+    if (desc->n_rows == 0 || desc->tokens_per_row == 0) return MOT_OK;
+    return launch_value_mix_bwd(*desc, *grads, (hipStream_t)stream);
+}
+
 }  // extern "C"

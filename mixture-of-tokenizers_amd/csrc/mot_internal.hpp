@@ -136,5 +136,18 @@ int value_embeds_check(const MotValueEmbedsDesc *d, const MotValueEmbedsGrads *g
 size_t value_embeds_bwd_workspace_bytes(const MotValueEmbedsDesc *d);   // 0 for a descriptor the call would refuse
 int launch_value_embeds_fwd(const MotValueEmbedsDesc &d, hipStream_t stream);
 int launch_value_embeds_bwd(const MotValueEmbedsDesc &d, const MotValueEmbedsGrads &g, hipStream_t stream);
+// one table's gradient from fp32 rows with a row stride, written once in `dtype` (mot_values.hip: the value embeddings' order, canon,
+// slices and rows kernels).  ws: token_sums_ws_bytes; prepare = false reuses the order and canon an earlier call left there
+size_t token_sums_ws_bytes(int64_t n, int64_t rows, int dim, int dtype);
+int launch_token_sums_f32(const int32_t *tokens, int64_t n, int64_t rows, int dim, int dtype, const float *g, int g_ld, void *d_table,
+                          const int32_t *order, bool prepare, char *ws, uint32_t *status, hipStream_t stream);
+// mixture-of-tokenizers value embeddings (mot_valuemix.hip): validation before any HIP call (g: backward only), then the launches
+int value_mix_check(const MotValueMixDesc *d, const MotValueMixGrads *g, bool backward);
+size_t value_mix_workspace_bytes(const MotValueMixDesc *d, bool backward);   // 0 for a descriptor the call would refuse
+int launch_value_mix_fwd(const MotValueMixDesc &d, hipStream_t stream);
+int launch_value_mix_bwd(const MotValueMixDesc &d, const MotValueMixGrads &g, hipStream_t stream);
+// the gather-GEMM of mot_concat16.hip for up to four (token table, byte table, W, out) sets over one token and id stream in ONE launch
+struct Concat16Slots { int n; const void *tok_table[4], *byte_table[4], *weight[4]; void *out[4]; float *row_rnorm[4]; };
+int launch_concat16_slots(const MotEmbedMixDesc &d, const Concat16Slots &S, const int32_t *tokens, const int64_t *ids, int64_t n, hipStream_t stream);
 
 }  // namespace mot

@@ -101,6 +101,7 @@ struct VeBwdArgs {
     float *part;       // [slices][2: head, tail][nslot][D] fp32 pieces of the groups that cross a slice boundary
     int64_t N;
     int rows, D, nslot, nck;   // nck: blocks of 64 16-byte chunks per row
+    int g_ld;                  // elements between the rows of g (D for the value embeddings' own gradients)
     const void *g[kVeTables];
     void *d[kVeTables];
 };
@@ -205,10 +206,26 @@ __global__ __launch_bounds__(kVeSortThreads) void ve_canon_sort_kernel(const VeB
     }
 }
 
-template <typename T>
+// how a lane's chunk of a gradient row arrives: in the tables' dtype (G == T), or as fp32 rows for bf16 tables (the value mix's du,
+// mot_valuemix.hip: the sums then start from unrounded terms)
+template <typename G, typename T> struct VeIn {
+    typedef typename Elem<T>::raw raw;
+    static __device__ __forceinline__ raw load(const G *p) { return Elem<T>::load_raw(p); }
+    static __device__ __forceinline__ typename Elem<T>::vec widen(raw r) { return Elem<T>::widen(r); }
+};
+template <> struct VeIn<float, __bf16> {
+    typedef float8v raw;
+    static __device__ __forceinline__ raw load(const float *p) {
+        const float4v a = *(const float4v *)p, b = *(const float4v *)(p + 4);
+        return float8v{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    }
+    static __device__ __forceinline__ float8v widen(raw r) { return r; }
+};
+
+template <typename G, typename T>
 __global__ __launch_bounds__(kThreads) void ve_bwd_slices_kernel(const VeBwdArgs A) {
     typedef typename Elem<T>::vec vec_t;
-    typedef typename Elem<T>::raw raw_t;
+    typedef typename VeIn<G, T>::raw raw_t;
     constexpr int VEC = Elem<T>::kVec, U = 8;   // rows in flight per lane, whatever the groups' lengths
     const int lane = threadIdx.x & 63;
     const int64_t slice = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
@@ -217,7 +234,7 @@ __global__ __launch_bounds__(kThreads) void ve_bwd_slices_kernel(const VeBwdArgs
     const int js = blockIdx.y / A.nck, ck = blockIdx.y - js * A.nck;
     const int D = A.D, col = VEC * (ck * 64 + lane);
     const bool act = col < D;
-    const T *g = (const T *)A.g[js] + (act ? col : 0);
+    const G *g = (const G *)A.g[js] + (act ? col : 0);
     T *dt = (T *)A.d[js] + col;
     const int n = (int)min((int64_t)kVeSlice, A.N - b);
     int myid = -1, myp = 0;
@@ -235,12 +252,12 @@ __global__ __launch_bounds__(kThreads) void ve_bwd_slices_kernel(const VeBwdArgs
     for (int t0 = 0; t0 < n; t0 += U) {
         raw_t r[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u) r[u] = Elem<T>::load_raw(g + (int64_t)__shfl(myp, min(t0 + u, n - 1)) * D);
+        for (int u = 0; u < U; ++u) r[u] = VeIn<G, T>::load(g + (int64_t)__shfl(myp, min(t0 + u, n - 1)) * A.g_ld);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int t = t0 + u;
             if (t >= n) break;
-            acc += Elem<T>::widen(r[u]);
+            acc += VeIn<G, T>::widen(r[u]);
             if (!((ends >> t) & 1ull)) continue;
             const int id = __shfl(myid, t);
             const bool opens = m > 0 || id != before;        // the group's first position is in this slice
@@ -402,27 +419,15 @@ int launch_value_embeds_fwd(const MotValueEmbedsDesc &d, hipStream_t stream) {
     }
 }
 
-int launch_value_embeds_bwd(const MotValueEmbedsDesc &d, const MotValueEmbedsGrads &gr, hipStream_t stream) {
-    const int64_t N = d.n_tokens;
-    const bool bf = d.dtype == MOT_BF16;
-    VeBwdArgs A{};
-    A.N = N; A.rows = (int)d.tok_rows; A.D = d.dim;
-    A.nck = (d.dim / (bf ? 8 : 4) + 63) / 64;
-    for (int j = 0; j < d.n_tables; ++j) {
-        if (!gr.grad_outs[j]) continue;
-        A.g[A.nslot] = gr.grad_outs[j];
-        A.d[A.nslot++] = gr.d_tables[j];
-    }
-    if (!A.nslot) return MOT_OK;
-    const VeLayout L = value_embeds_layout(d);
-    char *ws = (char *)d.workspace;
-    const int32_t *order = gr.token_order;
+// the token order (the caller's, or one made at L.order) and the canonical positions at L.canon
+static int ve_order_and_canon(VeBwdArgs &A, const VeLayout &L, const int32_t *tokens, const int32_t *order, char *ws, uint32_t *status, hipStream_t stream) {
+    const int64_t N = A.N;
     if (!order) {
         const int32_t *pos, *ids;
-        if (int rc = launch_group_positions(d.tokens, N, d.tok_rows, (int32_t *)(ws + L.order), &pos, &ids, d.status, stream)) return rc;
+        if (int rc = launch_group_positions(tokens, N, A.rows, (int32_t *)(ws + L.order), &pos, &ids, status, stream)) return rc;
         order = (const int32_t *)(ws + L.order);
     }
-    const GroupedPositions G = grouped_positions_view(order, N, d.tok_rows);
+    const GroupedPositions G = grouped_positions_view(order, N, A.rows);
     A.counts = G.counts; A.starts = G.starts; A.pos_sorted = G.pos_sorted; A.id_sorted = G.id_sorted;
     A.canon = (int32_t *)(ws + L.canon);
     A.part = (float *)(ws + L.part);
@@ -437,17 +442,62 @@ int launch_value_embeds_bwd(const MotValueEmbedsDesc &d, const MotValueEmbedsGra
             if (int rc = ensure_max_dyn_lds((const void *)ve_canon_sort_kernel, lds_ok, "ve_canon_sort_kernel")) return rc;
         hipLaunchKernelGGL(ve_canon_sort_kernel, dim3(kVeSortBlocks), dim3(kVeSortThreads), lds, stream, A, cap);
     }
-    if (int rc = check_launch("value_embeds canon kernels")) return rc;
-    const dim3 sg((unsigned)((L.slices + kWaves - 1) / kWaves), (unsigned)(A.nslot * A.nck));
-    const dim3 rg((unsigned)((d.tok_rows + kVeRowIds - 1) / kVeRowIds), (unsigned)(A.nslot * A.nck));
-    if (bf) {
-        hipLaunchKernelGGL(ve_bwd_slices_kernel<__bf16>, sg, dim3(kThreads), 0, stream, A);
-        hipLaunchKernelGGL(ve_bwd_rows_kernel<__bf16>, rg, dim3(kThreads), 0, stream, A);
-    } else {
-        hipLaunchKernelGGL(ve_bwd_slices_kernel<float>, sg, dim3(kThreads), 0, stream, A);
-        hipLaunchKernelGGL(ve_bwd_rows_kernel<float>, rg, dim3(kThreads), 0, stream, A);
-    }
+    return check_launch("value_embeds canon kernels");
+}
+
+template <typename G, typename T>
+static int ve_launch_sums(const VeBwdArgs &A, int64_t slices, hipStream_t stream) {
+    const dim3 sg((unsigned)((slices + kWaves - 1) / kWaves), (unsigned)(A.nslot * A.nck));
+    const dim3 rg((unsigned)(((int64_t)A.rows + kVeRowIds - 1) / kVeRowIds), (unsigned)(A.nslot * A.nck));
+    hipLaunchKernelGGL((ve_bwd_slices_kernel<G, T>), sg, dim3(kThreads), 0, stream, A);
+    hipLaunchKernelGGL(ve_bwd_rows_kernel<T>, rg, dim3(kThreads), 0, stream, A);
     return check_launch("value_embeds backward kernels");
+}
+
+int launch_value_embeds_bwd(const MotValueEmbedsDesc &d, const MotValueEmbedsGrads &gr, hipStream_t stream) {
+    const bool bf = d.dtype == MOT_BF16;
+    VeBwdArgs A{};
+    A.N = d.n_tokens; A.rows = (int)d.tok_rows; A.D = A.g_ld = d.dim;
+    A.nck = (d.dim / (bf ? 8 : 4) + 63) / 64;
+    for (int j = 0; j < d.n_tables; ++j) {
+        if (!gr.grad_outs[j]) continue;
+        A.g[A.nslot] = gr.grad_outs[j];
+        A.d[A.nslot++] = gr.d_tables[j];
+    }
+    if (!A.nslot) return MOT_OK;
+    const VeLayout L = value_embeds_layout(d);
+    if (int rc = ve_order_and_canon(A, L, d.tokens, gr.token_order, (char *)d.workspace, d.status, stream)) return rc;
+    return bf ? ve_launch_sums<__bf16, __bf16>(A, L.slices, stream) : ve_launch_sums<float, float>(A, L.slices, stream);
+}
+
+// ------------------------------------------------------------------------------------------ one table from fp32 rows (mot_valuemix.hip)
+// The same order, canon, slices and rows kernels for ONE table of `dtype` whose gradient rows are fp32 with a row stride of g_ld
+// (a column block of du = dy W): d_table[r, :] = round(sum over the positions of id r of g[n, 0:dim]), written once, +0 where absent.
+// `prepare` makes the order (unless the caller brings one) and the canonical positions; a later slot of the same tokens passes
+// false and reuses what the workspace holds.
+static MotValueEmbedsDesc token_sums_desc(int64_t n, int64_t rows, int dim, int dtype) {
+    MotValueEmbedsDesc d{};
+    d.dtype = dtype; d.n_tokens = n; d.tok_rows = rows; d.dim = dim; d.n_tables = 1;
+    return d;
+}
+size_t token_sums_ws_bytes(int64_t n, int64_t rows, int dim, int dtype) { return n ? value_embeds_layout(token_sums_desc(n, rows, dim, dtype)).total : 0; }
+int launch_token_sums_f32(const int32_t *tokens, int64_t n, int64_t rows, int dim, int dtype, const float *g, int g_ld, void *d_table,
+                          const int32_t *order, bool prepare, char *ws, uint32_t *status, hipStream_t stream) {
+    const bool bf = dtype == MOT_BF16;
+    const VeLayout L = value_embeds_layout(token_sums_desc(n, rows, dim, dtype));
+    VeBwdArgs A{};
+    A.N = n; A.rows = (int)rows; A.D = dim; A.g_ld = g_ld;
+    A.nck = (dim / (bf ? 8 : 4) + 63) / 64;
+    A.g[0] = g; A.d[0] = d_table; A.nslot = 1;
+    if (prepare) {
+        if (int rc = ve_order_and_canon(A, L, tokens, order, ws, status, stream)) return rc;
+    } else {
+        const GroupedPositions G = grouped_positions_view(order ? order : (const int32_t *)(ws + L.order), n, rows);
+        A.counts = G.counts; A.starts = G.starts; A.pos_sorted = G.pos_sorted; A.id_sorted = G.id_sorted;
+        A.canon = (int32_t *)(ws + L.canon);
+        A.part = (float *)(ws + L.part);
+    }
+    return bf ? ve_launch_sums<float, __bf16>(A, L.slices, stream) : ve_launch_sums<float, float>(A, L.slices, stream);
 }
 
 }  // namespace mot

@@ -1586,3 +1586,211 @@ def value_embeds(tokens: torch.Tensor, tables) -> tuple:
     if torch.is_grad_enabled() and any(t.requires_grad for t in tables):
         return tuple(_ValueEmbedsFn.apply(tokens, *tables))
     return _value_embeds_fwd(tokens, tables)
+
+
+# ------------------------------------------------------------------------------------------------
+# mixture-of-tokenizers value embeddings (modded-nanogpt/runs/9_mot-in_mot-valemb.py:225-235, 252-254, 310-313; runs 3 and 6):
+# ve_j = norm(W_j . cat(Vt_j[tok], Vb_j[id_0], ..., Vb_j[id_{bpt-1}])) for up to four slots over one token and one id stream
+# ------------------------------------------------------------------------------------------------
+def _value_mix_desc(tokens, tok_tables, byte_tables, weights, bpt, norm_out, eps, what):
+    """The descriptor's problem part, checked: tokens (B, T) int32 contiguous; per slot a (tok_rows, token_dim) table, a
+    (byte_rows, byte_dim) table and an (out_dim, token_dim + bpt*byte_dim) weight, all of one dtype and of one shape per kind."""
+    tt, bt, ws = list(tok_tables), list(byte_tables), list(weights)
+    if not (len(tt) == len(bt) == len(ws)):
+        raise ValueError(f"{what}: {len(tt)} token tables, {len(bt)} byte tables and {len(ws)} weights: one of each per slot")
+    if not 1 <= len(tt) <= capi.VALUE_MIX_MAX_SLOTS:
+        raise ValueError(f"{what}: {len(tt)} slots, 1..{capi.VALUE_MIX_MAX_SLOTS} are built")
+    dt = tt[0].dtype
+    for kind, ts in (("token table", tt), ("byte table", bt), ("weight", ws)):
+        for j, t in enumerate(ts):
+            if t.dtype != dt:
+                raise TypeError(f"{what}: {kind} {j} is {t.dtype} but token table 0 is {dt}: all tensors share one dtype")
+            if t.ndim != 2 or t.shape != ts[0].shape:
+                raise ValueError(f"{what}: {kind} {j} must be 2-D of shape {tuple(ts[0].shape)}, got {tuple(t.shape)}")
+    capi.dtype_code(dt)
+    Dt, Db, Do = tt[0].shape[1], bt[0].shape[1], ws[0].shape[0]
+    if ws[0].shape[1] != Dt + int(bpt) * Db:
+        raise ValueError(f"{what}: weights must be (out_dim, token_dim + bpt*byte_dim) = (*, {Dt} + {int(bpt)}*{Db}), got {tuple(ws[0].shape)}")
+    if tokens.ndim not in (1, 2):
+        raise ValueError(f"{what}: tokens must be (B, T) or (T,)")
+    t2 = tokens if tokens.ndim == 2 else tokens[None]
+    tok = t2.to(torch.int32) if t2.dtype != torch.int32 else t2
+    tok = tok if tok.is_contiguous() else tok.contiguous()
+    tt, bt, ws = ([_table(t, f"{what}: {k} {j}") for j, t in enumerate(ts)] for k, ts in (("token table", tt), ("byte table", bt), ("weight", ws)))
+    d = capi.MotValueMixDesc()
+    d.struct_size = C.sizeof(capi.MotValueMixDesc)
+    d.dtype = capi.dtype_code(dt)
+    d.n_rows, d.tokens_per_row, d.bpt = tok.shape[0], tok.shape[1], int(bpt)
+    d.tokens = capi.ptr(tok)
+    d.tok_rows, d.byte_rows, d.token_dim, d.byte_dim, d.out_dim, d.n_slots = tt[0].shape[0], bt[0].shape[0], Dt, Db, Do, len(tt)
+    d.norm_out, d.eps = int(bool(norm_out)), float(eps or 0.0)
+    for j in range(len(tt)):
+        d.slot[j].tok_table, d.slot[j].byte_table, d.slot[j].weight = capi.ptr(tt[j]), capi.ptr(bt[j]), capi.ptr(ws[j])
+    return d, tok, [tok, tt, bt, ws]
+
+
+def _value_mix_ids(d, ids, bpt, keep, what):
+    ia = _contig(ids, torch.int64, "ids")
+    if ia.numel() != d.n_rows * d.tokens_per_row * bpt:
+        raise ValueError(f"{what}: byte ids must hold bytes_per_token ids per token, in per-token order (.., T*bpt)")
+    keep.append(ia)
+    d.id_source, d.ids = capi.IDS_GIVEN, capi.ptr(ia)
+    return ia
+
+
+@torch.compiler.disable
+def _value_mix_fwd(tokens, tok_tables, byte_tables, weights, *, bpt, ids=None, ttb=None, pull=None, pad_byte=456, eot_byte=457, norm_out=True,
+                   eps=None, save=False):
+    """One mot_value_mix_fwd call.  Returns (outs, ids_used, row_rnorms): with `save` the ids the tables were read with (the given
+    ones, or those made from `ttb`) and each slot's fp32 row factors, which the backward wants; (outs, None, None) otherwise."""
+    dev = capi.require_device(tokens, *tok_tables, *byte_tables, *weights, ids, ttb)
+    d, tok, keep = _value_mix_desc(tokens, tok_tables, byte_tables, weights, bpt, norm_out, eps, "value_mix")
+    B, T = tok.shape
+    outs = tuple(torch.empty(tuple(tokens.shape) + (d.out_dim,), dtype=tok_tables[0].dtype, device=dev) for _ in range(d.n_slots))
+    ids_used = None
+    if ttb is not None:
+        tab = _int_table(ttb, "value_mix")
+        if tab.shape[1] != bpt:
+            raise ValueError(f"ttb has {tab.shape[1]} slots per token, bpt={bpt}")
+        keep.append(tab)
+        d.id_source, d.pull_dir = capi.IDS_FROM_TTB, _PULLS[pull]
+        d.ttb, d.ttb_rows, d.ttb_elem_bytes = capi.ptr(tab), tab.shape[0], tab.element_size()
+        if save:
+            ids_used = torch.empty((B, T * bpt), dtype=torch.int64, device=dev)
+            d.out_ids = capi.ptr(ids_used)
+    else:
+        if ids is None:
+            raise ValueError("either ttb or ids must be given")
+        ids_used = _value_mix_ids(d, ids, bpt, keep, "value_mix")
+    d.pad_byte, d.eot_byte = int(pad_byte), int(eot_byte)
+    rns = None
+    if save and norm_out:
+        rns = tuple(torch.empty((B, T), dtype=torch.float32, device=dev) for _ in range(d.n_slots))
+    if B * T == 0:   # an empty batch: nothing to launch
+        return outs, ids_used, rns
+    for j, o in enumerate(outs):
+        d.slot[j].out = capi.ptr(o)
+        if rns is not None:
+            d.slot[j].out_row_rnorm = capi.ptr(rns[j])
+    d.status = capi.ptr(capi.status_word(dev))
+    ws = _workspace(dev, capi.lib.mot_value_mix_workspace_bytes(C.byref(d), 0))
+    if ws is not None:
+        d.workspace, d.workspace_bytes = capi.ptr(ws), ws.numel()
+    capi.check(capi.lib.mot_value_mix_fwd(C.byref(d), capi.stream_of(dev)))
+    capi.after_call(dev)
+    return outs, (ids_used if save else None), rns
+
+
+@torch.compiler.disable
+def value_mix_backward(grad_outs, tokens, tok_tables, byte_tables, weights, *, bpt, ids, norm_out=True, eps=None, outs=None, row_rnorms=None,
+                       token_order=None) -> list:
+    """One call of mot_value_mix_bwd.  `grad_outs` holds one upstream gradient ``tokens.shape + (out_dim,)`` or None per slot; a
+    slot whose entry is None is skipped and gets None back.  Returns per slot a dict {tok_table, byte_table, weight}: the token
+    table's gradient in the TABLES' dtype, every element written exactly once by the call (fp32 sums rounded once, +0 rows for
+    absent ids, the same bits on every run, with or without `token_order`), the byte table's and the weight's as fresh fp32
+    tensors (float atomics).  With norm_out the call reads the forward's outputs `outs` and their `row_rnorms`.  `ids` are the byte
+    ids the forward used, `token_order` what :func:`token_order` returned for these tokens and the token tables' height."""
+    grad_outs = list(grad_outs)
+    dev = capi.require_device(tokens, *tok_tables, *byte_tables, *weights, ids, token_order, *[g for g in grad_outs if g is not None])
+    d, tok, keep = _value_mix_desc(tokens, tok_tables, byte_tables, weights, bpt, norm_out, eps, "value_mix_backward")
+    if len(grad_outs) != d.n_slots:
+        raise ValueError(f"value_mix_backward: {len(grad_outs)} gradients for {d.n_slots} slots")
+    _value_mix_ids(d, ids, bpt, keep, "value_mix_backward")
+    n, dt = tok.numel(), tok_tables[0].dtype
+    if norm_out and (outs is None or row_rnorms is None) and any(g is not None for g in grad_outs):
+        raise ValueError("value_mix_backward with norm_out needs the forward's outputs and row_rnorms")
+    gr = capi.MotValueMixGrads()
+    gr.struct_size = C.sizeof(capi.MotValueMixGrads)
+    res = []
+    for j, g in enumerate(grad_outs):
+        if g is None:
+            res.append(None)
+            continue
+        gc = _contig(g, dt, f"grad_outs[{j}]")
+        if gc.numel() != n * d.out_dim:
+            raise ValueError(f"grad_outs[{j}] must be tokens.shape + ({d.out_dim},), got {tuple(g.shape)}")
+        keep.append(gc)
+        r = {"tok_table": (torch.empty if n else torch.zeros)((d.tok_rows, d.token_dim), dtype=dt, device=dev),   # written once by the call
+             "byte_table": torch.zeros((d.byte_rows, d.byte_dim), dtype=torch.float32, device=dev),
+             "weight": torch.zeros((d.out_dim, d.token_dim + bpt * d.byte_dim), dtype=torch.float32, device=dev)}
+        res.append(r)
+        gr.slot[j].grad_out, gr.slot[j].d_tok, gr.slot[j].d_byte, gr.slot[j].d_weight = capi.ptr(gc), capi.ptr(r["tok_table"]), capi.ptr(r["byte_table"]), capi.ptr(r["weight"])
+        if norm_out:
+            xo = _contig(outs[j], dt, f"outs[{j}]")
+            rn = _contig(row_rnorms[j], torch.float32, f"row_rnorms[{j}]")
+            if xo.numel() != n * d.out_dim or rn.numel() != n:
+                raise ValueError(f"outs[{j}] / row_rnorms[{j}] are not the forward's")
+            keep += [xo, rn]
+            d.slot[j].out, d.slot[j].out_row_rnorm = capi.ptr(xo), capi.ptr(rn)
+    if n == 0 or all(g is None for g in grad_outs):
+        return res
+    if token_order is not None:
+        need = capi.lib.mot_token_order_ints(n, d.tok_rows)
+        if token_order.dtype != torch.int32 or token_order.numel() != need or not token_order.is_contiguous():
+            raise ValueError(f"token_order must be the contiguous int32[{need}] tensor token_order(tokens, {d.tok_rows}) returned")
+        gr.token_order = capi.ptr(token_order)
+    d.status = capi.ptr(capi.status_word(dev))
+    ws = _workspace(dev, capi.lib.mot_value_mix_workspace_bytes(C.byref(d), 1))
+    if ws is not None:
+        d.workspace, d.workspace_bytes = capi.ptr(ws), ws.numel()
+    capi.check(capi.lib.mot_value_mix_bwd(C.byref(d), C.byref(gr), capi.stream_of(dev)))
+    capi.after_call(dev)
+    return res
+
+
+class _ValueMixFn(torch.autograd.Function):
+    """Autograd node of value_mix: one mot_value_mix_fwd call forward, one mot_value_mix_bwd call backward for every slot's two
+    tables and weight.  Saved: the tokens, the byte ids, the parameters and, with norm_out, the outputs and 4 bytes per token and
+    slot of row factors; u is gathered again.  The token order comes from the cache the fused front-end uses."""
+
+    @staticmethod
+    def forward(ctx, tokens, kw, *params):
+        n = len(params) // 3
+        tt, bt, ws = params[:n], params[n:2 * n], params[2 * n:]
+        outs, ids, rns = _value_mix_fwd(tokens, [t.detach() for t in tt], [t.detach() for t in bt], [t.detach() for t in ws], save=True, **kw)
+        ctx.order = _token_orders.get(tokens, tt[0].shape[0]) if _HOIST_SORT and tokens.numel() else None
+        ctx.n, ctx.normed = n, rns is not None
+        ctx.kw = dict(bpt=kw["bpt"], norm_out=kw.get("norm_out", True), eps=kw.get("eps"))
+        ctx.save_for_backward(tokens, ids, *params, *(outs if rns is not None else ()), *(rns or ()))
+        ctx.set_materialize_grads(False)   # an output nothing depends on arrives as None and its slot is skipped
+        return outs
+
+    @staticmethod
+    def backward(ctx, *grads):
+        n = ctx.n
+        tokens, ids, *rest = ctx.saved_tensors
+        tt, bt, ws = rest[:n], rest[n:2 * n], rest[2 * n:3 * n]
+        outs, rns = (rest[3 * n:4 * n], rest[4 * n:5 * n]) if ctx.normed else (None, None)
+        gs = [g if any(ctx.needs_input_grad[2 + k * n + j] for k in range(3)) else None for j, g in enumerate(grads[:n])]
+        if all(g is None for g in gs):
+            return (None,) * (2 + 3 * n)
+        order = None
+        if ctx.order is not None:
+            order, ev = ctx.order
+            cur = torch.cuda.current_stream(tokens.device)
+            if ev is not None:
+                cur.wait_event(ev)
+            order.record_stream(cur)
+        res = value_mix_backward(gs, tokens, [t.detach() for t in tt], [t.detach() for t in bt], [t.detach() for t in ws], ids=ids,
+                                 outs=None if outs is None else [o.detach() for o in outs], row_rnorms=rns, token_order=order, **ctx.kw)
+        pick = lambda k, ps: tuple(None if r is None else r[k].to(p.dtype) for r, p in zip(res, ps))   # bf16: the fp32 sums rounded once
+        return (None, None, *pick("tok_table", tt), *pick("byte_table", bt), *pick("weight", ws))
+
+
+def value_mix(tokens: torch.Tensor, tok_tables, byte_tables, weights, *, bpt: int, ids: torch.Tensor | None = None, ttb: torch.Tensor | None = None,
+              pull: str | None = None, pad_byte: int = 456, eot_byte: int = 457, norm_out: bool = True, eps: float | None = None) -> tuple:
+    """The mixture-of-tokenizers value embeddings of modded-nanogpt/runs/9_mot-in_mot-valemb.py:310-313 (runs 3 and 6 alike):
+    for each of the 1..4 slots j, ``ve_j = norm(cat(tok_tables[j][tokens], byte_tables[j][ids[:, 0]], ..., byte_tables[j][ids[:,
+    bpt-1]]) @ weights[j].T)`` with weights[j] (out_dim, token_dim + bpt*byte_dim) in nn.Linear layout, no bias; float32 or
+    bfloat16 throughout (bf16: fp32 sums, rounded where the reference's bf16 run rounds: F.linear's result, then the normalised
+    row).  tokens (B, T) or (T,); the byte ids are in per-token order (.., T*bpt), given as `ids` (int64) or made once for all
+    slots from the token->byte table `ttb` (+ `pull` = "left" | "right" | None) inside the call.  `eps` None is the float32 epsilon
+    for both dtypes.  Returns a tuple of ``tokens.shape + (out_dim,)`` tensors through ONE autograd node: its backward is one call
+    for all slots over one token order, and every token table's gradient is written once, in the table's dtype."""
+    tt, bt, ws = list(tok_tables), list(byte_tables), list(weights)
+    capi.require_device(tokens, *tt, *bt, *ws, ids, ttb)
+    kw = dict(bpt=bpt, ids=ids, ttb=ttb, pull=pull, pad_byte=pad_byte, eot_byte=eot_byte, norm_out=norm_out, eps=eps)
+    if torch.is_grad_enabled() and any(p.requires_grad for p in (*tt, *bt, *ws)):
+        _value_mix_desc(tokens, tt, bt, ws, bpt, norm_out, eps, "value_mix")   # shape and dtype errors before the node exists
+        return tuple(_ValueMixFn.apply(tokens, kw, *tt, *bt, *ws))
+    return _value_mix_fwd(tokens, tt, bt, ws, **kw)[0]

@@ -800,6 +800,47 @@ class ValueEmbeds(nn.ModuleList):
         return list(F_mot.value_embeds(tokens, [_f32(e.weight, "value table") for e in self]))
 
 
+class MotValueEmbeds(nn.Module):
+    """The mixture-of-tokenizers value embeddings of runs/9_mot-in_mot-valemb.py (parameters at 252-254, call site 310-313,
+    mixin_bytes 225-235; runs 3 and 6 alike): ``ve_j = norm(F.linear(cat(value_embeds_toks[j](tok), value_embeds_bytes[j](bytes)),
+    value_byte_mixin_weights[j]))``, one forward and one backward call of the library for all n of them.  The attribute names, and
+    so the state-dict keys, are the runs': ``value_embeds_toks.{j}.weight``, ``value_embeds_bytes.{j}.weight`` and
+    ``value_byte_mixin_weights.{j}``.  The runs allocate the byte value tables with token_vocab_size rows although only byte ids
+    index them; the library sees the leading byte_vocab_size rows as a view and autograd pads the gradient with zeros.  The
+    weights are (out_dim, token_dim + bytes_per_token * byte_dim), out_dim = token_dim unless given, initialised as the runs'
+    init_linear does (uniform, bound sqrt(3) * 0.5 / sqrt(K))."""
+
+    def __init__(self, token_vocab_size: int, token_dim: int, byte_dim: int, bytes_per_token: int = 16, n: int = 3, byte_vocab_size: int = 458,
+                 out_dim: int | None = None, ttb=None, pad_byte: int = 456, eot_byte: int = 457):
+        super().__init__()
+        if not 1 <= n <= 4:
+            raise ValueError(f"MotValueEmbeds: n = {n}, one call serves 1..4 slots")
+        if byte_vocab_size > token_vocab_size:
+            raise ValueError(f"MotValueEmbeds: byte_vocab_size {byte_vocab_size} > token_vocab_size {token_vocab_size}, the rows of the byte value tables")
+        out_dim = token_dim if out_dim is None else out_dim
+        K = token_dim + bytes_per_token * byte_dim
+        bound = (3 ** 0.5) * 0.5 * (K ** -0.5)
+        self.value_embeds_toks = nn.ModuleList([nn.Embedding(token_vocab_size, token_dim) for _ in range(n)])
+        self.value_embeds_bytes = nn.ModuleList([nn.Embedding(token_vocab_size, byte_dim) for _ in range(n)])
+        self.value_byte_mixin_weights = nn.ParameterList([nn.Parameter(torch.empty(out_dim, K).uniform_(-bound, bound)) for _ in range(n)])
+        self.bpt, self.pad_byte, self.eot_byte, self.byte_vocab_size, self.out_dim = bytes_per_token, pad_byte, eot_byte, byte_vocab_size, out_dim
+        self.register_buffer("ttb", _table_of(ttb).clone() if ttb is not None else None, persistent=False)
+
+    def forward(self, token_inputs: Tensor, byte_inputs: Tensor | None = None) -> list[Tensor]:
+        """token_inputs (T,) or (B, T); byte_inputs (.., T*bpt) per-token-ordered byte ids, or None to produce them in-kernel from
+        the attached token->byte table.  Returns [ve_0, ..., ve_{n-1}], each ``token_inputs.shape + (out_dim,)``."""
+        kw = {}
+        if byte_inputs is None:
+            if self.ttb is None:
+                raise ValueError("MotValueEmbeds: pass byte_inputs or construct the module with a token->byte table (ttb)")
+            kw.update(ttb=self.ttb, pull="left", pad_byte=self.pad_byte, eot_byte=self.eot_byte)
+        else:
+            kw.update(ids=byte_inputs.to(torch.int64).reshape(1 if token_inputs.ndim == 1 else token_inputs.shape[0], -1))
+        return list(F_mot.value_mix(token_inputs, [_f32(e.weight, "token value table") for e in self.value_embeds_toks],
+                                    [_f32(e.weight, "byte value table")[:self.byte_vocab_size] for e in self.value_embeds_bytes],
+                                    [_f32(w, "mixin weight") for w in self.value_byte_mixin_weights], bpt=self.bpt, **kw))
+
+
 # ------------------------------------------------------------------------------------------------
 # Llama character mixer (inference/inference.py): BASELINE config 5's front-end
 # ------------------------------------------------------------------------------------------------
