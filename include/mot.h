@@ -859,6 +859,97 @@ size_t mot_value_mix_workspace_bytes(const MotValueMixDesc *desc /* host */, int
 int mot_value_mix_fwd(const MotValueMixDesc *desc /* host */, mot_stream_t stream);
 int mot_value_mix_bwd(const MotValueMixDesc *fwd /* host */, const MotValueMixGrads *grads /* host */, mot_stream_t stream);
 
+/*
+ * The three input streams of modded-nanogpt/runs/71081_mot-in_toks-valemb.py:302-304, 315 in ONE call (every block of that run
+ * reads x, x0t and x0b: :209-210, :319).  Per token n of row-major (B, T), with model_dim = bpt * byte_dim:
+ *   x0t[n]                     = r_t tok_table[tokens[n]],         r_t = rsqrt(mean over model_dim of the row^2 + eps)
+ *   x0b[n, k*byte_dim + c]     = r_k byte_table[ids[n, k], c],     r_k = rsqrt(mean over byte_dim of THAT byte row^2 + eps)
+ *   x[n]                       = *scale_tok x0t[n] + *scale_byte x0b[n]                      (no outer norm)
+ * Each of the three outputs may be NULL (not wanted); at least one is non-NULL.  The ids are in per-token byte order [B, T*bpt], given
+ * (MOT_IDS_GIVEN) or made inside the kernel from the token->byte table (MOT_IDS_FROM_TTB: tokens_to_bytes, then pull_dir), with the
+ * int64 id outputs, counters and status word of MotEmbedMixDesc; an id outside its table reads row 0 and raises MOT_STATUS_TOKEN_OOR /
+ * MOT_STATUS_BYTE_OOR.  One dtype for tables, outputs and output gradients.  Arithmetic is fp32; MOT_BF16 is rounded where the
+ * reference's eager bf16 run rounds: x0t = bf16(r_t a), x0b = bf16(r_k u), x = bf16(bf16(s_t x0t) + bf16(s_b x0b)) from the rounded
+ * x0t and x0b.  scale_tok / scale_byte are DEVICE pointers to one fp32 each (the run's scalars[-1] / scalars[-2]) and are never read
+ * on the host.  eps <= 0 means FLT_EPSILON for BOTH dtypes, as in MotByteFcMixDesc.
+ * Refused with MOT_EUNSUPPORTED before any launch: model_dim != bpt * byte_dim, byte_dim not a multiple of the 16-byte vector (4 fp32
+ * / 8 bf16 elements), model_dim above 2048, bpt outside 1..MOT_MAX_BPT, an unknown dtype, all three outputs NULL.  A wrong
+ * struct_size or a null required pointer is MOT_EINVAL.  An empty batch returns MOT_OK.  Every call is asynchronous on `stream`,
+ * allocates nothing, reads no environment variable and never synchronises; all zeroing is done by kernels, so forward + backward
+ * capture into a hipGraph.  The forward's workspace holds the byte rows' rms factors (byte_rows fp32).
+ */
+typedef struct MotSplitX0Desc {
+    uint32_t struct_size;   /* sizeof(MotSplitX0Desc), checked */
+    int32_t dtype;          /* MOT_F32 | MOT_BF16: tables, outputs and output gradients */
+    int64_t n_rows;         /* B */
+    int64_t tokens_per_row; /* T */
+    int32_t bpt;            /* byte slots per token */
+    int32_t model_dim;      /* columns of tok_table and of every output: bpt * byte_dim */
+    int32_t byte_dim;
+    int32_t id_source;      /* MOT_IDS_FROM_TTB | MOT_IDS_GIVEN */
+    const int32_t *tokens;  /* [B, T] */
+    const void *ttb;        /* [ttb_rows, bpt]      (FROM_TTB) */
+    int64_t ttb_rows;
+    int32_t ttb_elem_bytes; /* 2 | 4                (FROM_TTB) */
+    int32_t pull_dir;       /* MotPullDir           (FROM_TTB) */
+    int32_t pad_byte, eot_byte;
+    const int64_t *ids;     /* [B, T*bpt]           (GIVEN) */
+    const void *tok_table;  /* [tok_rows, model_dim] */
+    int64_t tok_rows;
+    const void *byte_table; /* [byte_rows, byte_dim] */
+    int64_t byte_rows;
+    const float *scale_tok;  /* device, one fp32: scalars[-1] */
+    const float *scale_byte; /* device, one fp32: scalars[-2] */
+    float eps;              /* <= 0 -> FLT_EPSILON, both dtypes */
+    uint32_t reserved0;     /* must be 0 */
+    void *out_x0t;          /* [B, T, model_dim] or NULL; ignored by the backward, like the next two */
+    void *out_x0b;
+    void *out_x;
+    int64_t *out_ids_padded; /* optional [B, T*bpt] (FROM_TTB) */
+    int64_t *out_ids_pulled; /* optional [B, T*bpt] (FROM_TTB): with pull_dir the ids the byte table was read with, what the backward wants */
+    int64_t *counters;      /* optional int64[4], as MotEmbedMixDesc.counters */
+    uint32_t *status;       /* optional device word, see MOT_STATUS_* */
+    void *workspace;        /* >= mot_splitx_workspace_bytes(desc, backward), 16-byte aligned */
+    size_t workspace_bytes;
+} MotSplitX0Desc;
+
+/*
+ * Backward: `fwd` is the forward's descriptor with id_source == MOT_IDS_GIVEN (the ids the forward used or wrote); the outputs are
+ * not read, everything is computed again from the tables.  With h_t = grad_x0t + s_t grad_x and h_b = grad_x0b + s_b grad_x (a NULL
+ * gradient is zero; at least one is non-NULL), y_k = r_k u_k:
+ *   d a_n     = r_t (h_t - x0t (h_t . x0t) / model_dim)
+ *   d u_{n,k} = r_k (h_b[k] - y_k (h_b[k] . y_k) / byte_dim)
+ *   d_tok_table[r, :]  = round_to_dtype(fp32 sum of d a_n over the positions n with tokens[n] == r),  +0 where r is absent
+ *   d_byte_table[ids[n, k], :] += d u_{n,k}
+ *   *d_scale_tok = sum_n grad_x[n] . x0t[n],   *d_scale_byte = sum_n grad_x[n] . x0b[n]
+ * Each of the four results may be NULL (not wanted).  d_tok_table is WRITTEN exactly once, in the tables' dtype, with plain stores,
+ * under the contract of mot_value_embeds_bwd (the caller zeroes nothing, the same bits on every run, with or without
+ * `token_order`); tok_rows >= 2^21 - 1 (the token order's limit) is refused with MOT_EUNSUPPORTED when it is asked for.  d_byte_table
+ * is FP32 for both dtypes and ACCUMULATED into (+=) through the LDS fixed-point sums of mot_byte_cat_bwd.  The two scalars are
+ * WRITTEN: per-workgroup partials over fixed ranges of 16 positions, added in order by one workgroup -- the same bits on every run.
+ * The workspace holds d a of the whole batch (N x model_dim fp32), d u of one slab of 16 384 positions and the token order.
+ */
+typedef struct MotSplitX0Grads {
+    uint32_t struct_size; /* sizeof(MotSplitX0Grads) */
+    uint32_t reserved;
+    const void *grad_x0t; /* [B, T, model_dim] in dtype, or NULL */
+    const void *grad_x0b;
+    const void *grad_x;
+    void *d_tok_table;    /* [tok_rows, model_dim] in dtype, written once */
+    void *d_byte_table;   /* [byte_rows, byte_dim] fp32, += */
+    float *d_scale_tok;   /* one fp32, written */
+    float *d_scale_byte;  /* one fp32, written */
+    const int32_t *token_order; /* optional, as MotEmbedMixGrads.token_order */
+} MotSplitX0Grads;
+
+size_t mot_splitx_desc_size(void);
+/* 0 for a descriptor the call would refuse on its shape, dtype or id source.  The query sees no pointers: a call whose three outputs
+ * (or three gradients) are all NULL, or a backward that wants a token-table gradient at tok_rows >= 2^21 - 1, gets a size here and is
+ * refused by the call itself. */
+size_t mot_splitx_workspace_bytes(const MotSplitX0Desc *desc /* host */, int backward);
+int mot_splitx_fwd(const MotSplitX0Desc *desc /* host */, mot_stream_t stream);
+int mot_splitx_bwd(const MotSplitX0Desc *fwd /* host */, const MotSplitX0Grads *grads /* host */, mot_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

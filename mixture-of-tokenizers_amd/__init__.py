@@ -8,9 +8,10 @@ Python layer mirrors the reference's interfaces for this path and nothing else:
                   byte_self_attn = the sliding-window byte self-attention layer of the concat mixin;
                   byte_fc_mix = the linear-on-bytes mixin of run 71051; byte_cat = the bytes-only front-end and byte value embeddings
                   of runs 2, 4, 5, 6, 8; value_embeds = the token value embeddings of train_gpt.py:566/600 and the *_toks-valemb runs;
-                  value_mix = the mixture-of-tokenizers value embeddings of runs 3, 6, 9)
+                  value_mix = the mixture-of-tokenizers value embeddings of runs 3, 6, 9;
+                  split_x0 = run 71081's x0t, x0b and x in one call)
   modules         FlexibleEmbedding / ByteMixin* / CastedLinear (scaled-pre-train), DigitMixin* / GPTConfig
-                  (mathblations), SumFrontEnd / ConcatFrontEnd / ByteFcFrontEnd / BytesFrontEnd / ValueEmbeds / MotValueEmbeds (modded-nanogpt), FusedFrontEnd (tokens -> x in one launch)
+                  (mathblations), SumFrontEnd / ConcatFrontEnd / ByteFcFrontEnd / BytesFrontEnd / ValueEmbeds / MotValueEmbeds / SplitX0FrontEnd (modded-nanogpt), FusedFrontEnd (tokens -> x in one launch)
   loader          shard reader, rank slice, input/target shift (distributed_data_generator)
   grad_sync       GradBucket: one flat all-reduce for the front-end's gradients (train_gpt.py:1320-1321)
 
@@ -20,10 +21,10 @@ shim at the repo root maps that name onto this directory).
 from . import _capi
 from . import data_creation, functional, grad_sync, loader, modules
 from ._capi import build_info, check_status, set_debug_ids
-from .modules import ByteFcFrontEnd, BytesFrontEnd, ConcatFrontEnd, MotValueEmbeds, ValueEmbeds
-from .functional import byte_cat, byte_fc_mix, byte_head_loss, byte_self_attn, create_batch, embed_mix, embed_mix_plan, gather_rows, pull_bytes, tokens_to_bytes, value_embeds, value_mix
+from .modules import ByteFcFrontEnd, BytesFrontEnd, ConcatFrontEnd, MotValueEmbeds, SplitX0FrontEnd, ValueEmbeds
+from .functional import byte_cat, byte_fc_mix, byte_head_loss, byte_self_attn, create_batch, embed_mix, embed_mix_plan, gather_rows, pull_bytes, split_x0, tokens_to_bytes, value_embeds, value_mix
 
 __all__ = [
-    "build_info", "check_status", "set_debug_ids", "ByteFcFrontEnd", "BytesFrontEnd", "ConcatFrontEnd", "MotValueEmbeds", "ValueEmbeds", "data_creation", "functional", "grad_sync", "loader", "modules",
-    "byte_cat", "byte_fc_mix", "byte_head_loss", "byte_self_attn", "create_batch", "embed_mix", "embed_mix_plan", "gather_rows", "pull_bytes", "tokens_to_bytes", "value_embeds", "value_mix",
+    "build_info", "check_status", "set_debug_ids", "ByteFcFrontEnd", "BytesFrontEnd", "ConcatFrontEnd", "MotValueEmbeds", "SplitX0FrontEnd", "ValueEmbeds", "data_creation", "functional", "grad_sync", "loader", "modules",
+    "byte_cat", "byte_fc_mix", "byte_head_loss", "byte_self_attn", "create_batch", "embed_mix", "embed_mix_plan", "gather_rows", "pull_bytes", "split_x0", "tokens_to_bytes", "value_embeds", "value_mix",
 ]

@@ -63,6 +63,7 @@ EXPORTS = (
     "mot_byte_cat_desc_size", "mot_byte_cat_workspace_bytes", "mot_byte_cat_bwd_workspace_bytes", "mot_byte_cat_fwd", "mot_byte_cat_bwd",
     "mot_value_embeds_desc_size", "mot_value_embeds_bwd_workspace_bytes", "mot_value_embeds_fwd", "mot_value_embeds_bwd",
     "mot_value_mix_desc_size", "mot_value_mix_workspace_bytes", "mot_value_mix_fwd", "mot_value_mix_bwd",
+    "mot_splitx_desc_size", "mot_splitx_workspace_bytes", "mot_splitx_fwd", "mot_splitx_bwd",
 )
 SWA_NO_RESIDUAL, SWA_ONE_RESIDUAL, SWA_TWO_RESIDUAL = 0, 1, 2
 
@@ -264,6 +265,28 @@ class MotValueMixGrads(C.Structure):
                 ("token_order", C.c_void_p)]
 
 
+class MotSplitX0Desc(C.Structure):
+    """Mirror of struct MotSplitX0Desc (include/mot.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("dtype", C.c_int32), ("n_rows", C.c_int64), ("tokens_per_row", C.c_int64),
+        ("bpt", C.c_int32), ("model_dim", C.c_int32), ("byte_dim", C.c_int32), ("id_source", C.c_int32), ("tokens", C.c_void_p),
+        ("ttb", C.c_void_p), ("ttb_rows", C.c_int64), ("ttb_elem_bytes", C.c_int32), ("pull_dir", C.c_int32),
+        ("pad_byte", C.c_int32), ("eot_byte", C.c_int32), ("ids", C.c_void_p),
+        ("tok_table", C.c_void_p), ("tok_rows", C.c_int64), ("byte_table", C.c_void_p), ("byte_rows", C.c_int64),
+        ("scale_tok", C.c_void_p), ("scale_byte", C.c_void_p), ("eps", C.c_float), ("reserved0", C.c_uint32),
+        ("out_x0t", C.c_void_p), ("out_x0b", C.c_void_p), ("out_x", C.c_void_p),
+        ("out_ids_padded", C.c_void_p), ("out_ids_pulled", C.c_void_p), ("counters", C.c_void_p), ("status", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
+class MotSplitX0Grads(C.Structure):
+    """Mirror of struct MotSplitX0Grads (include/mot.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("grad_x0t", C.c_void_p), ("grad_x0b", C.c_void_p), ("grad_x", C.c_void_p),
+                ("d_tok_table", C.c_void_p), ("d_byte_table", C.c_void_p), ("d_scale_tok", C.c_void_p), ("d_scale_byte", C.c_void_p),
+                ("token_order", C.c_void_p)]
+
+
 def _load() -> C.CDLL:
     if not LIB_PATH.exists():
         raise ImportError(
@@ -348,6 +371,13 @@ def _load() -> C.CDLL:
     lib.mot_value_mix_fwd.restype = C.c_int
     lib.mot_value_mix_bwd.argtypes = [C.POINTER(MotValueMixDesc), C.POINTER(MotValueMixGrads), vp]
     lib.mot_value_mix_bwd.restype = C.c_int
+    lib.mot_splitx_desc_size.restype = C.c_size_t
+    lib.mot_splitx_workspace_bytes.restype = C.c_size_t
+    lib.mot_splitx_workspace_bytes.argtypes = [C.POINTER(MotSplitX0Desc), i32]
+    lib.mot_splitx_fwd.argtypes = [C.POINTER(MotSplitX0Desc), vp]
+    lib.mot_splitx_fwd.restype = C.c_int
+    lib.mot_splitx_bwd.argtypes = [C.POINTER(MotSplitX0Desc), C.POINTER(MotSplitX0Grads), vp]
+    lib.mot_splitx_bwd.restype = C.c_int
     for name in ("mot_tokens_to_bytes", "mot_pull_bytes", "mot_create_batch", "mot_char_matrix", "mot_gather_rows", "mot_embed_mix_fwd",
                  "mot_embed_mix_bwd"):
         getattr(lib, name).restype = C.c_int
@@ -371,6 +401,8 @@ def _load() -> C.CDLL:
         raise ImportError("MotValueEmbedsDesc layout mismatch between include/mot.h and _capi.py")
     if lib.mot_value_mix_desc_size() != C.sizeof(MotValueMixDesc):
         raise ImportError("MotValueMixDesc layout mismatch between include/mot.h and _capi.py")
+    if lib.mot_splitx_desc_size() != C.sizeof(MotSplitX0Desc):
+        raise ImportError("MotSplitX0Desc layout mismatch between include/mot.h and _capi.py")
     return lib
 
 

@@ -496,4 +496,20 @@ int mot_value_mix_bwd(const MotValueMixDesc *desc, const MotValueMixGrads *grads
     return launch_value_mix_bwd(*desc, *grads, (hipStream_t)stream);
 }
 
+size_t mot_splitx_desc_size(void) { return sizeof(MotSplitX0Desc); }
+
+size_t mot_splitx_workspace_bytes(const MotSplitX0Desc *desc, int backward) { return split_x0_workspace_bytes(desc, backward != 0); }
+
+int mot_splitx_fwd(const MotSplitX0Desc *desc, mot_stream_t stream) {
+    if (int rc = split_x0_check(desc, nullptr, false)) return rc;
+    if (desc->n_rows == 0 || desc->tokens_per_row == 0) return MOT_OK;
+    return launch_split_x0_fwd(*desc, (hipStream_t)stream);
+}
+
+int mot_splitx_bwd(const MotSplitX0Desc *desc, const MotSplitX0Grads *grads, mot_stream_t stream) {
+    if (int rc = split_x0_check(desc, grads, true)) return rc;
+    if (desc->n_rows == 0 || desc->tokens_per_row == 0) return MOT_OK;
+    return launch_split_x0_bwd(*desc, *grads, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -146,6 +146,11 @@ int value_mix_check(const MotValueMixDesc *d, const MotValueMixGrads *g, bool ba
 size_t value_mix_workspace_bytes(const MotValueMixDesc *d, bool backward);   // 0 for a descriptor the call would refuse
 int launch_value_mix_fwd(const MotValueMixDesc &d, hipStream_t stream);
 int launch_value_mix_bwd(const MotValueMixDesc &d, const MotValueMixGrads &g, hipStream_t stream);
+// the three input streams of run 71081 (mot_splitx0.hip): validation before any HIP call (g: backward only), then the launches
+int split_x0_check(const MotSplitX0Desc *d, const MotSplitX0Grads *g, bool backward);
+size_t split_x0_workspace_bytes(const MotSplitX0Desc *d, bool backward);   // 0 for a descriptor refused on its shape (the query sees no pointers)
+int launch_split_x0_fwd(const MotSplitX0Desc &d, hipStream_t stream);
+int launch_split_x0_bwd(const MotSplitX0Desc &d, const MotSplitX0Grads &g, hipStream_t stream);
 // the gather-GEMM of mot_concat16.hip for up to four (token table, byte table, W, out) sets over one token and id stream in ONE launch
 struct Concat16Slots { int n; const void *tok_table[4], *byte_table[4], *weight[4]; void *out[4]; float *row_rnorm[4]; };
 int launch_concat16_slots(const MotEmbedMixDesc &d, const Concat16Slots &S, const int32_t *tokens, const int64_t *ids, int64_t n, hipStream_t stream);

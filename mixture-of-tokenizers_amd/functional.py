@@ -1794,3 +1794,235 @@ def value_mix(tokens: torch.Tensor, tok_tables, byte_tables, weights, *, bpt: in
         _value_mix_desc(tokens, tt, bt, ws, bpt, norm_out, eps, "value_mix")   # shape and dtype errors before the node exists
         return tuple(_ValueMixFn.apply(tokens, kw, *tt, *bt, *ws))
     return _value_mix_fwd(tokens, tt, bt, ws, **kw)[0]
+
+
+# ------------------------------------------------------------------------------------------------
+# the three input streams of modded-nanogpt/runs/71081_mot-in_toks-valemb.py:302-304, 315:
+# x0t = norm(E_t[tok]), x0b = cat_k norm(E_b[id_k]), x = s_t x0t + s_b x0b, all from one call
+# ------------------------------------------------------------------------------------------------
+_SPLIT_X0_OUTS = ("x0t", "x0b", "x")
+
+
+def _split_x0_scalar(s, what):
+    """A one-element float32 tensor (0-dim, (1,), or a one-element slice of a longer parameter): the kernel reads it where it lives."""
+    if not isinstance(s, torch.Tensor) or s.numel() != 1:
+        raise ValueError(f"{what} must be a one-element tensor on the device (the run's scalars[-1] / scalars[-2]); the host never reads it")
+    if s.dtype != torch.float32:
+        raise TypeError(f"{what}: expected torch.float32, got {s.dtype}")
+    return s.reshape(1)   # a view of one element is always contiguous
+
+
+def _split_x0_desc(tokens, tok_table, byte_table, scale_tok, scale_byte, bpt, eps, what):
+    """The descriptor's problem part, checked: tokens (B, T) int32 contiguous, a (tok_rows, model_dim) and a (byte_rows, byte_dim)
+    table of one dtype, the two scalars.  What the library does not build (model_dim != bpt * byte_dim, ...) is left to its refusal."""
+    if tok_table.dtype != byte_table.dtype:
+        raise TypeError(f"{what}: the byte table is {byte_table.dtype} but the token table is {tok_table.dtype}: all tensors share one dtype")
+    capi.dtype_code(tok_table.dtype)
+    if tok_table.ndim != 2 or byte_table.ndim != 2:
+        raise ValueError(f"{what}: tables must be 2-D, got {tuple(tok_table.shape)} and {tuple(byte_table.shape)}")
+    if tokens.ndim not in (1, 2):
+        raise ValueError(f"{what}: tokens must be (B, T) or (T,)")
+    t2 = tokens if tokens.ndim == 2 else tokens[None]
+    tok = t2.to(torch.int32) if t2.dtype != torch.int32 else t2
+    tok = tok if tok.is_contiguous() else tok.contiguous()
+    tt, bt = _table(tok_table, f"{what}: token table"), _table(byte_table, f"{what}: byte table")
+    st, sb = _split_x0_scalar(scale_tok, f"{what}: scale_tok"), _split_x0_scalar(scale_byte, f"{what}: scale_byte")
+    d = capi.MotSplitX0Desc()
+    d.struct_size = C.sizeof(capi.MotSplitX0Desc)
+    d.dtype = capi.dtype_code(tt.dtype)
+    d.n_rows, d.tokens_per_row, d.bpt = tok.shape[0], tok.shape[1], int(bpt)
+    d.model_dim, d.byte_dim = tt.shape[1], bt.shape[1]
+    d.tokens, d.tok_table, d.tok_rows, d.byte_table, d.byte_rows = capi.ptr(tok), capi.ptr(tt), tt.shape[0], capi.ptr(bt), bt.shape[0]
+    d.scale_tok, d.scale_byte = capi.ptr(st), capi.ptr(sb)
+    d.eps = float(eps or 0.0)
+    return d, tok, [tok, tt, bt, st, sb]
+
+
+def _split_x0_ids(d, ids, bpt, keep, what):
+    ia = _contig(ids, torch.int64, "ids")
+    if ia.numel() != d.n_rows * d.tokens_per_row * bpt:
+        raise ValueError(f"{what}: byte ids must hold bytes_per_token ids per token, in per-token order (.., T*bpt)")
+    keep.append(ia)
+    d.id_source, d.ids = capi.IDS_GIVEN, capi.ptr(ia)
+    return ia
+
+
+def _split_x0_want(want):
+    want = tuple(want)
+    if not want or any(w not in _SPLIT_X0_OUTS for w in want) or len(set(want)) != len(want):
+        raise ValueError(f"split_x0: want must name one to three of {_SPLIT_X0_OUTS}, each once, got {want}")
+    return want
+
+
+@torch.compiler.disable
+def _split_x0_fwd(tokens, tok_table, byte_table, scale_tok, scale_byte, *, bpt, ids=None, ttb=None, pull="left", pad_byte=456, eot_byte=457,
+                  eps=None, want=_SPLIT_X0_OUTS, save=False, return_ids=False, counters=None):
+    """One mot_splitx_fwd call.  Returns ({name: tensor} for the wanted outputs, ids_used): with `save` the ids the byte table was read
+    with (the given ones, or those made from `ttb`), which the backward wants.  With `return_ids` (ids from `ttb` only) it returns
+    (outs, ids_padded, ids_pulled) instead, the int64 tensors the kernel wrote; `counters` is an int64[4] device tensor the kernel
+    adds its statistics to, as in embed_mix."""
+    dev = capi.require_device(tokens, tok_table, byte_table, scale_tok, scale_byte, ids, ttb)
+    want = _split_x0_want(want)
+    d, tok, keep = _split_x0_desc(tokens, tok_table, byte_table, scale_tok, scale_byte, bpt, eps, "split_x0")
+    B, T = tok.shape
+    outs = {w: torch.empty(tuple(tokens.shape) + (d.model_dim,), dtype=tok_table.dtype, device=dev) for w in want}
+    ids_used = None
+    if ttb is not None:
+        tab = _int_table(ttb, "split_x0")
+        if tab.shape[1] != bpt:
+            raise ValueError(f"ttb has {tab.shape[1]} slots per token, bpt={bpt}")
+        keep.append(tab)
+        d.id_source, d.pull_dir = capi.IDS_FROM_TTB, _PULLS[pull]
+        d.ttb, d.ttb_rows, d.ttb_elem_bytes = capi.ptr(tab), tab.shape[0], tab.element_size()
+        if save or return_ids:
+            ids_used = torch.empty((B, T * bpt), dtype=torch.int64, device=dev)
+            d.out_ids_pulled = capi.ptr(ids_used)   # without a pull the "pulled" ids are the table's rows
+        if return_ids:
+            ids_padded = torch.empty((B, T * bpt), dtype=torch.int64, device=dev)
+            d.out_ids_padded = capi.ptr(ids_padded)
+    else:
+        if ids is None:
+            raise ValueError("either ttb or ids must be given")
+        if return_ids:
+            raise ValueError("split_x0: return_ids needs the token->byte table (ttb)")
+        ids_used = _split_x0_ids(d, ids, bpt, keep, "split_x0")
+    d.pad_byte, d.eot_byte = int(pad_byte), int(eot_byte)
+    if counters is not None:
+        if counters.dtype != torch.int64 or counters.numel() < 4 or counters.device != dev:
+            raise ValueError("counters must be an int64[4] tensor on the inputs' device")
+        d.counters = capi.ptr(counters)
+    if B * T == 0:   # an empty batch: nothing to launch
+        return (outs, ids_padded, ids_used) if return_ids else (outs, ids_used)
+    d.out_x0t, d.out_x0b, d.out_x = (capi.ptr(outs.get(w)) for w in _SPLIT_X0_OUTS)
+    d.status = capi.ptr(capi.status_word(dev))
+    ws = _workspace(dev, capi.lib.mot_splitx_workspace_bytes(C.byref(d), 0))
+    if ws is not None:
+        d.workspace, d.workspace_bytes = capi.ptr(ws), ws.numel()
+    capi.check(capi.lib.mot_splitx_fwd(C.byref(d), capi.stream_of(dev)))
+    capi.after_call(dev)
+    if return_ids:
+        return outs, ids_padded, ids_used
+    return outs, (ids_used if save else None)
+
+
+@torch.compiler.disable
+def split_x0_backward(grad_x0t, grad_x0b, grad_x, tokens, tok_table, byte_table, scale_tok, scale_byte, *, bpt, ids, eps=None, token_order=None,
+                      want_grads=("tok_table", "byte_table", "scale_tok", "scale_byte"), out=None, into=None) -> dict:
+    """One call of mot_splitx_bwd.  Each of the three upstream gradients ``tokens.shape + (model_dim,)`` may be None (zero; it is
+    passed to the library as NULL), at least one is given.  Returns a dict with the entries named in `want_grads`:
+    "tok_table" in the TABLES' dtype, every element written exactly once by the call (fp32 sums in ascending position order rounded
+    once, +0 rows for absent ids, the same bits on every run, with or without `token_order`; `out` names a buffer to write it INTO,
+    whatever it held); "byte_table" fp32, accumulated (+=) into `into` or into a fresh zeroed tensor (LDS fixed-point sums flushed
+    with float atomics); "scale_tok" and "scale_byte" fp32 one-element tensors, written, the same bits on every run.  Nothing of the
+    forward is needed but the byte `ids` it used."""
+    gs = [grad_x0t, grad_x0b, grad_x]
+    dev = capi.require_device(tokens, tok_table, byte_table, scale_tok, scale_byte, ids, token_order, out, into, *[g for g in gs if g is not None])
+    if all(g is None for g in gs):
+        raise ValueError("split_x0_backward: grad_x0t, grad_x0b and grad_x are all None")
+    d, tok, keep = _split_x0_desc(tokens, tok_table, byte_table, scale_tok, scale_byte, bpt, eps, "split_x0_backward")
+    _split_x0_ids(d, ids, bpt, keep, "split_x0_backward")
+    n, dt = tok.numel(), tok_table.dtype
+    gr = capi.MotSplitX0Grads()
+    gr.struct_size = C.sizeof(capi.MotSplitX0Grads)
+    for name, g in zip(("grad_x0t", "grad_x0b", "grad_x"), gs):
+        if g is None:
+            continue
+        gc = _contig(g, dt, name)
+        if gc.numel() != n * d.model_dim:
+            raise ValueError(f"{name} must be tokens.shape + ({d.model_dim},), got {tuple(g.shape)}")
+        keep.append(gc)
+        setattr(gr, name, capi.ptr(gc))
+    res = {}
+    if "tok_table" in want_grads:
+        r = out
+        if r is None:
+            r = (torch.empty if n else torch.zeros)((d.tok_rows, d.model_dim), dtype=dt, device=dev)   # written once by the call
+        elif r.dtype != dt or tuple(r.shape) != (d.tok_rows, d.model_dim) or not r.is_contiguous():
+            raise ValueError(f"out must be a contiguous {dt} tensor of the token table's shape")
+        elif n == 0:
+            r.zero_()
+        res["tok_table"], gr.d_tok_table = r, capi.ptr(r)
+    if "byte_table" in want_grads:
+        r = into if into is not None else torch.zeros((d.byte_rows, d.byte_dim), dtype=torch.float32, device=dev)
+        if r.dtype != torch.float32 or tuple(r.shape) != (d.byte_rows, d.byte_dim) or not r.is_contiguous():
+            raise ValueError("into must be a contiguous float32 tensor of the byte table's shape")
+        res["byte_table"], gr.d_byte_table = r, capi.ptr(r)
+    if "scale_tok" in want_grads or "scale_byte" in want_grads:
+        sc = torch.zeros(2, dtype=torch.float32, device=dev)   # (an empty batch launches nothing: zeros)
+        if "scale_tok" in want_grads:
+            res["scale_tok"], gr.d_scale_tok = sc[0:1], sc.data_ptr()
+        if "scale_byte" in want_grads:
+            res["scale_byte"], gr.d_scale_byte = sc[1:2], sc.data_ptr() + 4
+        keep.append(sc)
+    if n == 0 or not res:
+        return res
+    if token_order is not None:
+        need = capi.lib.mot_token_order_ints(n, d.tok_rows)
+        if token_order.dtype != torch.int32 or token_order.numel() != need or not token_order.is_contiguous():
+            raise ValueError(f"token_order must be the contiguous int32[{need}] tensor token_order(tokens, {d.tok_rows}) returned")
+        gr.token_order = capi.ptr(token_order)
+    d.status = capi.ptr(capi.status_word(dev))
+    ws = _workspace(dev, capi.lib.mot_splitx_workspace_bytes(C.byref(d), 1))
+    if ws is not None:
+        d.workspace, d.workspace_bytes = capi.ptr(ws), ws.numel()
+    capi.check(capi.lib.mot_splitx_bwd(C.byref(d), C.byref(gr), capi.stream_of(dev)))
+    capi.after_call(dev)
+    return res
+
+
+class _SplitX0Fn(torch.autograd.Function):
+    """Autograd node of split_x0: one mot_splitx_fwd call forward, one mot_splitx_bwd call backward for the two tables and the two
+    scalars.  Saved: the tokens, the byte ids, the tables and the scalars; every row is gathered and normalised again.  The token
+    order comes from the cache the fused front-end uses."""
+
+    @staticmethod
+    def forward(ctx, tokens, kw, tok_table, byte_table, scale_tok, scale_byte):
+        outs, ids = _split_x0_fwd(tokens, tok_table.detach(), byte_table.detach(), scale_tok.detach(), scale_byte.detach(), save=True, **kw)
+        ctx.order = _token_orders.get(tokens, tok_table.shape[0]) if _HOIST_SORT and tokens.numel() and tok_table.requires_grad else None
+        ctx.want = _split_x0_want(kw.get("want", _SPLIT_X0_OUTS))
+        ctx.kw = dict(bpt=kw["bpt"], eps=kw.get("eps"))
+        ctx.save_for_backward(tokens, ids, tok_table, byte_table, scale_tok, scale_byte)
+        ctx.set_materialize_grads(False)   # an output nothing depends on arrives as None and goes to the library as NULL
+        return tuple(outs[w] for w in ctx.want)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        tokens, ids, tok_table, byte_table, scale_tok, scale_byte = ctx.saved_tensors
+        g = dict(zip(ctx.want, grads))
+        names = [n for j, n in enumerate(("tok_table", "byte_table", "scale_tok", "scale_byte")) if ctx.needs_input_grad[2 + j]]
+        if all(v is None for v in g.values()) or not names:
+            return (None,) * 6
+        order = None
+        if ctx.order is not None:
+            order, ev = ctx.order
+            cur = torch.cuda.current_stream(tokens.device)
+            if ev is not None:
+                cur.wait_event(ev)
+            order.record_stream(cur)
+        r = split_x0_backward(g.get("x0t"), g.get("x0b"), g.get("x"), tokens, tok_table.detach(), byte_table.detach(), scale_tok.detach(),
+                              scale_byte.detach(), ids=ids, token_order=order, want_grads=names, **ctx.kw)
+        pick = lambda k, p: None if k not in r else r[k].to(p.dtype).reshape(p.shape)   # bf16 byte table: the fp32 sums rounded once
+        return (None, None, pick("tok_table", tok_table), pick("byte_table", byte_table), pick("scale_tok", scale_tok), pick("scale_byte", scale_byte))
+
+
+def split_x0(tokens: torch.Tensor, tok_table: torch.Tensor, byte_table: torch.Tensor, scale_tok: torch.Tensor, scale_byte: torch.Tensor, *, bpt: int,
+             ids: torch.Tensor | None = None, ttb: torch.Tensor | None = None, pull: str | None = "left", pad_byte: int = 456, eot_byte: int = 457,
+             eps: float | None = None, want=_SPLIT_X0_OUTS) -> tuple:
+    """The three input streams of modded-nanogpt/runs/71081_mot-in_toks-valemb.py:302-304, 315 in one launch:
+    ``x0t = norm(tok_table[tokens])``, ``x0b = cat_k norm(byte_table[ids[:, k]])`` (each byte row normalised over byte_dim BEFORE the
+    cat) and ``x = x0t * scale_tok + x0b * scale_byte`` (no outer norm), with model_dim = bpt * byte_dim; float32 or bfloat16 throughout
+    (bf16: fp32 arithmetic, rounded where the reference's eager bf16 run rounds).  tokens (B, T) or (T,); the byte ids are in per-token
+    order (.., T*bpt), given as `ids` (int64) or made inside the kernel from the token->byte table `ttb` (+ `pull` = "left" | "right" |
+    None).  `scale_tok` / `scale_byte` are one-element float32 tensors on the device (the run's ``scalars[-1]`` / ``scalars[-2]``; a
+    slice of a longer parameter works, and its gradient flows back into that parameter).  `eps` None is the float32 epsilon for both
+    dtypes.  Returns the tensors named in `want`, in that order, each ``tokens.shape + (model_dim,)``, through ONE autograd node whose
+    backward is one call: the token table's gradient is written once in the table's dtype with the same bits on every run."""
+    capi.require_device(tokens, tok_table, byte_table, scale_tok, scale_byte, ids, ttb)
+    want = _split_x0_want(want)
+    kw = dict(bpt=int(bpt), ids=ids, ttb=ttb, pull=pull, pad_byte=pad_byte, eot_byte=eot_byte, eps=eps, want=want)
+    params = (tok_table, byte_table, scale_tok, scale_byte)
+    if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+        _split_x0_desc(tokens, *params, bpt, eps, "split_x0")   # shape and dtype errors before the node exists
+        return tuple(_SplitX0Fn.apply(tokens, kw, *params))
+    outs, _ = _split_x0_fwd(tokens, *params, **kw)
+    return tuple(outs[w] for w in want)

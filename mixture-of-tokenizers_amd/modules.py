@@ -672,6 +672,43 @@ class SumFrontEnd(nn.Module):
                                _f32(self.embed_bytes.weight, "byte table"), mode="sum", bpt=self.bpt, **kw)
 
 
+class SplitX0FrontEnd(nn.Module):
+    """The three input streams of runs/71081_*.py:302-304, 315, which every block of that run mixes again (:209-210, :319):
+    ``x0t = norm(embed_tokens(tok))``, ``x0b = cat_k norm(embed_bytes(byte_k))`` and ``x = scalars[-1] * x0t + scalars[-2] * x0b``, from
+    one forward and one backward call of the library.  ``scalars`` starts at the run's 0.5 / 0.5 (:247); a caller that keeps the two
+    at the end of a longer parameter, as the run does, passes that two-element slice to forward().  Per-token byte semantics and
+    state-dict keys as in SumFrontEnd.  byte_dim * bytes_per_token must equal model_dim."""
+
+    def __init__(self, token_vocab_size: int, byte_vocab_size: int, model_dim: int, byte_dim: int, bytes_per_token: int = 16,
+                 ttb=None, pad_byte: int = 456, eot_byte: int = 457):
+        super().__init__()
+        assert byte_dim * bytes_per_token == model_dim
+        self.embed_tokens = nn.Embedding(token_vocab_size, model_dim)
+        self.embed_bytes = nn.Embedding(byte_vocab_size, byte_dim)
+        self.bpt, self.pad_byte, self.eot_byte = bytes_per_token, pad_byte, eot_byte
+        self.scalars = nn.Parameter(torch.tensor([0.5, 0.5]))  # [-2] bytes, [-1] tokens
+        self.register_buffer("ttb", _table_of(ttb).clone() if ttb is not None else None, persistent=False)
+
+    def forward(self, token_inputs: Tensor, byte_inputs: Tensor | None = None, scalars: Tensor | None = None):
+        """token_inputs (T,) or (B,T); byte_inputs (.., T*bpt) per-token-ordered pulled ids, or None to produce them in-kernel from
+        the attached token->byte table; scalars: a two-element float32 tensor to use instead of the module's own ([-2] bytes,
+        [-1] tokens).  Returns (x, x0t, x0b)."""
+        s = self.scalars if scalars is None else scalars
+        if s.numel() != 2:
+            raise ValueError(f"SplitX0FrontEnd: scalars must hold two elements ([-2] bytes, [-1] tokens), got {tuple(s.shape)}")
+        s = s.reshape(2)
+        kw = {}
+        if byte_inputs is None:
+            if self.ttb is None:
+                raise ValueError("SplitX0FrontEnd: pass byte_inputs or construct the module with a token->byte table (ttb)")
+            kw.update(ttb=self.ttb, pull="left", pad_byte=self.pad_byte, eot_byte=self.eot_byte)
+        else:
+            kw.update(ids=byte_inputs.to(torch.int64).reshape(1 if token_inputs.ndim == 1 else token_inputs.shape[0], -1))
+        x0t, x0b, x = F_mot.split_x0(token_inputs, _f32(self.embed_tokens.weight, "token table"), _f32(self.embed_bytes.weight, "byte table"),
+                                     s[1:2], s[0:1], bpt=self.bpt, **kw)
+        return x, x0t, x0b
+
+
 class ConcatFrontEnd(nn.Module):
     """``x = norm(cat([embed_tokens(tok), embed_bytes(byte_0), ..., embed_bytes(byte_{bpt-1})], -1))``: "MoT via pure
     concatenation" (runs/711_*.py:224-232, call site 314-316; runs 712 and 713 reuse it), one fused launch forward and one
