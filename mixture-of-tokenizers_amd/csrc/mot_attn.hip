@@ -447,23 +447,22 @@ static AttnLayout attn_layout(const MotCrossAttnDesc &d) {
     const size_t T = (size_t)d.n_tokens, HD = (size_t)d.n_heads * kHd, D = (size_t)d.dim;
     const bool dual = d.ids_b != nullptr;
     L.R = dual ? (int64_t)(T * d.bpt) : d.byte_rows;
-    size_t o = 0;
-    auto take = [&](size_t n) { size_t at = o; o += (n + 63) & ~(size_t)63; return at; };
-    L.q = take(T * HD); L.y = take(T * HD); L.kt = take((size_t)L.R * HD); L.vt = take((size_t)L.R * HD);
-    L.xkv = take(dual ? T * d.bpt * D : (size_t)L.R * D);   // the (normalised) key/value source rows: per kv position, or per byte-table row
-    L.xq = take(D > HD ? T * D : 0);   // the gathered query rows live in y's place until the attention writes y
+    Arena ar{0, 64};   // counts floats
+    L.q = ar.take(T * HD); L.y = ar.take(T * HD); L.kt = ar.take((size_t)L.R * HD); L.vt = ar.take((size_t)L.R * HD);
+    L.xkv = ar.take(dual ? T * d.bpt * D : (size_t)L.R * D);   // the (normalised) key/value source rows: per kv position, or per byte-table row
+    L.xq = ar.take(D > HD ? T * D : 0);   // the gathered query rows live in y's place until the attention writes y
     const size_t wide = D > HD ? D : HD;
     // bf16 copies: the row operand of a product, its weight (two id tensors: the key / value source rows of every kv position, kv_w)
     const size_t a16 = dual && T * d.bpt * D > T * wide ? T * d.bpt * D : T * wide;
-    L.a16 = take(mm16(d) ? (a16 + 1) / 2 : 0);
-    L.w16 = take(mm16(d) ? ((dual ? 2 : 1) * HD * D + 1) / 2 : 0);
+    L.a16 = ar.take(mm16(d) ? (a16 + 1) / 2 : 0);
+    L.w16 = ar.take(mm16(d) ? ((dual ? 2 : 1) * HD * D + 1) / 2 : 0);
     L.part_n = gemm_rows_sliced_floats(L.R, (int)D, (int)HD);   // the key / value projections of the few byte-table rows, cut along dim
-    L.part = take(L.part_n);
+    L.part = ar.take(L.part_n);
     // bf16 products, one id tensor: the two tables once more in bf16 for the attention kernel (per kv position they would cost a pass
     // over 2 x T*bpt x HD to make, what reading them in bf16 saves)
     const size_t t16 = mm16(d) && !dual ? ((size_t)L.R * HD + 1) / 2 : 0;
-    L.kt16 = take(t16); L.vt16 = take(t16);
-    L.total = o;
+    L.kt16 = ar.take(t16); L.vt16 = ar.take(t16);
+    L.total = ar.o;
     return L;
 }
 
@@ -1172,14 +1171,13 @@ static AttnBwdLayout attn_bwd_layout(const MotCrossAttnDesc &d) {
     const size_t T = (size_t)d.n_tokens, HD = (size_t)d.n_heads * kHd, D = (size_t)d.dim, P = T * d.bpt;
     const bool dual = d.ids_b != nullptr;
     const size_t R = dual ? P : (size_t)d.byte_rows;   // key / value rows: per byte-table row, or per kv position
-    size_t o = 0;
-    auto take = [&](size_t n) { size_t at = o; o += (n + 63) & ~(size_t)63; return at; };
-    L.q = take(T * HD); L.y = take(T * HD); L.kpre = take(R * HD); L.vpre = take(R * HD); L.kn = take(R * HD); L.vl = take(R * HD);
-    L.dy = take(T * HD); L.dq = take(T * HD); L.pw = take(P * d.n_heads); L.dsw = take(P * d.n_heads); L.qrot = take(T * HD);
+    Arena ar{0, 64};   // counts floats
+    L.q = ar.take(T * HD); L.y = ar.take(T * HD); L.kpre = ar.take(R * HD); L.vpre = ar.take(R * HD); L.kn = ar.take(R * HD); L.vl = ar.take(R * HD);
+    L.dy = ar.take(T * HD); L.dq = ar.take(T * HD); L.pw = ar.take(P * d.n_heads); L.dsw = ar.take(P * d.n_heads); L.qrot = ar.take(T * HD);
     // byte ids of the kv positions, grouped -- or, per position, the identity order (2 P ints)
-    L.grp = take(dual ? 2 * P : group_positions_ws_ints((int64_t)P, (int64_t)d.byte_rows));
-    L.dkn_tab = take(R * HD); L.dvl_tab = take(R * HD); L.dkv = take(R * 2 * HD); L.xkv = take(R * D); L.dxkv = take(R * D);
-    L.xq = take(T * D); L.dxq = take(T * D); L.ids32 = take(P); L.ids32b = take(dual ? P : 0);
+    L.grp = ar.take(dual ? 2 * P : group_positions_ws_ints((int64_t)P, (int64_t)d.byte_rows));
+    L.dkn_tab = ar.take(R * HD); L.dvl_tab = ar.take(R * HD); L.dkv = ar.take(R * 2 * HD); L.xkv = ar.take(R * D); L.dxkv = ar.take(R * D);
+    L.xq = ar.take(T * D); L.dxq = ar.take(T * D); L.ids32 = ar.take(P); L.ids32b = ar.take(dual ? P : 0);
     MotEmbedMixDesc e;   // scratch of the token-table embedding backward and of the two byte-table backwards of the two-id embedding
     noop_bwd_desc(e, nullptr, (int64_t)T, nullptr, d.tok_rows, (int)D, d.norm_tok, 0.f, nullptr);
     size_t a = embed_mix_bwd_workspace_bytes(e), b = 0;
@@ -1188,21 +1186,21 @@ static AttnBwdLayout attn_bwd_layout(const MotCrossAttnDesc &d) {
         b = embed_mix_bwd_workspace_bytes(e);
     }
     L.emb_bytes = a > b ? a : b;
-    L.emb = take((L.emb_bytes + 3) / 4);
+    L.emb = ar.take((L.emb_bytes + 3) / 4);
     const size_t wide = D > HD ? D : HD;   // matmul_dtype == MOT_BF16: two bf16 row operands and one (transposed) weight at a time
     // (two id tensors: + the key / value source rows of every kv position; b1 also takes dkv, w16 also kv_w)
     const size_t b1n = dual && P * 2 * HD > T * wide ? P * 2 * HD : T * wide;
-    L.b0 = take(mm16(d) ? (T * wide + 1) / 2 : 0); L.b1 = take(mm16(d) ? (b1n + 1) / 2 : 0); L.w16 = take(mm16(d) ? ((dual ? 2 : 1) * HD * D + 1) / 2 : 0);
-    L.x16 = take(mm16(d) && dual ? (P * D + 1) / 2 : 0);
-    L.dq16 = take(mm16(d) ? (T * HD + 1) / 2 : 0);   // dq in bf16, written by the attention backward (b1 is reused for dkv in between)
+    L.b0 = ar.take(mm16(d) ? (T * wide + 1) / 2 : 0); L.b1 = ar.take(mm16(d) ? (b1n + 1) / 2 : 0); L.w16 = ar.take(mm16(d) ? ((dual ? 2 : 1) * HD * D + 1) / 2 : 0);
+    L.x16 = ar.take(mm16(d) && dual ? (P * D + 1) / 2 : 0);
+    L.dq16 = ar.take(mm16(d) ? (T * HD + 1) / 2 : 0);   // dq in bf16, written by the attention backward (b1 is reused for dkv in between)
     // partial blocks of the few-row products (key / value projections; dxkv = dkv W_kv), see launch_gemm_rows_sliced
     const size_t pa = gemm_rows_sliced_floats((int64_t)R, (int)D, (int)HD), pb = gemm_rows_sliced_floats((int64_t)R, (int)(2 * HD), (int)D);
     L.part_n = pa > pb ? pa : pb;
-    L.part = take(L.part_n);
+    L.part = ar.take(L.part_n);
     const size_t t16 = mm16(d) && !dual ? (R * HD + 1) / 2 : 0;   // norm(k), lambda v in bf16 (as in the forward)
-    L.kn16 = take(t16); L.vl16 = take(t16);
-    L.wt = take(mm16(d) ? 0 : 2 * HD * D);   // a transposed fp32 weight (c_proj, q_w, kv_w) for the k-major products over many rows
-    L.total = o;
+    L.kn16 = ar.take(t16); L.vl16 = ar.take(t16);
+    L.wt = ar.take(mm16(d) ? 0 : 2 * HD * D);   // a transposed fp32 weight (c_proj, q_w, kv_w) for the k-major products over many rows
+    L.total = ar.o;
     return L;
 }
 

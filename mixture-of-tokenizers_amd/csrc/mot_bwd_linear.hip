@@ -94,11 +94,10 @@ static LinBwdLayout lin_bwd_layout(const MotEmbedMixDesc &d) {
     L.Kp = (int)((K + 127) / 128 * 128);            // output columns of the du GEMM, padded as the MFMA kernel pads them
     if (L.Kp > 512 && L.Kp <= 768) L.Kp = 768; else if (L.Kp > 768) L.Kp = 1024;
     L.Dmp = (d.model_dim + 15) / 16 * 16;
-    size_t o = 0;
-    auto take = [&](size_t n) { size_t at = o; o += (n + 3) & ~(size_t)3; return at; };
-    L.rnorm = take(d.byte_rows); L.dy = take(N * d.model_dim); L.du = take(N * K); L.utok = take(N * d.tok_dim);
-    L.ubyte = take(N * d.bpt * d.byte_dim); L.wk = take((size_t)L.Dmp * L.Kp); L.byte0 = take(4); L.iota = take(N);
-    L.sort = take(scatter_ws_ints(d)); L.total = o;
+    Arena ar{0, 4};   // counts floats
+    L.rnorm = ar.take(d.byte_rows); L.dy = ar.take(N * d.model_dim); L.du = ar.take(N * K); L.utok = ar.take(N * d.tok_dim);
+    L.ubyte = ar.take(N * d.bpt * d.byte_dim); L.wk = ar.take((size_t)L.Dmp * L.Kp); L.byte0 = ar.take(4); L.iota = ar.take(N);
+    L.sort = ar.take(scatter_ws_ints(d)); L.total = ar.o;
     return L;
 }
 
@@ -109,11 +108,10 @@ struct UpLayout { size_t tok, byte, w, bias, g, x, total; };
 static UpLayout up_layout(const MotEmbedMixDesc &d) {
     UpLayout U;
     const size_t N = (size_t)(d.n_rows * d.tokens_per_row), K = (size_t)d.tok_dim + (size_t)d.bpt * d.byte_dim;
-    size_t o = 0;
-    auto take = [&](size_t n) { size_t at = o; o += (n + 3) & ~(size_t)3; return at; };
-    U.tok = take((size_t)d.tok_rows * d.tok_dim); U.byte = take((size_t)d.byte_rows * d.byte_dim); U.w = take((size_t)d.model_dim * K);
-    U.bias = take(d.bias ? d.model_dim : 0); U.g = take(N * d.model_dim); U.x = take(d.norm_out ? N * d.model_dim : 0);
-    U.total = o;
+    Arena ar{0, 4};   // counts floats
+    U.tok = ar.take((size_t)d.tok_rows * d.tok_dim); U.byte = ar.take((size_t)d.byte_rows * d.byte_dim); U.w = ar.take((size_t)d.model_dim * K);
+    U.bias = ar.take(d.bias ? d.model_dim : 0); U.g = ar.take(N * d.model_dim); U.x = ar.take(d.norm_out ? N * d.model_dim : 0);
+    U.total = ar.o;
     return U;
 }
 
@@ -124,11 +122,10 @@ struct Du16Layout { size_t dy16, wt16, uT, total; };
 static Du16Layout du16_layout(const MotEmbedMixDesc &d) {
     Du16Layout U;
     const size_t N = (size_t)(d.n_rows * d.tokens_per_row), K = (size_t)d.tok_dim + (size_t)d.bpt * d.byte_dim, Dm = (size_t)d.model_dim;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
-    U.dy16 = take(N * Dm * 2); U.wt16 = take(K * Dm * 2);
-    U.uT = take(N * K * 2);   // the concat operand in bf16, row-major (dW)
-    U.total = o;
+    Arena ar;
+    U.dy16 = ar.take(N * Dm * 2); U.wt16 = ar.take(K * Dm * 2);
+    U.uT = ar.take(N * K * 2);   // the concat operand in bf16, row-major (dW)
+    U.total = ar.o;
     return U;
 }
 static bool du16_usable(const MotEmbedMixDesc &d) {

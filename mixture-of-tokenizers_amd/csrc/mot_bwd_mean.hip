@@ -65,14 +65,13 @@ static MeanBwdLayout mean_bwd_layout(const MotEmbedMixDesc &d) {
     MeanBwdLayout L;
     const int64_t N = d.n_rows * d.tokens_per_row, slab = N < kMeanSlab ? N : kMeanSlab;
     L.ld = (int)((d.byte_rows + 3) & ~3);
-    size_t o = 0;
-    auto take = [&](size_t n) { size_t at = o; o += (n + 63) & ~(size_t)63; return at; };
-    L.rn = take(d.byte_rows); L.vn = take((size_t)d.byte_rows * d.byte_dim); L.m1 = take((size_t)d.byte_rows * d.byte_dim); L.w = take(d.byte_rows);
-    L.cnt = take((size_t)slab * L.ld); L.s = take((size_t)slab * L.ld); L.scatter = take(scatter_ws_ints(d));
+    Arena ar{0, 64};   // counts floats
+    L.rn = ar.take(d.byte_rows); L.vn = ar.take((size_t)d.byte_rows * d.byte_dim); L.m1 = ar.take((size_t)d.byte_rows * d.byte_dim); L.w = ar.take(d.byte_rows);
+    L.cnt = ar.take((size_t)slab * L.ld); L.s = ar.take((size_t)slab * L.ld); L.scatter = ar.take(scatter_ws_ints(d));
     // bf16 tables / gradient rows: the character side runs on fp32 copies -- the 132-row table once, the gradient rows a slab at a time
     L.tab32 = L.g32 = 0;
-    if (d.dtype == MOT_BF16) { L.tab32 = take((size_t)d.byte_rows * d.byte_dim); L.g32 = take((size_t)slab * d.byte_dim); }
-    L.total = o;
+    if (d.dtype == MOT_BF16) { L.tab32 = ar.take((size_t)d.byte_rows * d.byte_dim); L.g32 = ar.take((size_t)slab * d.byte_dim); }
+    L.total = ar.o;
     return L;
 }
 

@@ -330,7 +330,6 @@ __global__ __launch_bounds__(kCatBwdThreads) void byte_cat_bwd_kernel(const CatB
 }
 
 // ------------------------------------------------------------------------------------------ validation (no HIP call)
-static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // everything that does not need the pointers: also what the two size queries run
 static int byte_cat_check_shape(const MotByteCatDesc *d, bool backward) {
@@ -341,15 +340,7 @@ static int byte_cat_check_shape(const MotByteCatDesc *d, bool backward) {
     if (d->reserved0) return set_error(MOT_EINVAL, "byte_cat: reserved0 %u", d->reserved0);
     if (d->n_out < 1 || d->n_out > MOT_BYTE_CAT_MAX_OUT) return set_error(MOT_EUNSUPPORTED, "byte_cat: n_out %d outside [1, %d]", d->n_out, MOT_BYTE_CAT_MAX_OUT);
     if (d->n_rows < 0 || d->tokens_per_row < 0) return set_error(MOT_ESHAPE, "byte_cat: negative shape");
-    if (d->bpt < 1 || d->bpt > MOT_MAX_BPT) return set_error(MOT_EUNSUPPORTED, "byte_cat: bytes_per_token %d outside [1, %d]", d->bpt, MOT_MAX_BPT);
-    if (d->id_source == MOT_IDS_FROM_TTB) {
-        if (d->ttb_elem_bytes != 2 && d->ttb_elem_bytes != 4) return set_error(MOT_EINVAL, "byte_cat: ttb_elem_bytes must be 2 or 4");
-        if (d->pull_dir < MOT_PULL_NONE || d->pull_dir > MOT_PULL_RIGHT) return set_error(MOT_EINVAL, "byte_cat: bad pull_dir %d", d->pull_dir);
-        if (d->ttb_rows <= 0) return set_error(MOT_EINVAL, "byte_cat: ttb missing");
-        if (backward) return set_error(MOT_EUNSUPPORTED, "byte_cat_bwd: pass the byte ids the forward used (MOT_IDS_GIVEN)");
-    } else if (d->id_source != MOT_IDS_GIVEN) {
-        return set_error(MOT_EINVAL, "byte_cat: bad id_source %d", d->id_source);
-    }
+    if (int rc = check_id_source_shape("byte_cat", id_source_of(*d), backward)) return rc;
     const int vec = d->dtype == MOT_BF16 ? 8 : 4;
     if (d->byte_dim <= 0 || (d->byte_dim % vec))
         return set_error(MOT_EUNSUPPORTED, "byte_cat: byte_dim %d must be a positive multiple of %d elements (16 bytes)", d->byte_dim, vec);
@@ -361,8 +352,7 @@ static int byte_cat_check_shape(const MotByteCatDesc *d, bool backward) {
         if (d->slot[j].rows <= 0 || d->slot[j].rows > 0x7fffffffLL / d->byte_dim)
             return set_error(MOT_ESHAPE, "byte_cat: slot %d has a table of %lld rows", j, (long long)d->slot[j].rows);
     }
-    if (d->tokens_per_row * (int64_t)d->bpt > 0x7fffffffLL || d->n_rows * d->tokens_per_row > 0x7fffffffLL)
-        return set_error(MOT_EUNSUPPORTED, "byte_cat: T*bpt or B*T exceeds 2^31");
+    if (int rc = check_id_source_limits("byte_cat", id_source_of(*d))) return rc;
     return MOT_OK;
 }
 
@@ -391,19 +381,11 @@ int byte_cat_check(const MotByteCatDesc *d, const MotByteCatGrads *g, bool backw
         if (!backward && !d->slot[j].out) return set_error(MOT_EINVAL, "byte_cat: slot %d has a null out", j);
         if (backward && g->slot[j].grad_out && !g->slot[j].d_table) return set_error(MOT_EINVAL, "byte_cat_bwd: slot %d has a grad_out but a null d_table", j);
     }
-    if (d->id_source == MOT_IDS_FROM_TTB) {
-        if (!d->tokens || !d->ttb) return set_error(MOT_EINVAL, "byte_cat: tokens / ttb missing");
-    } else {
-        if (!d->ids) return set_error(MOT_EINVAL, "byte_cat: ids missing");
-        if (d->out_ids_padded || d->out_ids_pulled) return set_error(MOT_EINVAL, "byte_cat: out_ids_* need MOT_IDS_FROM_TTB");
-    }
-    if (d->n_rows == 0 || d->tokens_per_row == 0) return MOT_OK;
-    if (backward) {
-        const size_t need = byte_cat_bwd_workspace_bytes(d);
-        if (need && (!d->workspace || d->workspace_bytes < need || ((uintptr_t)d->workspace & 15)))
-            return set_error(MOT_EWORKSPACE, "byte_cat_bwd: needs %zu 16-byte aligned workspace bytes, got %zu", need, d->workspace_bytes);
-    }
-    return MOT_OK;
+    // (the only front-end that reads `tokens` for the ids alone: it has no token table)
+    if (d->id_source == MOT_IDS_FROM_TTB && (!d->tokens || !d->ttb)) return set_error(MOT_EINVAL, "byte_cat: tokens / ttb missing");
+    if (int rc = check_id_source_ptrs("byte_cat", id_source_of(*d))) return rc;
+    if (d->n_rows == 0 || d->tokens_per_row == 0 || !backward) return MOT_OK;
+    return check_workspace("byte_cat", true, d->workspace, d->workspace_bytes, byte_cat_bwd_workspace_bytes(d));
 }
 
 // ------------------------------------------------------------------------------------------ launches
@@ -419,13 +401,9 @@ static int launch_cat_fwd(const CatArgs &C, int64_t blocks, size_t lds, hipStrea
 int launch_byte_cat_fwd(const MotByteCatDesc &d, hipStream_t stream) {
     CatArgs C{};
     MixArgs &A = C.M;
-    const int64_t N = d.n_rows * d.tokens_per_row;
-    A.tokens = d.tokens; A.T = d.tokens_per_row; A.bpt = d.bpt;
-    A.id_source = d.id_source; A.pull_dir = d.pull_dir; A.ttb = d.ttb; A.ttb_rows = d.ttb_rows; A.ttb_elem = d.ttb_elem_bytes;
-    A.pad = d.pad_byte; A.eot = d.eot_byte; A.ids_a = d.ids; A.ids_b = nullptr;
+    fill_mix_ids(A, id_source_of(d));
     A.Db = d.byte_dim;
     A.eps = d.eps > 0.f ? d.eps : FLT_EPSILON;
-    A.out_ids_padded = d.out_ids_padded; A.out_ids_pulled = d.out_ids_pulled; A.counters = d.counters; A.status = d.status;
     int64_t max_rows = 0;
     for (int j = 0; j < d.n_out; ++j) {
         C.table[j] = d.slot[j].table; C.out[j] = d.slot[j].out; C.rows[j] = (int)d.slot[j].rows; C.norm[j] = d.slot[j].norm;
@@ -433,14 +411,9 @@ int launch_byte_cat_fwd(const MotByteCatDesc &d, hipStream_t stream) {
     }
     A.byte_rows = max_rows;   // the index phase clamps to the largest table; the streaming loop clamps per table
     C.n_out = d.n_out; C.Dm = d.bpt * d.byte_dim;
-    A.unit = N >= 131072 ? 32 : 16;   // tokens per wave, the fused front-end's choice (mot_embed.hip, pick_unit)
-    A.units_per_row = (d.tokens_per_row + A.unit - 1) / A.unit;
-    A.n_units = d.n_rows * A.units_per_row;
-    const int64_t blocks = (A.n_units + kWaves - 1) / kWaves;
-    if (blocks > 0x7fffffffLL) return set_error(MOT_EUNSUPPORTED, "byte_cat: too many units");
-    const int stream_eb = (d.id_source == MOT_IDS_FROM_TTB && d.pull_dir != MOT_PULL_NONE) ? d.ttb_elem_bytes : 0;
-    A.wave_lds = (int)wave_lds_bytes(A.unit, d.bpt, false, stream_eb);
-    const size_t lds = (size_t)A.wave_lds * kWaves;
+    int64_t blocks;
+    size_t lds;
+    if (int rc = wave_geometry("byte_cat", A, d.n_rows, blocks, lds)) return rc;
     // NCH = 16-byte chunks per lane; U keeps ~8 independent 16-byte loads per lane in flight
     if (d.dtype == MOT_BF16) {
         switch ((C.Dm / 8 + 63) / 64) {

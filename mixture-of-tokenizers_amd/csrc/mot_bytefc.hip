@@ -176,7 +176,6 @@ __global__ __launch_bounds__(kThreads) void bytefc_count_kernel(const int64_t *_
 }
 
 // ------------------------------------------------------------------------------------------ validation (no HIP call)
-static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // rows of the lane-contiguous scatter: the byte part of [ds | du] in blocks of `per` whole slots (0: the general kernel takes the row)
 static int scatter_split_per(int Dm, int Db, int bpt) {
@@ -196,15 +195,7 @@ static int byte_fc_check_shape(const MotByteFcMixDesc *d, bool backward) {
     if (d->dtype != MOT_F32 && d->dtype != MOT_BF16) return set_error(MOT_EINVAL, "byte_fc_mix: bad dtype %d", d->dtype);
     if (d->flags & ~MOT_BYTE_FC_COMPOSED) return set_error(MOT_EINVAL, "byte_fc_mix: unknown flags 0x%x", d->flags);
     if (d->n_rows < 0 || d->tokens_per_row < 0) return set_error(MOT_ESHAPE, "byte_fc_mix: negative shape");
-    if (d->bpt < 1 || d->bpt > MOT_MAX_BPT) return set_error(MOT_EUNSUPPORTED, "byte_fc_mix: bytes_per_token %d outside [1, %d]", d->bpt, MOT_MAX_BPT);
-    if (d->id_source == MOT_IDS_FROM_TTB) {
-        if (d->ttb_elem_bytes != 2 && d->ttb_elem_bytes != 4) return set_error(MOT_EINVAL, "byte_fc_mix: ttb_elem_bytes must be 2 or 4");
-        if (d->pull_dir < MOT_PULL_NONE || d->pull_dir > MOT_PULL_RIGHT) return set_error(MOT_EINVAL, "byte_fc_mix: bad pull_dir %d", d->pull_dir);
-        if (d->ttb_rows <= 0) return set_error(MOT_EINVAL, "byte_fc_mix: ttb missing");
-        if (backward) return set_error(MOT_EUNSUPPORTED, "byte_fc_mix_bwd: pass the byte ids the forward used (MOT_IDS_GIVEN)");
-    } else if (d->id_source != MOT_IDS_GIVEN) {
-        return set_error(MOT_EINVAL, "byte_fc_mix: bad id_source %d", d->id_source);
-    }
+    if (int rc = check_id_source_shape("byte_fc_mix", id_source_of(*d), backward)) return rc;
     if (d->tok_rows <= 0 || d->byte_rows <= 0 || d->tok_dim <= 0 || d->byte_dim <= 0 || d->model_dim <= 0)
         return set_error(MOT_ESHAPE, "byte_fc_mix: empty table (tok %lld x %d, byte %lld x %d, model_dim %d)", (long long)d->tok_rows, d->tok_dim,
                          (long long)d->byte_rows, d->byte_dim, d->model_dim);
@@ -216,8 +207,7 @@ static int byte_fc_check_shape(const MotByteFcMixDesc *d, bool backward) {
     const int64_t K = (int64_t)d->bpt * d->byte_dim;
     if (d->model_dim > kFcMaxDim || K > kFcMaxDim)
         return set_error(MOT_EUNSUPPORTED, "byte_fc_mix: model_dim %d / bpt*byte_dim %lld above %d is not built", d->model_dim, (long long)K, kFcMaxDim);
-    if (d->tokens_per_row * (int64_t)d->bpt > 0x7fffffffLL || d->n_rows * d->tokens_per_row > 0x7fffffffLL)
-        return set_error(MOT_EUNSUPPORTED, "byte_fc_mix: T*bpt or B*T exceeds 2^31");
+    if (int rc = check_id_source_limits("byte_fc_mix", id_source_of(*d))) return rc;
     if (backward) {
         if (d->tok_rows >= (1 << 21) - 1)
             return set_error(MOT_EUNSUPPORTED, "byte_fc_mix_bwd: token tables of %lld rows (>= 2^21 - 1) are not built", (long long)d->tok_rows);
@@ -234,11 +224,10 @@ static FcFwdLayout fc_fwd_layout(const MotByteFcMixDesc &d) {
     const size_t N = (size_t)(d.n_rows * d.tokens_per_row), K = (size_t)d.bpt * d.byte_dim, esz = d.dtype == MOT_BF16 ? 2 : 4;
     const size_t ns = N < (size_t)kFcFwdSlab ? N : (size_t)kFcFwdSlab;
     FcFwdLayout L;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o += up256(bytes); return at; };
-    L.u = take(ns * K * esz);
-    L.ids = take(d.id_source == MOT_IDS_FROM_TTB ? 2 * N * d.bpt * sizeof(int64_t) : 0);
-    L.total = o;
+    Arena ar;
+    L.u = ar.take(ns * K * esz);
+    L.ids = ar.take(d.id_source == MOT_IDS_FROM_TTB ? 2 * N * d.bpt * sizeof(int64_t) : 0);
+    L.total = ar.o;
     return L;
 }
 
@@ -250,16 +239,15 @@ static FcBwdLayout fc_bwd_layout(const MotByteFcMixDesc &d) {
     FcBwdLayout L;
     L.slab = (int64_t)(N < (size_t)kFcBwdSlab ? N : (size_t)kFcBwdSlab);
     const size_t ns = (size_t)L.slab;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o += up256(bytes); return at; };
-    L.rows = take(ns * (Dm + K) * 4);
-    L.sort = take((2 * (size_t)d.tok_rows + 3 * ns) * 4);
-    L.u = take(ns * K * (bf ? 2 : 4));
-    L.ds16 = take(bf ? ns * Dm * 2 : 0);
-    L.wt16 = take(bf ? K * Dm * 2 : 0);
-    L.tok32 = take(bf ? (size_t)d.tok_rows * Dm * 4 : 0);
-    L.byte32 = take(bf ? (size_t)d.byte_rows * d.byte_dim * 4 : 0);
-    L.total = o;
+    Arena ar;
+    L.rows = ar.take(ns * (Dm + K) * 4);
+    L.sort = ar.take((2 * (size_t)d.tok_rows + 3 * ns) * 4);
+    L.u = ar.take(ns * K * (bf ? 2 : 4));
+    L.ds16 = ar.take(bf ? ns * Dm * 2 : 0);
+    L.wt16 = ar.take(bf ? K * Dm * 2 : 0);
+    L.tok32 = ar.take(bf ? (size_t)d.tok_rows * Dm * 4 : 0);
+    L.byte32 = ar.take(bf ? (size_t)d.byte_rows * d.byte_dim * 4 : 0);
+    L.total = ar.o;
     return L;
 }
 
@@ -270,12 +258,7 @@ int byte_fc_check(const MotByteFcMixDesc *d, const MotByteFcMixGrads *g, bool ba
     if (int rc = byte_fc_check_shape(d, backward)) return rc;
     if (!d->byte_fc) return set_error(MOT_EINVAL, "byte_fc_mix: byte_fc [%d, %d] missing", d->model_dim, d->bpt * d->byte_dim);
     if (!d->tokens || !d->tok_table || !d->byte_table) return set_error(MOT_EINVAL, "byte_fc_mix: tokens/tok_table/byte_table must be non-null");
-    if (d->id_source == MOT_IDS_FROM_TTB) {
-        if (!d->ttb) return set_error(MOT_EINVAL, "byte_fc_mix: ttb missing");
-    } else {
-        if (!d->ids) return set_error(MOT_EINVAL, "byte_fc_mix: ids missing");
-        if (d->out_ids_padded || d->out_ids_pulled) return set_error(MOT_EINVAL, "byte_fc_mix: out_ids_* need MOT_IDS_FROM_TTB");
-    }
+    if (int rc = check_id_source_ptrs("byte_fc_mix", id_source_of(*d))) return rc;
     if (backward) {
         if (!g || g->struct_size != sizeof(MotByteFcMixGrads)) return set_error(MOT_EINVAL, "byte_fc_mix_bwd: grads struct missing or struct_size mismatch");
         if (!g->grad_out || !g->d_tok || !g->d_byte || !g->d_byte_fc) return set_error(MOT_EINVAL, "byte_fc_mix_bwd: grad_out/d_tok/d_byte/d_byte_fc must be non-null");
@@ -285,10 +268,7 @@ int byte_fc_check(const MotByteFcMixDesc *d, const MotByteFcMixGrads *g, bool ba
         return set_error(MOT_EINVAL, "byte_fc_mix: out must be non-null");
     }
     if (d->n_rows == 0 || d->tokens_per_row == 0) return MOT_OK;
-    const size_t need = backward ? fc_bwd_layout(*d).total : fc_fwd_layout(*d).total;
-    if (!d->workspace || d->workspace_bytes < need || ((uintptr_t)d->workspace & 15))
-        return set_error(MOT_EWORKSPACE, "byte_fc_mix%s: needs %zu 16-byte aligned workspace bytes, got %zu", backward ? "_bwd" : "", need, d->workspace_bytes);
-    return MOT_OK;
+    return check_workspace("byte_fc_mix", backward, d->workspace, d->workspace_bytes, backward ? fc_bwd_layout(*d).total : fc_fwd_layout(*d).total);
 }
 
 // ------------------------------------------------------------------------------------------ forward
@@ -332,15 +312,10 @@ int launch_byte_fc_mix_fwd(const MotByteFcMixDesc &d, hipStream_t stream) {
         int64_t *ws_ids = (int64_t *)(ws + L.ids);
         int64_t *padded = d.out_ids_padded ? d.out_ids_padded : ws_ids;
         int64_t *pulled = d.out_ids_pulled ? d.out_ids_pulled : ws_ids + slots;
-        if ((rc = launch_tokens_to_bytes(d.tokens, N, d.ttb, d.ttb_elem_bytes, d.ttb_rows, bpt, padded, d.status, stream))) return rc;
-        ids = padded_c = padded;
-        if (d.pull_dir != MOT_PULL_NONE) {
-            if ((rc = launch_pull_bytes(padded, pulled, d.n_rows, d.tokens_per_row, bpt, d.pad_byte, d.eot_byte,
-                                        d.pull_dir == MOT_PULL_LEFT ? kPullLeft : kPullRight, stream))) return rc;
-            ids = pulled;
-        } else if (d.out_ids_pulled) {   // nothing is pulled: that output is the padded tensor again
+        if ((rc = launch_ids_from_ttb(id_source_of(d), padded, pulled, &ids, stream))) return rc;
+        padded_c = padded;
+        if (d.pull_dir == MOT_PULL_NONE && d.out_ids_pulled)   // nothing is pulled: that output is the padded tensor again
             if ((rc = launch_tokens_to_bytes(d.tokens, N, d.ttb, d.ttb_elem_bytes, d.ttb_rows, bpt, d.out_ids_pulled, nullptr, stream))) return rc;
-        }
     }
     if (d.counters) {
         int64_t blocks = padded_c ? (slots + kThreads * 16 - 1) / (kThreads * 16) : 1;

@@ -617,7 +617,6 @@ int launch_rows_rnorm(const void *table, int64_t rows, int dim, float eps, float
 // Tokens per wave.  16 below 131 072 tokens: the shard a GPU gets when config 4 is split over 8 GPUs is 65 536 tokens, and 16 puts
 // 16 waves on every CU there (measured 58.8 us = 86 % of the roofline, 60.4 us with 32); 32 from there on: the index pass over
 // the 64-token window is then shared by twice the tokens (434.6 us at 524 288 tokens against 438.3).
-static int pick_unit(int64_t n_tokens) { return n_tokens >= 131072 ? 32 : 16; }
 
 // The routed SUM forward: byte ids from the token->byte table, no id outputs (the index pass writes them only in the fused
 // kernel), byte ids that fit uint16, and enough tokens.  fp32 tables that fit the 256 MiB Infinity Cache only: measured at

@@ -4,6 +4,7 @@
 #pragma once
 #include <float.h>
 
+#include "mot_desc.hpp"
 #include "mot_internal.hpp"
 #include "mot_tile.hpp"
 
@@ -169,12 +170,19 @@ __device__ __forceinline__ void phase1_given(const MixArgs &A, const TileLds &L,
 }
 
 
+// Fills the id fields of MixArgs from a front-end's id source: one id tensor, nothing added to the padded ids.
+inline void fill_mix_ids(MixArgs &A, const IdSource &s) {
+    A.tokens = s.tokens; A.T = s.tokens_per_row; A.bpt = s.bpt;
+    A.id_source = s.id_source; A.pull_dir = s.pull_dir; A.ttb = s.ttb; A.ttb_rows = s.ttb_rows; A.ttb_elem = s.ttb_elem_bytes;
+    A.add_padded = 0; A.pad = s.pad_byte; A.eot = s.eot_byte; A.ids_a = s.ids; A.ids_b = nullptr;
+    A.out_ids_padded = s.out_ids_padded; A.out_ids_pulled = s.out_ids_pulled; A.counters = s.counters; A.status = s.status;
+}
+
 // Fills the id-related fields of MixArgs from the public descriptor.
 inline void fill_mix_args(MixArgs &A, const MotEmbedMixDesc &d) {
-    A.tokens = d.tokens; A.T = d.tokens_per_row; A.bpt = d.mode == MOT_MIX_NOOP ? 0 : d.bpt;
-    A.id_source = d.id_source; A.pull_dir = d.pull_dir; A.ttb = d.ttb; A.ttb_rows = d.ttb_rows;
-    A.ttb_elem = d.ttb_elem_bytes; A.add_padded = d.add_padded; A.pad = d.pad_byte; A.eot = d.eot_byte;
-    A.ids_a = d.ids_a; A.ids_b = d.ids_b;
+    fill_mix_ids(A, {d.tokens, d.n_rows, d.tokens_per_row, d.mode == MOT_MIX_NOOP ? 0 : d.bpt, d.id_source, d.pull_dir, d.ttb, d.ttb_rows,
+                     d.ttb_elem_bytes, d.ids_a, d.pad_byte, d.eot_byte, d.out_ids_padded, d.out_ids_pulled, d.counters, d.status});
+    A.add_padded = d.add_padded; A.ids_b = d.ids_b;
     A.tok_table = (const float *)d.tok_table; A.tok_rows = d.tok_rows; A.Dt = d.tok_dim;
     A.byte_table = (const float *)d.byte_table; A.byte_rows = d.byte_rows; A.Db = d.byte_dim;
     A.norm_tok = d.norm_tok; A.norm_byte = d.norm_byte; A.norm_out = d.norm_out;
@@ -185,8 +193,6 @@ inline void fill_mix_args(MixArgs &A, const MotEmbedMixDesc &d) {
     A.out = (float *)d.out;
     A.add16 = nullptr;
     A.add_out = 0;
-    A.out_ids_padded = d.out_ids_padded; A.out_ids_pulled = d.out_ids_pulled; A.counters = d.counters;
-    A.status = d.status;
 }
 
 }  // namespace mot

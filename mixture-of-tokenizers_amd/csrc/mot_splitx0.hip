@@ -348,7 +348,6 @@ __global__ __launch_bounds__(kSxSumThreads) void split_x0_scalars_kernel(const f
 }
 
 // ------------------------------------------------------------------------------------------ validation (no HIP call)
-static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // everything that does not need the pointers: also what the size query runs
 static int split_x0_check_shape(const MotSplitX0Desc *d, bool backward) {
@@ -358,15 +357,7 @@ static int split_x0_check_shape(const MotSplitX0Desc *d, bool backward) {
     if (d->dtype != MOT_F32 && d->dtype != MOT_BF16) return set_error(MOT_EUNSUPPORTED, "split_x0: dtype %d is not built (MOT_F32 or MOT_BF16)", d->dtype);
     if (d->reserved0) return set_error(MOT_EINVAL, "split_x0: reserved0 %u", d->reserved0);
     if (d->n_rows < 0 || d->tokens_per_row < 0) return set_error(MOT_ESHAPE, "split_x0: negative shape");
-    if (d->bpt < 1 || d->bpt > MOT_MAX_BPT) return set_error(MOT_EUNSUPPORTED, "split_x0: bytes_per_token %d outside [1, %d]", d->bpt, MOT_MAX_BPT);
-    if (d->id_source == MOT_IDS_FROM_TTB) {
-        if (d->ttb_elem_bytes != 2 && d->ttb_elem_bytes != 4) return set_error(MOT_EINVAL, "split_x0: ttb_elem_bytes must be 2 or 4");
-        if (d->pull_dir < MOT_PULL_NONE || d->pull_dir > MOT_PULL_RIGHT) return set_error(MOT_EINVAL, "split_x0: bad pull_dir %d", d->pull_dir);
-        if (d->ttb_rows <= 0) return set_error(MOT_EINVAL, "split_x0: ttb missing");
-        if (backward) return set_error(MOT_EUNSUPPORTED, "split_x0_bwd: pass the byte ids the forward used (MOT_IDS_GIVEN)");
-    } else if (d->id_source != MOT_IDS_GIVEN) {
-        return set_error(MOT_EINVAL, "split_x0: bad id_source %d", d->id_source);
-    }
+    if (int rc = check_id_source_shape("split_x0", id_source_of(*d), backward)) return rc;
     if (d->tok_rows <= 0 || d->byte_rows <= 0 || d->model_dim <= 0 || d->byte_dim <= 0)
         return set_error(MOT_ESHAPE, "split_x0: empty table (tok %lld x %d, byte %lld x %d)", (long long)d->tok_rows, d->model_dim, (long long)d->byte_rows,
                          d->byte_dim);
@@ -375,8 +366,7 @@ static int split_x0_check_shape(const MotSplitX0Desc *d, bool backward) {
     if ((int64_t)d->bpt * d->byte_dim != d->model_dim)
         return set_error(MOT_EUNSUPPORTED, "split_x0: model_dim %d != bpt*byte_dim = %d*%d (x0b is the cat of the byte rows)", d->model_dim, d->bpt, d->byte_dim);
     if (d->model_dim > kSxMaxDim) return set_error(MOT_EUNSUPPORTED, "split_x0: model_dim %d above %d is not built", d->model_dim, kSxMaxDim);
-    if (d->tokens_per_row * (int64_t)d->bpt > 0x7fffffffLL || d->n_rows * d->tokens_per_row > 0x7fffffffLL)
-        return set_error(MOT_EUNSUPPORTED, "split_x0: T*bpt or B*T exceeds 2^31");
+    if (int rc = check_id_source_limits("split_x0", id_source_of(*d))) return rc;
     if (d->byte_rows > 0x7fffffffLL / d->byte_dim || d->tok_rows > 0x7fffffffLL)
         return set_error(MOT_ESHAPE, "split_x0: tables of %lld and %lld rows", (long long)d->tok_rows, (long long)d->byte_rows);
     return MOT_OK;
@@ -390,17 +380,16 @@ static SxLayout split_x0_layout(const MotSplitX0Desc &d, bool backward) {
     SxLayout L{};
     L.slab = (int64_t)(N < (size_t)kSxSlab ? N : (size_t)kSxSlab);
     L.nblk = (int64_t)((N + kSxBlockTok - 1) / kSxBlockTok);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o += up256(bytes); return at; };
-    L.rnorm = take((size_t)d.byte_rows * sizeof(float));
+    Arena ar;
+    L.rnorm = ar.take((size_t)d.byte_rows * sizeof(float));
     if (backward) {
-        L.part = take((size_t)L.nblk * 2 * sizeof(float));
+        L.part = ar.take((size_t)L.nblk * 2 * sizeof(float));
         // a table at or above the token order's limit takes no token-table gradient (refused where one is asked for)
-        L.sums = take(d.tok_rows < kSxOrderLimit ? token_sums_ws_bytes((int64_t)N, d.tok_rows, d.model_dim, d.dtype) : 0);
-        L.da = take(d.tok_rows < kSxOrderLimit ? N * D * sizeof(float) : 0);
-        L.dub = take((size_t)L.slab * D * sizeof(float));
+        L.sums = ar.take(d.tok_rows < kSxOrderLimit ? token_sums_ws_bytes((int64_t)N, d.tok_rows, d.model_dim, d.dtype) : 0);
+        L.da = ar.take(d.tok_rows < kSxOrderLimit ? N * D * sizeof(float) : 0);
+        L.dub = ar.take((size_t)L.slab * D * sizeof(float));
     }
-    L.total = o;
+    L.total = ar.o;
     return L;
 }
 
@@ -428,18 +417,9 @@ int split_x0_check(const MotSplitX0Desc *d, const MotSplitX0Grads *g, bool backw
     if (!backward) align |= (uintptr_t)d->out_x0t | (uintptr_t)d->out_x0b | (uintptr_t)d->out_x;
     else align |= (uintptr_t)g->grad_x0t | (uintptr_t)g->grad_x0b | (uintptr_t)g->grad_x | (uintptr_t)g->d_tok_table | (uintptr_t)g->d_byte_table;
     if (align & 15) return set_error(MOT_EINVAL, "split_x0: tables, outputs and gradients must be 16-byte aligned");
-    if (d->id_source == MOT_IDS_FROM_TTB) {
-        if (!d->ttb) return set_error(MOT_EINVAL, "split_x0: ttb missing");
-    } else {
-        if (!d->ids) return set_error(MOT_EINVAL, "split_x0: ids missing");
-        if (d->out_ids_padded || d->out_ids_pulled) return set_error(MOT_EINVAL, "split_x0: out_ids_* need MOT_IDS_FROM_TTB");
-    }
+    if (int rc = check_id_source_ptrs("split_x0", id_source_of(*d))) return rc;
     if (d->n_rows == 0 || d->tokens_per_row == 0) return MOT_OK;
-    const size_t need = split_x0_layout(*d, backward).total;
-    if (!d->workspace || d->workspace_bytes < need || ((uintptr_t)d->workspace & 15))
-        return set_error(MOT_EWORKSPACE, "split_x0%s: needs %zu 16-byte aligned workspace bytes, got %zu", backward ? "_bwd" : "", need,
-                         d->workspace ? d->workspace_bytes : (size_t)0);
-    return MOT_OK;
+    return check_workspace("split_x0", backward, d->workspace, d->workspace ? d->workspace_bytes : (size_t)0, split_x0_layout(*d, backward).total);
 }
 
 // ------------------------------------------------------------------------------------------ launches
@@ -459,23 +439,14 @@ int launch_split_x0_fwd(const MotSplitX0Desc &d, hipStream_t stream) {
     if (int rc = launch_rows_rnorm(d.byte_table, d.byte_rows, d.byte_dim, eps, rnorm, d.dtype, stream)) return rc;
     SplitArgs S{};
     MixArgs &A = S.M;
-    const int64_t N = d.n_rows * d.tokens_per_row;
-    A.tokens = d.tokens; A.T = d.tokens_per_row; A.bpt = d.bpt;
-    A.id_source = d.id_source; A.pull_dir = d.pull_dir; A.ttb = d.ttb; A.ttb_rows = d.ttb_rows; A.ttb_elem = d.ttb_elem_bytes;
-    A.pad = d.pad_byte; A.eot = d.eot_byte; A.ids_a = d.ids; A.ids_b = nullptr;
+    fill_mix_ids(A, id_source_of(d));
     A.tok_table = (const float *)d.tok_table; A.tok_rows = d.tok_rows; A.Dt = d.model_dim;
     A.byte_table = (const float *)d.byte_table; A.byte_rows = d.byte_rows; A.Db = d.byte_dim;
     A.eps = eps; A.scale_tok = d.scale_tok; A.scale_byte = d.scale_byte; A.byte_rnorm = rnorm;
-    A.out_ids_padded = d.out_ids_padded; A.out_ids_pulled = d.out_ids_pulled; A.counters = d.counters; A.status = d.status;
     S.x0t = d.out_x0t; S.x0b = d.out_x0b; S.x = d.out_x; S.Dm = d.model_dim;
-    A.unit = N >= 131072 ? 32 : 16;   // tokens per wave, the fused front-end's choice (mot_embed.hip, pick_unit)
-    A.units_per_row = (d.tokens_per_row + A.unit - 1) / A.unit;
-    A.n_units = d.n_rows * A.units_per_row;
-    const int64_t blocks = (A.n_units + kWaves - 1) / kWaves;
-    if (blocks > 0x7fffffffLL) return set_error(MOT_EUNSUPPORTED, "split_x0: too many units");
-    const int stream_eb = (d.id_source == MOT_IDS_FROM_TTB && d.pull_dir != MOT_PULL_NONE) ? d.ttb_elem_bytes : 0;
-    A.wave_lds = (int)wave_lds_bytes(A.unit, d.bpt, false, stream_eb);
-    const size_t lds = (size_t)A.wave_lds * kWaves;
+    int64_t blocks;
+    size_t lds;
+    if (int rc = wave_geometry("split_x0", A, d.n_rows, blocks, lds)) return rc;
     // NCH = 16-byte chunks per lane; U keeps ~8 independent 16-byte row loads per lane in flight (a token and a byte chunk per token)
     if (d.dtype == MOT_BF16) {
         switch ((S.Dm / 8 + 63) / 64) {

@@ -89,7 +89,6 @@ __global__ __launch_bounds__(kThreads) void valuemix_dy_kernel(const T *__restri
 }
 
 // ------------------------------------------------------------------------------------------ validation (no HIP call)
-static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // everything that does not need the pointers: also what the size query runs
 static int value_mix_check_shape(const MotValueMixDesc *d, bool backward) {
@@ -99,15 +98,7 @@ static int value_mix_check_shape(const MotValueMixDesc *d, bool backward) {
     if (d->dtype != MOT_F32 && d->dtype != MOT_BF16) return set_error(MOT_EINVAL, "value_mix: bad dtype %d", d->dtype);
     if (d->n_slots < 1 || d->n_slots > kVmSlots) return set_error(MOT_EUNSUPPORTED, "value_mix: n_slots %d outside [1, %d]", d->n_slots, kVmSlots);
     if (d->n_rows < 0 || d->tokens_per_row < 0) return set_error(MOT_ESHAPE, "value_mix: negative shape");
-    if (d->bpt < 1 || d->bpt > MOT_MAX_BPT) return set_error(MOT_EUNSUPPORTED, "value_mix: bytes_per_token %d outside [1, %d]", d->bpt, MOT_MAX_BPT);
-    if (d->id_source == MOT_IDS_FROM_TTB) {
-        if (d->ttb_elem_bytes != 2 && d->ttb_elem_bytes != 4) return set_error(MOT_EINVAL, "value_mix: ttb_elem_bytes must be 2 or 4");
-        if (d->pull_dir < MOT_PULL_NONE || d->pull_dir > MOT_PULL_RIGHT) return set_error(MOT_EINVAL, "value_mix: bad pull_dir %d", d->pull_dir);
-        if (d->ttb_rows <= 0) return set_error(MOT_EINVAL, "value_mix: ttb missing");
-        if (backward) return set_error(MOT_EUNSUPPORTED, "value_mix_bwd: pass the byte ids the forward used (MOT_IDS_GIVEN)");
-    } else if (d->id_source != MOT_IDS_GIVEN) {
-        return set_error(MOT_EINVAL, "value_mix: bad id_source %d", d->id_source);
-    }
+    if (int rc = check_id_source_shape("value_mix", id_source_of(*d), backward)) return rc;
     if (d->tok_rows <= 0 || d->byte_rows <= 0 || d->token_dim <= 0 || d->byte_dim <= 0 || d->out_dim <= 0)
         return set_error(MOT_ESHAPE, "value_mix: empty table (tok %lld x %d, byte %lld x %d, out_dim %d)", (long long)d->tok_rows, d->token_dim,
                          (long long)d->byte_rows, d->byte_dim, d->out_dim);
@@ -118,8 +109,7 @@ static int value_mix_check_shape(const MotValueMixDesc *d, bool backward) {
     const int64_t K = d->token_dim + (int64_t)d->bpt * d->byte_dim;
     if (K > kVmMaxDim) return set_error(MOT_EUNSUPPORTED, "value_mix: K = token_dim + bpt*byte_dim = %lld above %d is not built", (long long)K, kVmMaxDim);
     if (d->out_dim > kVmMaxDim) return set_error(MOT_EUNSUPPORTED, "value_mix: out_dim %d above %d is not built", d->out_dim, kVmMaxDim);
-    if (d->tokens_per_row * (int64_t)d->bpt > 0x7fffffffLL || d->n_rows * d->tokens_per_row > 0x7fffffffLL)
-        return set_error(MOT_EUNSUPPORTED, "value_mix: T*bpt or B*T exceeds 2^31");
+    if (int rc = check_id_source_limits("value_mix", id_source_of(*d))) return rc;
     if (d->byte_rows > 0x7fffffffLL / d->byte_dim) return set_error(MOT_ESHAPE, "value_mix: byte tables of %lld rows", (long long)d->byte_rows);
     if (backward && d->tok_rows >= (1 << 21) - 1)
         return set_error(MOT_EUNSUPPORTED, "value_mix_bwd: token tables of %lld rows (>= 2^21 - 1, the token order's limit) are not built", (long long)d->tok_rows);
@@ -145,11 +135,10 @@ static VmFwdLayout vm_fwd_layout(const MotValueMixDesc &d) {
     const size_t N = (size_t)(d.n_rows * d.tokens_per_row), K = (size_t)d.token_dim + (size_t)d.bpt * d.byte_dim, esz = d.dtype == MOT_BF16 ? 2 : 4;
     const size_t ns = N < (size_t)kVmSlab ? N : (size_t)kVmSlab;
     VmFwdLayout L;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o += up256(bytes); return at; };
-    L.u = take(vm_one_launch(d) ? 0 : ns * K * esz);
-    L.ids = take(d.id_source == MOT_IDS_FROM_TTB ? 2 * N * d.bpt * sizeof(int64_t) : 0);
-    L.total = o;
+    Arena ar;
+    L.u = ar.take(vm_one_launch(d) ? 0 : ns * K * esz);
+    L.ids = ar.take(d.id_source == MOT_IDS_FROM_TTB ? 2 * N * d.bpt * sizeof(int64_t) : 0);
+    L.total = ar.o;
     return L;
 }
 
@@ -163,15 +152,14 @@ static VmBwdLayout vm_bwd_layout(const MotValueMixDesc &d) {
     VmBwdLayout L;
     L.slab = (int64_t)(N < (size_t)kVmSlab ? N : (size_t)kVmSlab);
     const size_t ns = (size_t)L.slab;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o += up256(bytes); return at; };
-    L.sums = take(token_sums_ws_bytes((int64_t)N, d.tok_rows, d.token_dim, d.dtype));
-    L.dut = take(N * Dt * 4);
-    L.dub = take(ns * Kb * 4);
-    L.u = take(ns * K * esz);
-    L.dy = take(d.norm_out ? ns * Do * esz : 0);
-    L.wt16 = take(bf ? K * Do * 2 : 0);
-    L.total = o;
+    Arena ar;
+    L.sums = ar.take(token_sums_ws_bytes((int64_t)N, d.tok_rows, d.token_dim, d.dtype));
+    L.dut = ar.take(N * Dt * 4);
+    L.dub = ar.take(ns * Kb * 4);
+    L.u = ar.take(ns * K * esz);
+    L.dy = ar.take(d.norm_out ? ns * Do * esz : 0);
+    L.wt16 = ar.take(bf ? K * Do * 2 : 0);
+    L.total = ar.o;
     return L;
 }
 
@@ -202,17 +190,9 @@ int value_mix_check(const MotValueMixDesc *d, const MotValueMixGrads *g, bool ba
         align |= (uintptr_t)q.grad_out | (uintptr_t)q.d_tok | (uintptr_t)q.d_byte | (uintptr_t)q.d_weight;
     }
     if (align & 15) return set_error(MOT_EINVAL, "value_mix: tables, weights, outputs and gradients must be 16-byte aligned");
-    if (d->id_source == MOT_IDS_FROM_TTB) {
-        if (!d->ttb) return set_error(MOT_EINVAL, "value_mix: ttb missing");
-    } else {
-        if (!d->ids) return set_error(MOT_EINVAL, "value_mix: ids missing");
-        if (d->out_ids) return set_error(MOT_EINVAL, "value_mix: out_ids needs MOT_IDS_FROM_TTB");
-    }
+    if (int rc = check_id_source_ptrs("value_mix", id_source_of(*d), "out_ids needs")) return rc;
     if (d->n_rows == 0 || d->tokens_per_row == 0) return MOT_OK;
-    const size_t need = backward ? vm_bwd_layout(*d).total : vm_fwd_layout(*d).total;
-    if (need && (!d->workspace || d->workspace_bytes < need || ((uintptr_t)d->workspace & 15)))
-        return set_error(MOT_EWORKSPACE, "value_mix%s: needs %zu 16-byte aligned workspace bytes, got %zu", backward ? "_bwd" : "", need, d->workspace_bytes);
-    return MOT_OK;
+    return check_workspace("value_mix", backward, d->workspace, d->workspace_bytes, backward ? vm_bwd_layout(*d).total : vm_fwd_layout(*d).total);
 }
 
 // ------------------------------------------------------------------------------------------ forward
@@ -230,15 +210,9 @@ int launch_value_mix_fwd(const MotValueMixDesc &d, hipStream_t stream) {
     if (d.id_source == MOT_IDS_FROM_TTB) {
         int64_t *ws_ids = (int64_t *)(ws + L.ids);
         const bool pull = d.pull_dir != MOT_PULL_NONE;
-        int64_t *padded = (!pull && d.out_ids) ? d.out_ids : ws_ids;
-        if ((rc = launch_tokens_to_bytes(d.tokens, N, d.ttb, d.ttb_elem_bytes, d.ttb_rows, bpt, padded, d.status, stream))) return rc;
-        ids = padded;
-        if (pull) {
-            int64_t *pulled = d.out_ids ? d.out_ids : ws_ids + slots;
-            if ((rc = launch_pull_bytes(padded, pulled, d.n_rows, d.tokens_per_row, bpt, d.pad_byte, d.eot_byte,
-                                        d.pull_dir == MOT_PULL_LEFT ? kPullLeft : kPullRight, stream))) return rc;
-            ids = pulled;
-        }
+        int64_t *padded = (!pull && d.out_ids) ? d.out_ids : ws_ids;   // the one id output takes the ids the tables are read with
+        int64_t *pulled = d.out_ids ? d.out_ids : ws_ids + slots;
+        if ((rc = launch_ids_from_ttb(id_source_of(d), padded, pulled, &ids, stream))) return rc;
     }
     // 2a. bf16 at the gather-GEMM's shapes: one launch over (token tile, slot)
     if (vm_one_launch(d)) {

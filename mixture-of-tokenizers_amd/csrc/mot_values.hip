@@ -334,7 +334,6 @@ __global__ __launch_bounds__(kThreads) void ve_bwd_rows_kernel(const VeBwdArgs A
 }
 
 // ------------------------------------------------------------------------------------------ validation (no HIP call)
-static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 static int value_embeds_check_shape(const MotValueEmbedsDesc *d) {
     if (!d) return set_error(MOT_EINVAL, "value_embeds: null descriptor");

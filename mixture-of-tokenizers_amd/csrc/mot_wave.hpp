@@ -72,6 +72,20 @@ __host__ __device__ inline size_t wave_lds_bytes(int unit, int bpt, bool dual, i
     size_t b = (size_t)unit * sv * 4 * (dual ? 2 : 1) + ((size_t)66 * bpt + 1) * stream_elem_bytes;
     return (b + 15) & ~(size_t)15;
 }
+// Host side: the launch geometry of a wave kernel with one id tensor, from MixArgs whose id fields are filled (fill_mix_ids).
+// Sets unit, units_per_row, n_units and wave_lds; `blocks` workgroups of kWaves waves with `lds` bytes take the call.
+inline int pick_unit(int64_t n_tokens) { return n_tokens >= 131072 ? 32 : 16; }   // tokens per wave
+inline int wave_geometry(const char *fn, MixArgs &A, int64_t n_rows, int64_t &blocks, size_t &lds) {
+    A.unit = pick_unit(n_rows * A.T);
+    A.units_per_row = (A.T + A.unit - 1) / A.unit;
+    A.n_units = n_rows * A.units_per_row;
+    blocks = (A.n_units + kWaves - 1) / kWaves;
+    if (blocks > 0x7fffffffLL) return set_error(MOT_EUNSUPPORTED, "%s: too many units", fn);
+    const int stream_eb = (A.id_source == MOT_IDS_FROM_TTB && A.pull_dir != MOT_PULL_NONE) ? A.ttb_elem : 0;
+    A.wave_lds = (int)wave_lds_bytes(A.unit, A.bpt, false, stream_eb);
+    lds = (size_t)A.wave_lds * kWaves;
+    return MOT_OK;
+}
 __device__ __forceinline__ WaveLds wave_lds_carve(unsigned char *base, int unit, int bpt, bool dual, int stream_elem_bytes) {
     WaveLds W;
     const int sv = bpt | 1;

@@ -183,6 +183,98 @@ def release_workspaces() -> None:
     _retired.clear()
 
 
+# ----------------------------------------------------------------------------------------------
+# what the descriptor front-ends share: the token tensor, the byte-id source, the optional bindings, the call itself and the
+# autograd nodes' common lines.  A new front-end is written on top of these ("Shared front-end pieces").
+# ----------------------------------------------------------------------------------------------
+def _int32(t: torch.Tensor) -> torch.Tensor:
+    t = t.to(torch.int32) if t.dtype != torch.int32 else t
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _tokens_2d(tokens: torch.Tensor, what: str = "tokens must be (B, T) or (T,)") -> torch.Tensor:
+    """tokens (B, T) or (T,) of any integer dtype -> the (B, T) int32 contiguous tensor the library reads; `what` is the refusal."""
+    if tokens.ndim == 1:
+        tokens = tokens[None]
+    if tokens.ndim != 2:
+        raise ValueError(what)
+    tokens = tokens.to(torch.int32) if tokens.dtype != torch.int32 else tokens
+    return tokens if tokens.is_contiguous() else tokens.contiguous()
+
+
+def _bind_byte_ids(d, keep, *, B, T, bpt, ids, ttb, pull, what, ids_what="byte ids must hold bytes_per_token ids per token"):
+    """The descriptor's byte-id source: the token->byte table `ttb` (+ `pull`) for the library to make the ids from, else the given
+    int64 `ids`, which are returned (None with `ttb`: the caller allocates and binds whichever id outputs it wants back)."""
+    if ttb is not None:
+        tab = _int_table(ttb, what)
+        if tab.shape[1] != bpt:
+            raise ValueError(f"ttb has {tab.shape[1]} slots per token, bpt={bpt}")
+        keep.append(tab)
+        d.id_source, d.pull_dir = capi.IDS_FROM_TTB, _PULLS[pull]
+        d.ttb, d.ttb_rows, d.ttb_elem_bytes = capi.ptr(tab), tab.shape[0], tab.element_size()
+        return None
+    if ids is None:
+        raise ValueError("either ttb or ids must be given")
+    ia = _contig(ids, torch.int64, "ids")
+    if ia.numel() != B * T * bpt:
+        raise ValueError(ids_what)
+    keep.append(ia)
+    d.id_source, d.ids = capi.IDS_GIVEN, capi.ptr(ia)
+    return ia
+
+
+def _new_ids(B, T, bpt, dev) -> torch.Tensor:
+    return torch.empty((B, T * bpt), dtype=torch.int64, device=dev)
+
+
+def _bind_counters(d, counters, dev) -> None:
+    if counters is not None:
+        if counters.dtype != torch.int64 or counters.numel() < 4 or counters.device != dev:
+            raise ValueError("counters must be an int64[4] tensor on the inputs' device")
+        d.counters = capi.ptr(counters)
+
+
+def _bind_token_order(gr, keep, token_order, n_tokens, tok_rows, dev, contiguous="contiguous ") -> None:
+    if token_order is not None:
+        need = capi.lib.mot_token_order_ints(n_tokens, int(tok_rows))
+        if token_order.dtype != torch.int32 or token_order.numel() != need or token_order.device != dev or not token_order.is_contiguous():
+            raise ValueError(f"token_order must be the {contiguous}int32[{need}] tensor token_order(tokens, {tok_rows}) returned")
+        gr.token_order = capi.ptr(token_order)
+        keep.append(token_order)
+
+
+def _launch(dev, d, fn, *extra, ws_bytes=None):
+    """The tail of every descriptor call: the device's status word, the workspace (`ws_bytes`: the library's size query, called with
+    the descriptor), `fn(desc, *extra, stream)` on the current stream, its return code and the deferred status check.  `fn` None
+    binds only (embed_mix_plan launches later).  Returns the workspace."""
+    d.status = capi.ptr(capi.status_word(dev))
+    ws = None if ws_bytes is None else _workspace(dev, ws_bytes(C.byref(d)))
+    if ws is not None:
+        d.workspace, d.workspace_bytes = capi.ptr(ws), ws.numel()
+    if fn is not None:
+        capi.check(fn(C.byref(d), *extra, capi.stream_of(dev)))
+        capi.after_call(dev)
+    return ws
+
+
+def _ready_order(ctx_order, device):
+    """The token order an autograd node asked for beside its forward, made ready for the backward on `device`'s current stream
+    (None: the backward groups the positions itself)."""
+    if ctx_order is None:
+        return None
+    order, ev = ctx_order
+    cur = torch.cuda.current_stream(device)
+    if ev is not None:
+        cur.wait_event(ev)
+    order.record_stream(cur)
+    return order
+
+
+def _grad_like(g, p):
+    """The fp32 gradient sums rounded once to the parameter's dtype, in its shape."""
+    return None if g is None else g.to(p.dtype).reshape(p.shape)
+
+
 @torch.compiler.disable
 def _embed_mix_fwd(tokens: torch.Tensor, tok_table: torch.Tensor, byte_table: torch.Tensor | None = None, *,
               mode: str, bpt: int = 0,
@@ -208,16 +300,11 @@ def _embed_mix_fwd(tokens: torch.Tensor, tok_table: torch.Tensor, byte_table: to
     whole-row kernel instead of the LDS column-slice kernel) override the import-time defaults (MotEmbedMixDesc.flags).
     """
     m = _MODES[mode]
-    if tokens.ndim == 1:
-        tokens = tokens[None]
-    if tokens.ndim != 2:
-        raise ValueError("tokens must be (B, T) or (T,)")
+    tok = _tokens_2d(tokens)
     dev = capi.require_device(tokens, tok_table, byte_table, ttb, ids_a, ids_b, weight, bias, scale_tok, scale_byte)
     for what, sc in (("scale_tok", scale_tok), ("scale_byte", scale_byte)):
         if sc is not None and (sc.dtype != torch.float32 or sc.numel() != 1):
             raise TypeError(f"{what}: expected a 1-element float32 device tensor, got {sc.dtype} x {sc.numel()}")
-    tok = tokens.to(torch.int32) if tokens.dtype != torch.int32 else tokens
-    tok = tok if tok.is_contiguous() else tok.contiguous()
     B, T = tok.shape
     tt = _table(tok_table, "tok_table")
     fdt = tt.dtype
@@ -245,8 +332,7 @@ def _embed_mix_fwd(tokens: torch.Tensor, tok_table: torch.Tensor, byte_table: to
             d.ttb, d.ttb_rows, d.ttb_elem_bytes = capi.ptr(tab), tab.shape[0], tab.element_size()
             d.add_padded = int(add_padded)
             if return_ids:
-                ids_padded = torch.empty((B, T * bpt), dtype=torch.int64, device=dev)
-                ids_pulled = torch.empty((B, T * bpt), dtype=torch.int64, device=dev)
+                ids_padded, ids_pulled = _new_ids(B, T, bpt, dev), _new_ids(B, T, bpt, dev)
                 d.out_ids_padded, d.out_ids_pulled = capi.ptr(ids_padded), capi.ptr(ids_pulled)
         else:
             if ids_a is None:
@@ -288,23 +374,15 @@ def _embed_mix_fwd(tokens: torch.Tensor, tok_table: torch.Tensor, byte_table: to
         if out.shape != (B, T, d.model_dim) or out.dtype != fdt or not out.is_contiguous() or out.device != dev:
             raise ValueError("out must be a contiguous (B, T, model_dim) tensor of the tables' dtype on their device")
     d.out = capi.ptr(out)
-    if counters is not None:
-        if counters.dtype != torch.int64 or counters.numel() < 4 or counters.device != dev:
-            raise ValueError("counters must be an int64[4] tensor on the inputs' device")
-        d.counters = capi.ptr(counters)
-    d.status = capi.ptr(capi.status_word(dev))
+    _bind_counters(d, counters, dev)
     if row_rnorm is not None:   # (B, T) fp32, written by the concat_linear kernel when norm_out (saved for the backward)
         assert row_rnorm.dtype == torch.float32 and row_rnorm.numel() == B * T and row_rnorm.is_contiguous()
         d.out_row_rnorm = capi.ptr(row_rnorm)
-    ws = _workspace(dev, capi.lib.mot_embed_mix_workspace_bytes(C.byref(d)))
-    if ws is not None:
-        d.workspace, d.workspace_bytes = capi.ptr(ws), ws.numel()
-        keep.append(ws)
     result = MixResult(out, ids_padded, ids_pulled) if return_ids else out
     if _plan:
-        return EmbedMixPlan(d, keep + [out, ids_padded, ids_pulled, counters, row_rnorm, scale_tok, scale_byte], dev, result)
-    capi.check(capi.lib.mot_embed_mix_fwd(C.byref(d), capi.stream_of(dev)))
-    capi.after_call(dev)
+        ws = _launch(dev, d, None, ws_bytes=capi.lib.mot_embed_mix_workspace_bytes)
+        return EmbedMixPlan(d, keep + [ws, out, ids_padded, ids_pulled, counters, row_rnorm, scale_tok, scale_byte], dev, result)
+    _launch(dev, d, capi.lib.mot_embed_mix_fwd, ws_bytes=capi.lib.mot_embed_mix_workspace_bytes)
     return result
 
 
@@ -335,8 +413,7 @@ def token_order(tokens: torch.Tensor, tok_rows: int) -> torch.Tensor:
     """One call of mot_token_order: the batch's positions grouped by token id (opaque int32 buffer), which the table-gradient
     scatter of every backward over these tokens walks.  Depends on `tokens` only; runs on the current stream."""
     dev = capi.require_device(tokens)
-    tok = tokens.to(torch.int32) if tokens.dtype != torch.int32 else tokens
-    tok = tok if tok.is_contiguous() else tok.contiguous()
+    tok = _int32(tokens)
     order = torch.empty(capi.lib.mot_token_order_ints(tok.numel(), int(tok_rows)), dtype=torch.int32, device=dev)
     capi.check(capi.lib.mot_token_order(capi.ptr(tok), tok.numel(), int(tok_rows), capi.ptr(order), capi.ptr(capi.status_word(dev)),
                                         capi.stream_of(dev)))
@@ -437,21 +514,14 @@ class _EmbedMixFn(torch.autograd.Function):
         # autograd as usual.
         direct = {k: p.grad for k, p in (("tok_table", tok_table), ("byte_table", byte_table), ("weight", weight), ("bias", bias))
                   if _accumulates_in_place(p)}
-        order = None
-        if ctx.order is not None:
-            order, ev = ctx.order
-            if ev is not None:
-                torch.cuda.current_stream(gx.device).wait_event(ev)
-            order.record_stream(torch.cuda.current_stream(gx.device))
         g = embed_mix_backward(gx, tokens, tok_table.detach(), None if byte_table is None else byte_table.detach(),
-                               ids_a=ids_a, ids_b=ids_b, token_order=order,
+                               ids_a=ids_a, ids_b=ids_b, token_order=_ready_order(ctx.order, gx.device),
                                scale_tok=None if scale_tok is None else scale_tok.detach(),
                                scale_byte=None if scale_byte is None else scale_byte.detach(),
                                weight=None if weight is None else weight.detach(), bias=None if bias is None else bias.detach(),
                                out=None if x is None else x.detach(), row_rnorm=rn, into=direct, **ctx.kw)
         def like(k, p):  # bf16 parameters get their gradient rounded once, from the fp32 sums
-            t = g.get(k)
-            return None if t is None or p is None or k in direct else t.to(p.dtype).reshape(p.shape)
+            return None if p is None or k in direct else _grad_like(g.get(k), p)
         return (like("tok_table", tok_table), like("byte_table", byte_table), like("scale_tok", scale_tok),
                 like("scale_byte", scale_byte), like("weight", weight), like("bias", bias), None, None)
 
@@ -482,8 +552,7 @@ def embed_mix_backward(grad_out: torch.Tensor, tokens: torch.Tensor, tok_table: 
     if tokens.ndim == 1:
         tokens = tokens[None]
     dev = capi.require_device(grad_out, tokens, tok_table, byte_table, ids_a, ids_b, scale_tok, scale_byte)
-    tok = tokens.to(torch.int32) if tokens.dtype != torch.int32 else tokens
-    tok = tok if tok.is_contiguous() else tok.contiguous()
+    tok = _int32(tokens)
     B, T = tok.shape
     dt = tok_table.dtype
     code = capi.dtype_code(dt)
@@ -547,18 +616,8 @@ def embed_mix_backward(grad_out: torch.Tensor, tokens: torch.Tensor, tok_table: 
         if sc is not None and out[k] is None:
             out[k] = torch.zeros(1, dtype=torch.float32, device=dev)
     gr.d_scale_tok, gr.d_scale_byte = capi.ptr(out["scale_tok"]), capi.ptr(out["scale_byte"])
-    if token_order is not None:
-        need = capi.lib.mot_token_order_ints(B * T, tt.shape[0])
-        if token_order.dtype != torch.int32 or token_order.numel() != need or token_order.device != dev or not token_order.is_contiguous():
-            raise ValueError(f"token_order must be the contiguous int32[{need}] tensor token_order(tokens, {tt.shape[0]}) returned")
-        gr.token_order = capi.ptr(token_order)
-        keep.append(token_order)
-    d.status = capi.ptr(capi.status_word(dev))
-    ws = _workspace(dev, capi.lib.mot_embed_mix_bwd_workspace_bytes(C.byref(d)))
-    if ws is not None:
-        d.workspace, d.workspace_bytes = capi.ptr(ws), ws.numel()
-    capi.check(capi.lib.mot_embed_mix_bwd(C.byref(d), C.byref(gr), capi.stream_of(dev)))
-    capi.after_call(dev)
+    _bind_token_order(gr, keep, token_order, B * T, tt.shape[0], dev)
+    _launch(dev, d, capi.lib.mot_embed_mix_bwd, C.byref(gr), ws_bytes=capi.lib.mot_embed_mix_bwd_workspace_bytes)
     return out
 
 
@@ -594,8 +653,7 @@ def _cross_attn_desc(tokens, ids_a, ids_b, tok_table, byte_table, q_w, kv_w, pro
     instead of made again."""
     dev = capi.require_device(tokens, ids_a, ids_b, tok_table, byte_table, q_w, kv_w, proj_w, lambda_factor, cos_q, sin_q, cos_k, sin_k)
     T = tokens.shape[1]
-    tok = tokens.to(torch.int32) if tokens.dtype != torch.int32 else tokens
-    tok = tok if tok.is_contiguous() else tok.contiguous()
+    tok = _int32(tokens)
     f32 = torch.float32
     # bf16 tables (the production cast, train_gpt.py:1124-1126): the attention kernels of this mixin are fp32, so the operands are
     # widened once per call -- the tables as they are (bf16 values), the fp32 master weights rounded to bf16 first, as
@@ -662,7 +720,6 @@ def _cross_attn_desc(tokens, ids_a, ids_b, tok_table, byte_table, q_w, kv_w, pro
     # norm() is F.rms_norm(x, eps=None): eps = finfo(x.dtype).eps, and with bf16 tables every tensor it is applied to here (the
     # embeddings, q, k) is bf16 in the reference -- 2^-7, not the float32 epsilon of the widened copies (train_gpt.py:172-173)
     d.eps = float(eps or (2.0 ** -7 if bf else 0.0))
-    d.status = capi.ptr(capi.status_word(dev))
     return d, [tok, tt, bt, qw, kvw, pw, lam, ia, ib] + rot + [tt16], dev, T, D
 
 
@@ -714,11 +771,7 @@ def cross_attn_backward(grad_out, tokens, ids_a, tok_table, byte_table, *, q_w, 
     gr.d_q_w, gr.d_kv_w, gr.d_proj_w, gr.d_lambda = capi.ptr(out["q_w"]), capi.ptr(out["kv_w"]), capi.ptr(out["proj_w"]), capi.ptr(out["lambda_factor"])
     if saved_qy is not None:
         d.saved_qy = capi.ptr(_contig(saved_qy, torch.float32, "saved_qy"))
-    ws = _workspace(dev, capi.lib.mot_cross_attn_bwd_workspace_bytes(C.byref(d)))
-    if ws is not None:
-        d.workspace, d.workspace_bytes = capi.ptr(ws), ws.numel()
-    capi.check(capi.lib.mot_cross_attn_bwd(C.byref(d), C.byref(gr), capi.stream_of(dev)))
-    capi.after_call(dev)
+    _launch(dev, d, capi.lib.mot_cross_attn_bwd, C.byref(gr), ws_bytes=capi.lib.mot_cross_attn_bwd_workspace_bytes)
     return out
 
 
@@ -742,11 +795,7 @@ def _cross_attn_fwd(tokens, ids_a, ids_b, tok_table, byte_table, q_w, kv_w, proj
             kv_cache["buf"], kv_cache["key"] = torch.empty(n, dtype=torch.float32, device=dev), None
         d.kv_tables, d.kv_tables_ready = capi.ptr(kv_cache["buf"]), int(kv_cache.get("key") == key)
         kv_cache["key"] = key
-    ws = _workspace(dev, capi.lib.mot_cross_attn_workspace_bytes(C.byref(d)))
-    if ws is not None:
-        d.workspace, d.workspace_bytes = capi.ptr(ws), ws.numel()
-    capi.check(capi.lib.mot_cross_attn_fwd(C.byref(d), capi.stream_of(dev)))
-    capi.after_call(dev)
+    _launch(dev, d, capi.lib.mot_cross_attn_fwd, ws_bytes=capi.lib.mot_cross_attn_workspace_bytes)
     return out
 
 
@@ -855,18 +904,13 @@ def char_swa(tokens: torch.Tensor, char_ids: torch.Tensor, tok_table: torch.Tens
     d.io_dtype = capi.BF16 if (bf and mm_bf16) else capi.F32   # bf16 tables: the last product writes the bf16 result itself
     out = torch.empty((B, T, D), dtype=torch.bfloat16 if d.io_dtype == capi.BF16 else f32, device=dev)
     d.out = capi.ptr(out)
-    d.status = capi.ptr(capi.status_word(dev))
     if kv_cache is not None:
         n = 2 * ct.shape[0] * hdim
         if kv_cache.get("buf") is None or kv_cache["buf"].numel() != n or kv_cache["buf"].device != dev:
             kv_cache["buf"], kv_cache["key"] = torch.empty(n, dtype=f32, device=dev), None
         d.kv_tables, d.kv_tables_ready = capi.ptr(kv_cache["buf"]), int(kv_cache.get("key") == kv_key + (str(dev),))
         kv_cache["key"] = kv_key + (str(dev),)
-    ws = _workspace(dev, capi.lib.mot_char_swa_workspace_bytes(C.byref(d)))
-    if ws is not None:
-        d.workspace, d.workspace_bytes = capi.ptr(ws), ws.numel()
-    capi.check(capi.lib.mot_char_swa_fwd(C.byref(d), capi.stream_of(dev)))
-    capi.after_call(dev)
+    _launch(dev, d, capi.lib.mot_char_swa_fwd, ws_bytes=capi.lib.mot_char_swa_workspace_bytes)
     return out.to(torch.bfloat16) if bf else out
 
 
@@ -885,10 +929,6 @@ def _byte_head_desc(x, w, targets, method, bpt, n_layer_out, row_stats, loss):
     d.method, d.dtype, d.bpt = _HEAD_METHODS[method], capi.dtype_code(x.dtype), int(bpt)
     d.n_tokens, d.model_dim, d.n_layer_out, d.vocab, d.eps = x.shape[0], x.shape[1], int(n_layer_out), w.shape[0], 0.0
     d.x, d.weight, d.targets, d.loss, d.row_stats = capi.ptr(x), capi.ptr(w), capi.ptr(targets), capi.ptr(loss), capi.ptr(row_stats)
-    d.status = capi.ptr(capi.status_word(dev))
-    ws = _workspace(dev, capi.lib.mot_byte_head_workspace_bytes(C.byref(d)))
-    if ws is not None:
-        d.workspace, d.workspace_bytes = capi.ptr(ws), ws.numel()
     return d, dev
 
 
@@ -916,8 +956,7 @@ class _ByteHeadFn(torch.autograd.Function):
         row_stats = torch.empty(2 * rows, dtype=torch.float32, device=x2.device)
         loss = torch.empty((), dtype=torch.float32, device=x2.device)
         d, dev = _byte_head_desc(x2, w, t, method, bpt, n_layer_out, row_stats, loss)
-        capi.check(capi.lib.mot_byte_head_fwd(C.byref(d), capi.stream_of(dev)))
-        capi.after_call(dev)
+        _launch(dev, d, capi.lib.mot_byte_head_fwd, ws_bytes=capi.lib.mot_byte_head_workspace_bytes)
         ctx.save_for_backward(x2, w, t, row_stats)
         ctx.cfg = (method, bpt, n_layer_out, x.shape, weight.dtype)
         return loss
@@ -930,8 +969,7 @@ class _ByteHeadFn(torch.autograd.Function):
         go = _contig(grad_loss.detach().reshape(()).float(), torch.float32, "grad_loss")
         dx = torch.empty_like(x2)
         dw = torch.empty(w.shape, dtype=torch.float32, device=dev)
-        capi.check(capi.lib.mot_byte_head_bwd(C.byref(d), capi.ptr(go), capi.ptr(dx), capi.ptr(dw), capi.stream_of(dev)))
-        capi.after_call(dev)
+        _launch(dev, d, capi.lib.mot_byte_head_bwd, capi.ptr(go), capi.ptr(dx), capi.ptr(dw), ws_bytes=capi.lib.mot_byte_head_workspace_bytes)
         return dx.reshape(xshape), dw.to(wdtype), None, None, None, None
 
 
@@ -959,7 +997,7 @@ def _byte_self_attn_desc(x3, qkv_w, proj_w, lam, cos, sin, bpt, window, block_ca
     d.dim, d.n_heads, d.head_dim = D, qkv_w.shape[1] // 128, 128
     d.x, d.qkv_w, d.proj_w, d.lambda_v = capi.ptr(x3), capi.ptr(qkv_w), capi.ptr(proj_w), capi.ptr(lam)
     d.cos, d.sin, d.rope_rows, d.eps = capi.ptr(cos), capi.ptr(sin), cos.shape[0], 0.0
-    d.out, d.status = capi.ptr(out), capi.ptr(capi.status_word(dev))
+    d.out = capi.ptr(out)
     if saved is not None:
         d.saved, d.saved_bytes = capi.ptr(saved), saved.numel()
     return d, dev
@@ -988,8 +1026,7 @@ class _ByteSelfAttnFn(torch.autograd.Function):
         d, dev = _byte_self_attn_desc(x3, w, pw, lam, cs, sn, bpt, window, block_causal, out, None)
         saved = torch.empty(int(capi.lib.mot_byte_self_attn_saved_bytes(C.byref(d))), dtype=torch.uint8, device=dev)
         d.saved, d.saved_bytes = capi.ptr(saved), saved.numel()
-        capi.check(capi.lib.mot_byte_self_attn_fwd(C.byref(d), capi.stream_of(dev)))
-        capi.after_call(dev)
+        _launch(dev, d, capi.lib.mot_byte_self_attn_fwd)
         ctx.save_for_backward(x3, w, pw, lam, cs, sn, saved)
         ctx.cfg = (bpt, window, block_causal)
         return out
@@ -999,9 +1036,6 @@ class _ByteSelfAttnFn(torch.autograd.Function):
         x3, w, pw, lam, cs, sn, saved = ctx.saved_tensors
         bpt, window, block_causal = ctx.cfg
         d, dev = _byte_self_attn_desc(x3, w, pw, lam, cs, sn, bpt, window, block_causal, None, saved)
-        ws = _workspace(dev, capi.lib.mot_byte_self_attn_workspace_bytes(C.byref(d)))
-        if ws is not None:
-            d.workspace, d.workspace_bytes = capi.ptr(ws), ws.numel()
         go = _contig(grad_out.detach(), torch.float32, "grad_out")
         need = ctx.needs_input_grad
         dx = torch.empty_like(x3) if need[0] else None
@@ -1011,8 +1045,7 @@ class _ByteSelfAttnFn(torch.autograd.Function):
         g = capi.MotByteSelfAttnGrads()
         g.struct_size = C.sizeof(capi.MotByteSelfAttnGrads)
         g.grad_out, g.dx, g.d_qkv_w, g.d_proj_w, g.d_lambda = capi.ptr(go), capi.ptr(dx), capi.ptr(dw), capi.ptr(dpw), capi.ptr(dlam)
-        capi.check(capi.lib.mot_byte_self_attn_bwd(C.byref(d), C.byref(g), capi.stream_of(dev)))
-        capi.after_call(dev)
+        _launch(dev, d, capi.lib.mot_byte_self_attn_bwd, C.byref(g), ws_bytes=capi.lib.mot_byte_self_attn_workspace_bytes)
         return dx, dw, dpw, dlam, None, None, None, None, None
 
 
@@ -1035,12 +1068,7 @@ _BYTE_FC_COMPOSED = bool(os.environ.get("MOT_BYTE_FC_COMPOSED"))   # kernel-sele
 
 def _byte_fc_desc(tokens, tok_table, byte_table, byte_fc, bpt, norm_out, eps):
     """The descriptor's problem part, checked: tokens (B, T) int32 contiguous, the three float tensors of one dtype."""
-    if tokens.ndim == 1:
-        tokens = tokens[None]
-    if tokens.ndim != 2:
-        raise ValueError("tokens must be (B, T) or (T,)")
-    tok = tokens.to(torch.int32) if tokens.dtype != torch.int32 else tokens
-    tok = tok if tok.is_contiguous() else tok.contiguous()
+    tok = _tokens_2d(tokens)
     tt = _table(tok_table, "tok_table")
     bt = _table(byte_table, "byte_table", tt.dtype)
     w = _table(byte_fc, "byte_fc", tt.dtype)
@@ -1067,43 +1095,20 @@ def _byte_fc_mix_fwd(tokens, tok_table, byte_table, byte_fc, *, bpt, ids=None, t
     d.flags = capi.BYTE_FC_COMPOSED if (_BYTE_FC_COMPOSED if composed is None else composed) else 0
     B, T = tok.shape
     ids_padded = ids_pulled = None
-    if ttb is not None:
-        tab = _int_table(ttb, "byte_fc_mix")
-        if tab.shape[1] != bpt:
-            raise ValueError(f"ttb has {tab.shape[1]} slots per token, bpt={bpt}")
-        keep.append(tab)
-        d.id_source, d.pull_dir = capi.IDS_FROM_TTB, _PULLS[pull]
-        d.ttb, d.ttb_rows, d.ttb_elem_bytes = capi.ptr(tab), tab.shape[0], tab.element_size()
-        if return_ids:
-            ids_padded = torch.empty((B, T * bpt), dtype=torch.int64, device=dev)
-            ids_pulled = torch.empty((B, T * bpt), dtype=torch.int64, device=dev)
-            d.out_ids_padded, d.out_ids_pulled = capi.ptr(ids_padded), capi.ptr(ids_pulled)
-    else:
-        if ids is None:
-            raise ValueError("either ttb or ids must be given")
-        ia = _contig(ids, torch.int64, "ids")
-        if ia.numel() != B * T * bpt:
-            raise ValueError("byte ids must hold bytes_per_token ids per token")
-        keep.append(ia)
-        d.id_source, d.ids = capi.IDS_GIVEN, capi.ptr(ia)
+    _bind_byte_ids(d, keep, B=B, T=T, bpt=bpt, ids=ids, ttb=ttb, pull=pull, what="byte_fc_mix")
+    if ttb is not None and return_ids:
+        ids_padded, ids_pulled = _new_ids(B, T, bpt, dev), _new_ids(B, T, bpt, dev)
+        d.out_ids_padded, d.out_ids_pulled = capi.ptr(ids_padded), capi.ptr(ids_pulled)
     d.pad_byte, d.eot_byte = int(pad_byte), int(eot_byte)
     out = torch.empty((B, T, d.model_dim), dtype=tok_table.dtype, device=dev)
     if B * T == 0:   # an empty batch: nothing to launch (torch hands out null pointers for empty tensors, which the C validation refuses)
         return MixResult(out, ids_padded, ids_pulled) if return_ids else out
     d.out = capi.ptr(out)
-    if counters is not None:
-        if counters.dtype != torch.int64 or counters.numel() < 4 or counters.device != dev:
-            raise ValueError("counters must be an int64[4] tensor on the inputs' device")
-        d.counters = capi.ptr(counters)
+    _bind_counters(d, counters, dev)
     if row_rnorm is not None:
         assert row_rnorm.dtype == torch.float32 and row_rnorm.numel() == B * T and row_rnorm.is_contiguous()
         d.out_row_rnorm = capi.ptr(row_rnorm)
-    d.status = capi.ptr(capi.status_word(dev))
-    ws = _workspace(dev, capi.lib.mot_byte_fc_mix_workspace_bytes(C.byref(d)))
-    if ws is not None:
-        d.workspace, d.workspace_bytes = capi.ptr(ws), ws.numel()
-    capi.check(capi.lib.mot_byte_fc_mix_fwd(C.byref(d), capi.stream_of(dev)))
-    capi.after_call(dev)
+    _launch(dev, d, capi.lib.mot_byte_fc_mix_fwd, ws_bytes=capi.lib.mot_byte_fc_mix_workspace_bytes)
     return MixResult(out, ids_padded, ids_pulled) if return_ids else out
 
 
@@ -1139,18 +1144,8 @@ def byte_fc_mix_backward(grad_out, tokens, tok_table, byte_table, byte_fc, *, bp
     gr = capi.MotByteFcMixGrads()
     gr.struct_size = C.sizeof(capi.MotByteFcMixGrads)
     gr.grad_out, gr.d_tok, gr.d_byte, gr.d_byte_fc = capi.ptr(g), capi.ptr(res["tok_table"]), capi.ptr(res["byte_table"]), capi.ptr(res["byte_fc"])
-    if token_order is not None:
-        need = capi.lib.mot_token_order_ints(B * T, tok_table.shape[0])
-        if token_order.dtype != torch.int32 or token_order.numel() != need or token_order.device != dev or not token_order.is_contiguous():
-            raise ValueError(f"token_order must be the contiguous int32[{need}] tensor token_order(tokens, {tok_table.shape[0]}) returned")
-        gr.token_order = capi.ptr(token_order)
-        keep.append(token_order)
-    d.status = capi.ptr(capi.status_word(dev))
-    ws = _workspace(dev, capi.lib.mot_byte_fc_mix_bwd_workspace_bytes(C.byref(d)))
-    if ws is not None:
-        d.workspace, d.workspace_bytes = capi.ptr(ws), ws.numel()
-    capi.check(capi.lib.mot_byte_fc_mix_bwd(C.byref(d), C.byref(gr), capi.stream_of(dev)))
-    capi.after_call(dev)
+    _bind_token_order(gr, keep, token_order, B * T, tok_table.shape[0], dev)
+    _launch(dev, d, capi.lib.mot_byte_fc_mix_bwd, C.byref(gr), ws_bytes=capi.lib.mot_byte_fc_mix_bwd_workspace_bytes)
     return res
 
 
@@ -1184,16 +1179,9 @@ class _ByteFcMixFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gx, *_):
         tok_table, byte_table, byte_fc, tokens, ids, x, rn = ctx.saved_tensors
-        order = None
-        if ctx.order is not None:
-            order, ev = ctx.order
-            if ev is not None:
-                torch.cuda.current_stream(gx.device).wait_event(ev)
-            order.record_stream(torch.cuda.current_stream(gx.device))
         g = byte_fc_mix_backward(gx, tokens, tok_table.detach(), byte_table.detach(), byte_fc.detach(), ids=ids,
-                                 out=None if x is None else x.detach(), row_rnorm=rn, token_order=order, **ctx.kw)
-        like = lambda k, p: g[k].to(p.dtype).reshape(p.shape)   # bf16 parameters get their gradient rounded once, from the fp32 sums
-        return like("tok_table", tok_table), like("byte_table", byte_table), like("byte_fc", byte_fc), None, None
+                                 out=None if x is None else x.detach(), row_rnorm=rn, token_order=_ready_order(ctx.order, gx.device), **ctx.kw)
+        return _grad_like(g["tok_table"], tok_table), _grad_like(g["byte_table"], byte_table), _grad_like(g["byte_fc"], byte_fc), None, None
 
 
 def byte_fc_mix(tokens: torch.Tensor, tok_table: torch.Tensor, byte_table: torch.Tensor, byte_fc: torch.Tensor, *, bpt: int,
@@ -1243,11 +1231,7 @@ def _byte_cat_desc(tables, norm, bpt, eps, tokens, ids, what):
     keep = list(tabs)
     tok = None
     if tokens is not None:
-        tok = tokens[None] if tokens.ndim == 1 else tokens
-        if tok.ndim != 2:
-            raise ValueError("tokens must be (B, T) or (T,)")
-        tok = tok.to(torch.int32) if tok.dtype != torch.int32 else tok
-        tok = tok if tok.is_contiguous() else tok.contiguous()
+        tok = _tokens_2d(tokens)
         B, T = tok.shape
         keep.append(tok)
     else:
@@ -1274,43 +1258,25 @@ def _byte_cat_fwd(tables, *, bpt, norm, tokens=None, ids=None, ttb=None, pull=No
     dev = capi.require_device(*tables, tokens, ids, ttb)
     d, tabs, keep, (B, T) = _byte_cat_desc(tables, norm, bpt, eps, tokens, None if ttb is not None else ids, "byte_cat")
     ids_padded = ids_pulled = None
+    if ttb is not None and tokens is None:
+        raise ValueError("byte_cat: ids from the token->byte table need the tokens")
+    _bind_byte_ids(d, keep, B=B, T=T, bpt=bpt, ids=ids, ttb=ttb, pull=pull, what="byte_cat")
     if ttb is not None:
-        if tokens is None:
-            raise ValueError("byte_cat: ids from the token->byte table need the tokens")
-        tab = _int_table(ttb, "byte_cat")
-        if tab.shape[1] != bpt:
-            raise ValueError(f"ttb has {tab.shape[1]} slots per token, bpt={bpt}")
-        keep.append(tab)
-        d.id_source, d.pull_dir = capi.IDS_FROM_TTB, _PULLS[pull]
-        d.ttb, d.ttb_rows, d.ttb_elem_bytes = capi.ptr(tab), tab.shape[0], tab.element_size()
         used_only = return_ids == "used"   # the autograd node: only the tensor the gathers index (8 * bpt bytes per token, written once)
         if return_ids and not (used_only and d.pull_dir != capi.PULL_NONE):
-            ids_padded = torch.empty((B, T * bpt), dtype=torch.int64, device=dev)
+            ids_padded = _new_ids(B, T, bpt, dev)
             d.out_ids_padded = capi.ptr(ids_padded)
         if return_ids and not (used_only and d.pull_dir == capi.PULL_NONE):
-            ids_pulled = torch.empty((B, T * bpt), dtype=torch.int64, device=dev)
+            ids_pulled = _new_ids(B, T, bpt, dev)
             d.out_ids_pulled = capi.ptr(ids_pulled)
-    else:
-        if ids is None:
-            raise ValueError("either ttb or ids must be given")
-        ia = _contig(ids, torch.int64, "ids")
-        if ia.numel() != B * T * bpt:
-            raise ValueError("byte ids must hold bytes_per_token ids per token")
-        keep.append(ia)
-        d.id_source, d.ids = capi.IDS_GIVEN, capi.ptr(ia)
     d.pad_byte, d.eot_byte = int(pad_byte), int(eot_byte)
     outs = tuple(torch.empty((B, T, bpt * d.byte_dim), dtype=tabs[0].dtype, device=dev) for _ in tabs)
     if B * T == 0:   # an empty batch: nothing to launch
         return outs, ids_padded, ids_pulled
     for j, o in enumerate(outs):
         d.slot[j].out = capi.ptr(o)
-    if counters is not None:
-        if counters.dtype != torch.int64 or counters.numel() < 4 or counters.device != dev:
-            raise ValueError("counters must be an int64[4] tensor on the inputs' device")
-        d.counters = capi.ptr(counters)
-    d.status = capi.ptr(capi.status_word(dev))
-    capi.check(capi.lib.mot_byte_cat_fwd(C.byref(d), capi.stream_of(dev)))
-    capi.after_call(dev)
+    _bind_counters(d, counters, dev)
+    _launch(dev, d, capi.lib.mot_byte_cat_fwd)
     return outs, ids_padded, ids_pulled
 
 
@@ -1352,12 +1318,7 @@ def byte_cat_backward(grad_outs, tables, *, bpt, norm, ids, eps=None, into=None,
         if counters.dtype != torch.int64 or counters.numel() < 2 or counters.device != dev:
             raise ValueError("counters must be an int64[2] tensor on the inputs' device")
         d.counters = capi.ptr(counters)
-    d.status = capi.ptr(capi.status_word(dev))
-    ws = _workspace(dev, capi.lib.mot_byte_cat_bwd_workspace_bytes(C.byref(d)))
-    if ws is not None:
-        d.workspace, d.workspace_bytes = capi.ptr(ws), ws.numel()
-    capi.check(capi.lib.mot_byte_cat_bwd(C.byref(d), C.byref(gr), capi.stream_of(dev)))
-    capi.after_call(dev)
+    _launch(dev, d, capi.lib.mot_byte_cat_bwd, C.byref(gr), ws_bytes=capi.lib.mot_byte_cat_bwd_workspace_bytes)
     return res
 
 
@@ -1392,7 +1353,7 @@ class _ByteCatFn(torch.autograd.Function):
             return (None,) * (1 + ctx.n_out)
         res = byte_cat_backward(gs, [t.detach() for t in tables], ids=ids, **ctx.kw)
         # bf16 parameters get their gradient rounded once, from the fp32 sums
-        return (None, *[None if r is None else r.to(t.dtype) for r, t in zip(res, tables)])
+        return (None, *[_grad_like(r, t) for r, t in zip(res, tables)])
 
 
 def byte_cat(tables, *, bpt: int, norm, tokens: torch.Tensor | None = None, ids: torch.Tensor | None = None, ttb: torch.Tensor | None = None,
@@ -1432,8 +1393,7 @@ def _value_embeds_tokens(tokens, what):
         raise TypeError(f"{what}: tokens must be int32 or int64, got {tokens.dtype}")
     if tokens.ndim not in (1, 2):
         raise ValueError(f"{what}: tokens must be (T,) or (B, T), got {tuple(tokens.shape)}")
-    tok = tokens.to(torch.int32) if tokens.dtype != torch.int32 else tokens
-    return tok if tok.is_contiguous() else tok.contiguous()
+    return _int32(tokens)
 
 
 def _value_embeds_desc(tok, n_tables, rows, dim, dtype, what):
@@ -1472,9 +1432,7 @@ def _value_embeds_fwd(tokens, tables):
         return outs
     for j, (t, o) in enumerate(zip(tabs, outs)):
         d.tables[j], d.outs[j] = capi.ptr(t), capi.ptr(o)
-    d.status = capi.ptr(capi.status_word(dev))
-    capi.check(capi.lib.mot_value_embeds_fwd(C.byref(d), capi.stream_of(dev)))
-    capi.after_call(dev)
+    _launch(dev, d, capi.lib.mot_value_embeds_fwd)
     return outs
 
 
@@ -1511,17 +1469,8 @@ def _value_embeds_bwd(grad_outs, tokens, rows, dim, dtype, token_order, out=None
         gr.grad_outs[j], gr.d_tables[j] = capi.ptr(gc), capi.ptr(dt)
     if n == 0 or all(g is None for g in grad_outs):
         return res
-    if token_order is not None:
-        need = capi.lib.mot_token_order_ints(n, int(rows))
-        if token_order.dtype != torch.int32 or token_order.numel() != need or not token_order.is_contiguous():
-            raise ValueError(f"token_order must be the int32[{need}] tensor token_order(tokens, {rows}) returned")
-        gr.token_order = capi.ptr(token_order)
-    d.status = capi.ptr(capi.status_word(dev))
-    ws = _workspace(dev, capi.lib.mot_value_embeds_bwd_workspace_bytes(C.byref(d)))
-    if ws is not None:
-        d.workspace, d.workspace_bytes = capi.ptr(ws), ws.numel()
-    capi.check(capi.lib.mot_value_embeds_bwd(C.byref(d), C.byref(gr), capi.stream_of(dev)))
-    capi.after_call(dev)
+    _bind_token_order(gr, keep, token_order, n, rows, dev, contiguous="")
+    _launch(dev, d, capi.lib.mot_value_embeds_bwd, C.byref(gr), ws_bytes=capi.lib.mot_value_embeds_bwd_workspace_bytes)
     return res
 
 
@@ -1563,14 +1512,7 @@ class _ValueEmbedsFn(torch.autograd.Function):
         gs = [g if ctx.needs_input_grad[1 + j] else None for j, g in enumerate(grads[:n])]
         if all(g is None for g in gs):
             return (None,) * (1 + n)
-        order = None
-        if ctx.order is not None:
-            order, ev = ctx.order
-            cur = torch.cuda.current_stream(tokens.device)
-            if ev is not None:
-                cur.wait_event(ev)
-            order.record_stream(cur)
-        return (None, *_value_embeds_bwd(gs, tokens, rows, dim, dtype, order))
+        return (None, *_value_embeds_bwd(gs, tokens, rows, dim, dtype, _ready_order(ctx.order, tokens.device)))
 
 
 def value_embeds(tokens: torch.Tensor, tables) -> tuple:
@@ -1611,11 +1553,7 @@ def _value_mix_desc(tokens, tok_tables, byte_tables, weights, bpt, norm_out, eps
     Dt, Db, Do = tt[0].shape[1], bt[0].shape[1], ws[0].shape[0]
     if ws[0].shape[1] != Dt + int(bpt) * Db:
         raise ValueError(f"{what}: weights must be (out_dim, token_dim + bpt*byte_dim) = (*, {Dt} + {int(bpt)}*{Db}), got {tuple(ws[0].shape)}")
-    if tokens.ndim not in (1, 2):
-        raise ValueError(f"{what}: tokens must be (B, T) or (T,)")
-    t2 = tokens if tokens.ndim == 2 else tokens[None]
-    tok = t2.to(torch.int32) if t2.dtype != torch.int32 else t2
-    tok = tok if tok.is_contiguous() else tok.contiguous()
+    tok = _tokens_2d(tokens, f"{what}: tokens must be (B, T) or (T,)")
     tt, bt, ws = ([_table(t, f"{what}: {k} {j}") for j, t in enumerate(ts)] for k, ts in (("token table", tt), ("byte table", bt), ("weight", ws)))
     d = capi.MotValueMixDesc()
     d.struct_size = C.sizeof(capi.MotValueMixDesc)
@@ -1629,13 +1567,7 @@ def _value_mix_desc(tokens, tok_tables, byte_tables, weights, bpt, norm_out, eps
     return d, tok, [tok, tt, bt, ws]
 
 
-def _value_mix_ids(d, ids, bpt, keep, what):
-    ia = _contig(ids, torch.int64, "ids")
-    if ia.numel() != d.n_rows * d.tokens_per_row * bpt:
-        raise ValueError(f"{what}: byte ids must hold bytes_per_token ids per token, in per-token order (.., T*bpt)")
-    keep.append(ia)
-    d.id_source, d.ids = capi.IDS_GIVEN, capi.ptr(ia)
-    return ia
+_IDS_PER_TOKEN = "{}: byte ids must hold bytes_per_token ids per token, in per-token order (.., T*bpt)"   # value_mix and split_x0
 
 
 @torch.compiler.disable
@@ -1647,21 +1579,10 @@ def _value_mix_fwd(tokens, tok_tables, byte_tables, weights, *, bpt, ids=None, t
     d, tok, keep = _value_mix_desc(tokens, tok_tables, byte_tables, weights, bpt, norm_out, eps, "value_mix")
     B, T = tok.shape
     outs = tuple(torch.empty(tuple(tokens.shape) + (d.out_dim,), dtype=tok_tables[0].dtype, device=dev) for _ in range(d.n_slots))
-    ids_used = None
-    if ttb is not None:
-        tab = _int_table(ttb, "value_mix")
-        if tab.shape[1] != bpt:
-            raise ValueError(f"ttb has {tab.shape[1]} slots per token, bpt={bpt}")
-        keep.append(tab)
-        d.id_source, d.pull_dir = capi.IDS_FROM_TTB, _PULLS[pull]
-        d.ttb, d.ttb_rows, d.ttb_elem_bytes = capi.ptr(tab), tab.shape[0], tab.element_size()
-        if save:
-            ids_used = torch.empty((B, T * bpt), dtype=torch.int64, device=dev)
-            d.out_ids = capi.ptr(ids_used)
-    else:
-        if ids is None:
-            raise ValueError("either ttb or ids must be given")
-        ids_used = _value_mix_ids(d, ids, bpt, keep, "value_mix")
+    ids_used = _bind_byte_ids(d, keep, B=B, T=T, bpt=bpt, ids=ids, ttb=ttb, pull=pull, what="value_mix", ids_what=_IDS_PER_TOKEN.format("value_mix"))
+    if ttb is not None and save:
+        ids_used = _new_ids(B, T, bpt, dev)
+        d.out_ids = capi.ptr(ids_used)
     d.pad_byte, d.eot_byte = int(pad_byte), int(eot_byte)
     rns = None
     if save and norm_out:
@@ -1672,12 +1593,7 @@ def _value_mix_fwd(tokens, tok_tables, byte_tables, weights, *, bpt, ids=None, t
         d.slot[j].out = capi.ptr(o)
         if rns is not None:
             d.slot[j].out_row_rnorm = capi.ptr(rns[j])
-    d.status = capi.ptr(capi.status_word(dev))
-    ws = _workspace(dev, capi.lib.mot_value_mix_workspace_bytes(C.byref(d), 0))
-    if ws is not None:
-        d.workspace, d.workspace_bytes = capi.ptr(ws), ws.numel()
-    capi.check(capi.lib.mot_value_mix_fwd(C.byref(d), capi.stream_of(dev)))
-    capi.after_call(dev)
+    _launch(dev, d, capi.lib.mot_value_mix_fwd, ws_bytes=lambda p: capi.lib.mot_value_mix_workspace_bytes(p, 0))
     return outs, (ids_used if save else None), rns
 
 
@@ -1695,7 +1611,8 @@ def value_mix_backward(grad_outs, tokens, tok_tables, byte_tables, weights, *, b
     d, tok, keep = _value_mix_desc(tokens, tok_tables, byte_tables, weights, bpt, norm_out, eps, "value_mix_backward")
     if len(grad_outs) != d.n_slots:
         raise ValueError(f"value_mix_backward: {len(grad_outs)} gradients for {d.n_slots} slots")
-    _value_mix_ids(d, ids, bpt, keep, "value_mix_backward")
+    _bind_byte_ids(d, keep, B=d.n_rows, T=d.tokens_per_row, bpt=bpt, ids=ids, ttb=None, pull=None, what="value_mix_backward",
+                   ids_what=_IDS_PER_TOKEN.format("value_mix_backward"))
     n, dt = tok.numel(), tok_tables[0].dtype
     if norm_out and (outs is None or row_rnorms is None) and any(g is not None for g in grad_outs):
         raise ValueError("value_mix_backward with norm_out needs the forward's outputs and row_rnorms")
@@ -1724,17 +1641,8 @@ def value_mix_backward(grad_outs, tokens, tok_tables, byte_tables, weights, *, b
             d.slot[j].out, d.slot[j].out_row_rnorm = capi.ptr(xo), capi.ptr(rn)
     if n == 0 or all(g is None for g in grad_outs):
         return res
-    if token_order is not None:
-        need = capi.lib.mot_token_order_ints(n, d.tok_rows)
-        if token_order.dtype != torch.int32 or token_order.numel() != need or not token_order.is_contiguous():
-            raise ValueError(f"token_order must be the contiguous int32[{need}] tensor token_order(tokens, {d.tok_rows}) returned")
-        gr.token_order = capi.ptr(token_order)
-    d.status = capi.ptr(capi.status_word(dev))
-    ws = _workspace(dev, capi.lib.mot_value_mix_workspace_bytes(C.byref(d), 1))
-    if ws is not None:
-        d.workspace, d.workspace_bytes = capi.ptr(ws), ws.numel()
-    capi.check(capi.lib.mot_value_mix_bwd(C.byref(d), C.byref(gr), capi.stream_of(dev)))
-    capi.after_call(dev)
+    _bind_token_order(gr, keep, token_order, n, d.tok_rows, dev)
+    _launch(dev, d, capi.lib.mot_value_mix_bwd, C.byref(gr), ws_bytes=lambda p: capi.lib.mot_value_mix_workspace_bytes(p, 1))
     return res
 
 
@@ -1764,16 +1672,10 @@ class _ValueMixFn(torch.autograd.Function):
         gs = [g if any(ctx.needs_input_grad[2 + k * n + j] for k in range(3)) else None for j, g in enumerate(grads[:n])]
         if all(g is None for g in gs):
             return (None,) * (2 + 3 * n)
-        order = None
-        if ctx.order is not None:
-            order, ev = ctx.order
-            cur = torch.cuda.current_stream(tokens.device)
-            if ev is not None:
-                cur.wait_event(ev)
-            order.record_stream(cur)
         res = value_mix_backward(gs, tokens, [t.detach() for t in tt], [t.detach() for t in bt], [t.detach() for t in ws], ids=ids,
-                                 outs=None if outs is None else [o.detach() for o in outs], row_rnorms=rns, token_order=order, **ctx.kw)
-        pick = lambda k, ps: tuple(None if r is None else r[k].to(p.dtype) for r, p in zip(res, ps))   # bf16: the fp32 sums rounded once
+                                 outs=None if outs is None else [o.detach() for o in outs], row_rnorms=rns,
+                                 token_order=_ready_order(ctx.order, tokens.device), **ctx.kw)
+        pick = lambda k, ps: tuple(None if r is None else _grad_like(r[k], p) for r, p in zip(res, ps))   # bf16: the fp32 sums rounded once
         return (None, None, *pick("tok_table", tt), *pick("byte_table", bt), *pick("weight", ws))
 
 
@@ -1820,11 +1722,7 @@ def _split_x0_desc(tokens, tok_table, byte_table, scale_tok, scale_byte, bpt, ep
     capi.dtype_code(tok_table.dtype)
     if tok_table.ndim != 2 or byte_table.ndim != 2:
         raise ValueError(f"{what}: tables must be 2-D, got {tuple(tok_table.shape)} and {tuple(byte_table.shape)}")
-    if tokens.ndim not in (1, 2):
-        raise ValueError(f"{what}: tokens must be (B, T) or (T,)")
-    t2 = tokens if tokens.ndim == 2 else tokens[None]
-    tok = t2.to(torch.int32) if t2.dtype != torch.int32 else t2
-    tok = tok if tok.is_contiguous() else tok.contiguous()
+    tok = _tokens_2d(tokens, f"{what}: tokens must be (B, T) or (T,)")
     tt, bt = _table(tok_table, f"{what}: token table"), _table(byte_table, f"{what}: byte table")
     st, sb = _split_x0_scalar(scale_tok, f"{what}: scale_tok"), _split_x0_scalar(scale_byte, f"{what}: scale_byte")
     d = capi.MotSplitX0Desc()
@@ -1836,15 +1734,6 @@ def _split_x0_desc(tokens, tok_table, byte_table, scale_tok, scale_byte, bpt, ep
     d.scale_tok, d.scale_byte = capi.ptr(st), capi.ptr(sb)
     d.eps = float(eps or 0.0)
     return d, tok, [tok, tt, bt, st, sb]
-
-
-def _split_x0_ids(d, ids, bpt, keep, what):
-    ia = _contig(ids, torch.int64, "ids")
-    if ia.numel() != d.n_rows * d.tokens_per_row * bpt:
-        raise ValueError(f"{what}: byte ids must hold bytes_per_token ids per token, in per-token order (.., T*bpt)")
-    keep.append(ia)
-    d.id_source, d.ids = capi.IDS_GIVEN, capi.ptr(ia)
-    return ia
 
 
 def _split_x0_want(want):
@@ -1866,40 +1755,21 @@ def _split_x0_fwd(tokens, tok_table, byte_table, scale_tok, scale_byte, *, bpt, 
     d, tok, keep = _split_x0_desc(tokens, tok_table, byte_table, scale_tok, scale_byte, bpt, eps, "split_x0")
     B, T = tok.shape
     outs = {w: torch.empty(tuple(tokens.shape) + (d.model_dim,), dtype=tok_table.dtype, device=dev) for w in want}
-    ids_used = None
-    if ttb is not None:
-        tab = _int_table(ttb, "split_x0")
-        if tab.shape[1] != bpt:
-            raise ValueError(f"ttb has {tab.shape[1]} slots per token, bpt={bpt}")
-        keep.append(tab)
-        d.id_source, d.pull_dir = capi.IDS_FROM_TTB, _PULLS[pull]
-        d.ttb, d.ttb_rows, d.ttb_elem_bytes = capi.ptr(tab), tab.shape[0], tab.element_size()
-        if save or return_ids:
-            ids_used = torch.empty((B, T * bpt), dtype=torch.int64, device=dev)
-            d.out_ids_pulled = capi.ptr(ids_used)   # without a pull the "pulled" ids are the table's rows
-        if return_ids:
-            ids_padded = torch.empty((B, T * bpt), dtype=torch.int64, device=dev)
-            d.out_ids_padded = capi.ptr(ids_padded)
-    else:
-        if ids is None:
-            raise ValueError("either ttb or ids must be given")
-        if return_ids:
-            raise ValueError("split_x0: return_ids needs the token->byte table (ttb)")
-        ids_used = _split_x0_ids(d, ids, bpt, keep, "split_x0")
+    if return_ids and ttb is None and ids is not None:
+        raise ValueError("split_x0: return_ids needs the token->byte table (ttb)")
+    ids_used = _bind_byte_ids(d, keep, B=B, T=T, bpt=bpt, ids=ids, ttb=ttb, pull=pull, what="split_x0", ids_what=_IDS_PER_TOKEN.format("split_x0"))
+    if ttb is not None and (save or return_ids):
+        ids_used = _new_ids(B, T, bpt, dev)
+        d.out_ids_pulled = capi.ptr(ids_used)   # without a pull the "pulled" ids are the table's rows
+    if ttb is not None and return_ids:
+        ids_padded = _new_ids(B, T, bpt, dev)
+        d.out_ids_padded = capi.ptr(ids_padded)
     d.pad_byte, d.eot_byte = int(pad_byte), int(eot_byte)
-    if counters is not None:
-        if counters.dtype != torch.int64 or counters.numel() < 4 or counters.device != dev:
-            raise ValueError("counters must be an int64[4] tensor on the inputs' device")
-        d.counters = capi.ptr(counters)
+    _bind_counters(d, counters, dev)
     if B * T == 0:   # an empty batch: nothing to launch
         return (outs, ids_padded, ids_used) if return_ids else (outs, ids_used)
     d.out_x0t, d.out_x0b, d.out_x = (capi.ptr(outs.get(w)) for w in _SPLIT_X0_OUTS)
-    d.status = capi.ptr(capi.status_word(dev))
-    ws = _workspace(dev, capi.lib.mot_splitx_workspace_bytes(C.byref(d), 0))
-    if ws is not None:
-        d.workspace, d.workspace_bytes = capi.ptr(ws), ws.numel()
-    capi.check(capi.lib.mot_splitx_fwd(C.byref(d), capi.stream_of(dev)))
-    capi.after_call(dev)
+    _launch(dev, d, capi.lib.mot_splitx_fwd, ws_bytes=lambda p: capi.lib.mot_splitx_workspace_bytes(p, 0))
     if return_ids:
         return outs, ids_padded, ids_used
     return outs, (ids_used if save else None)
@@ -1920,7 +1790,8 @@ def split_x0_backward(grad_x0t, grad_x0b, grad_x, tokens, tok_table, byte_table,
     if all(g is None for g in gs):
         raise ValueError("split_x0_backward: grad_x0t, grad_x0b and grad_x are all None")
     d, tok, keep = _split_x0_desc(tokens, tok_table, byte_table, scale_tok, scale_byte, bpt, eps, "split_x0_backward")
-    _split_x0_ids(d, ids, bpt, keep, "split_x0_backward")
+    _bind_byte_ids(d, keep, B=d.n_rows, T=d.tokens_per_row, bpt=bpt, ids=ids, ttb=None, pull=None, what="split_x0_backward",
+                   ids_what=_IDS_PER_TOKEN.format("split_x0_backward"))
     n, dt = tok.numel(), tok_table.dtype
     gr = capi.MotSplitX0Grads()
     gr.struct_size = C.sizeof(capi.MotSplitX0Grads)
@@ -1956,17 +1827,8 @@ def split_x0_backward(grad_x0t, grad_x0b, grad_x, tokens, tok_table, byte_table,
         keep.append(sc)
     if n == 0 or not res:
         return res
-    if token_order is not None:
-        need = capi.lib.mot_token_order_ints(n, d.tok_rows)
-        if token_order.dtype != torch.int32 or token_order.numel() != need or not token_order.is_contiguous():
-            raise ValueError(f"token_order must be the contiguous int32[{need}] tensor token_order(tokens, {d.tok_rows}) returned")
-        gr.token_order = capi.ptr(token_order)
-    d.status = capi.ptr(capi.status_word(dev))
-    ws = _workspace(dev, capi.lib.mot_splitx_workspace_bytes(C.byref(d), 1))
-    if ws is not None:
-        d.workspace, d.workspace_bytes = capi.ptr(ws), ws.numel()
-    capi.check(capi.lib.mot_splitx_bwd(C.byref(d), C.byref(gr), capi.stream_of(dev)))
-    capi.after_call(dev)
+    _bind_token_order(gr, keep, token_order, n, d.tok_rows, dev)
+    _launch(dev, d, capi.lib.mot_splitx_bwd, C.byref(gr), ws_bytes=lambda p: capi.lib.mot_splitx_workspace_bytes(p, 1))
     return res
 
 
@@ -1992,16 +1854,9 @@ class _SplitX0Fn(torch.autograd.Function):
         names = [n for j, n in enumerate(("tok_table", "byte_table", "scale_tok", "scale_byte")) if ctx.needs_input_grad[2 + j]]
         if all(v is None for v in g.values()) or not names:
             return (None,) * 6
-        order = None
-        if ctx.order is not None:
-            order, ev = ctx.order
-            cur = torch.cuda.current_stream(tokens.device)
-            if ev is not None:
-                cur.wait_event(ev)
-            order.record_stream(cur)
         r = split_x0_backward(g.get("x0t"), g.get("x0b"), g.get("x"), tokens, tok_table.detach(), byte_table.detach(), scale_tok.detach(),
-                              scale_byte.detach(), ids=ids, token_order=order, want_grads=names, **ctx.kw)
-        pick = lambda k, p: None if k not in r else r[k].to(p.dtype).reshape(p.shape)   # bf16 byte table: the fp32 sums rounded once
+                              scale_byte.detach(), ids=ids, token_order=_ready_order(ctx.order, tokens.device), want_grads=names, **ctx.kw)
+        pick = lambda k, p: _grad_like(r.get(k), p)   # bf16 byte table: the fp32 sums rounded once
         return (None, None, pick("tok_table", tok_table), pick("byte_table", byte_table), pick("scale_tok", scale_tok), pick("scale_byte", scale_byte))
 
 
