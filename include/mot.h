@@ -281,6 +281,40 @@ int mot_embed_mix_bwd(const MotEmbedMixDesc *fwd /* host */, const MotEmbedMixGr
                       mot_stream_t stream);
 
 /*
+ * The write-once backward of mot_embed_mix_fwd (opt-in; mot_embed_mix_bwd above is unchanged).  `fwd` as for mot_embed_mix_bwd
+ * (id_source == MOT_IDS_GIVEN), with a workspace of mot_embed_mix_bwd_once_workspace_bytes(fwd).
+ *   d_tok_table[r, :] = round_to_dtype(sum over the positions p with tokens[p] == r of d a_p): the sum in fp32 in ascending
+ *   position order (cut at multiples of 64 sorted slots; the pieces of a group that crosses a cut in ascending slice order, in
+ *   four fixed quarters), rounded once, +0 where r does not occur.  EVERY element is written exactly once: the caller zeroes
+ *   nothing, no atomic touches a gradient element, and the same call gives the same bits -- with a caller's token_order or one made
+ *   in the call, eagerly or replayed from a graph (no memset or memcpy node is used).
+ *   d_byte_table (fp32) is cleared by the call with a kernel and then summed in 64-bit fixed point (integer atomics in LDS and
+ *   global memory: the sums do not depend on the order of the adds), slab by slab of 16 384 positions;
+ *   d_scale_tok / d_scale_byte (fp32) are written, summed in a fixed order.
+ * With dtype == MOT_BF16 the forward quantities are recomputed from the tables in fp32 and are not re-rounded.
+ * Built: MOT_MIX_SUM, MOT_MIX_NOOP, MOT_MIX_CONCAT; fp32 and bf16; one id tensor; every norm / scale combination that
+ * mot_embed_mix_bwd takes for those modes; tok_dim and byte_dim multiples of the 16-byte vector, model_dim <= 2048,
+ * tok_rows < 2^21 - 1.  MOT_MIX_CONCAT_LINEAR, MOT_MIX_MEAN, ids_b and MOT_IDS_FROM_TTB return MOT_EUNSUPPORTED before any HIP call
+ * (the message starts "embed_mix_bwd_once" and names the follow-up); a missing or short workspace MOT_EWORKSPACE; null pointers and a
+ * bad struct_size MOT_EINVAL; an empty batch MOT_OK without a launch.  Out-of-range ids are clamped to row 0 and flagged in
+ * fwd->status.  No piece of the workspace is proportional to n_tokens x model_dim: it holds the token order and the canonical
+ * positions, 16 bytes of scalars per position, the slice pieces and ONE slab (16 384 positions) of the byte part's fp32 rows.
+ */
+typedef struct MotEmbedMixGradsOnce {
+    uint32_t struct_size; /* sizeof(MotEmbedMixGradsOnce) */
+    uint32_t reserved;    /* must be 0 */
+    const void *grad_out; /* [B, T, model_dim] in fwd->dtype */
+    void *d_tok_table;    /* [tok_rows, tok_dim] in fwd->dtype, WRITTEN (every element, once); NULL = not wanted */
+    float *d_byte_table;  /* [byte_rows, byte_dim] fp32, OVERWRITTEN (the call clears it with a kernel); NULL = not wanted */
+    float *d_scale_tok;   /* fp32 scalar, WRITTEN; NULL = not wanted */
+    float *d_scale_byte;  /* fp32 scalar, WRITTEN; NULL = not wanted */
+    const int32_t *token_order; /* optional, as in MotEmbedMixGrads */
+} MotEmbedMixGradsOnce;
+size_t mot_embed_mix_grads_once_size(void); /* sizeof(MotEmbedMixGradsOnce) in this build, for bindings */
+size_t mot_embed_mix_bwd_once_workspace_bytes(const MotEmbedMixDesc *fwd /* host */); /* 0 for a descriptor the call would refuse */
+int mot_embed_mix_bwd_once(const MotEmbedMixDesc *fwd /* host */, const MotEmbedMixGradsOnce *grads /* host */, mot_stream_t stream);
+
+/*
  * CONCAT_LINEAR runs as several kernels inside one call (index kernels when the ids come from the ttb, a gather that
  * writes the concat operand into the workspace, a dense MFMA kernel, a row-norm pass); in bf16, with one id tensor, embedding
  * dims that are multiples of 8, a concat width that is a multiple of 32 and model_dim 256/512/768/1024, everything behind the

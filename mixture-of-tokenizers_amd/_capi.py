@@ -64,6 +64,7 @@ EXPORTS = (
     "mot_value_embeds_desc_size", "mot_value_embeds_bwd_workspace_bytes", "mot_value_embeds_fwd", "mot_value_embeds_bwd",
     "mot_value_mix_desc_size", "mot_value_mix_workspace_bytes", "mot_value_mix_fwd", "mot_value_mix_bwd",
     "mot_splitx_desc_size", "mot_splitx_workspace_bytes", "mot_splitx_fwd", "mot_splitx_bwd",
+    "mot_embed_mix_grads_once_size", "mot_embed_mix_bwd_once_workspace_bytes", "mot_embed_mix_bwd_once",
 )
 SWA_NO_RESIDUAL, SWA_ONE_RESIDUAL, SWA_TWO_RESIDUAL = 0, 1, 2
 
@@ -93,6 +94,15 @@ class MotEmbedMixGrads(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("grad_out", C.c_void_p),
         ("d_tok_table", C.c_void_p), ("d_byte_table", C.c_void_p), ("d_weight", C.c_void_p), ("d_bias", C.c_void_p),
+        ("d_scale_tok", C.c_void_p), ("d_scale_byte", C.c_void_p), ("token_order", C.c_void_p),
+    ]
+
+
+class MotEmbedMixGradsOnce(C.Structure):
+    """Mirror of struct MotEmbedMixGradsOnce (include/mot.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("grad_out", C.c_void_p),
+        ("d_tok_table", C.c_void_p), ("d_byte_table", C.c_void_p),
         ("d_scale_tok", C.c_void_p), ("d_scale_byte", C.c_void_p), ("token_order", C.c_void_p),
     ]
 
@@ -378,6 +388,11 @@ def _load() -> C.CDLL:
     lib.mot_splitx_fwd.restype = C.c_int
     lib.mot_splitx_bwd.argtypes = [C.POINTER(MotSplitX0Desc), C.POINTER(MotSplitX0Grads), vp]
     lib.mot_splitx_bwd.restype = C.c_int
+    lib.mot_embed_mix_grads_once_size.restype = C.c_size_t
+    lib.mot_embed_mix_bwd_once_workspace_bytes.restype = C.c_size_t
+    lib.mot_embed_mix_bwd_once_workspace_bytes.argtypes = [C.POINTER(MotEmbedMixDesc)]
+    lib.mot_embed_mix_bwd_once.argtypes = [C.POINTER(MotEmbedMixDesc), C.POINTER(MotEmbedMixGradsOnce), vp]
+    lib.mot_embed_mix_bwd_once.restype = C.c_int
     for name in ("mot_tokens_to_bytes", "mot_pull_bytes", "mot_create_batch", "mot_char_matrix", "mot_gather_rows", "mot_embed_mix_fwd",
                  "mot_embed_mix_bwd"):
         getattr(lib, name).restype = C.c_int
@@ -403,6 +418,8 @@ def _load() -> C.CDLL:
         raise ImportError("MotValueMixDesc layout mismatch between include/mot.h and _capi.py")
     if lib.mot_splitx_desc_size() != C.sizeof(MotSplitX0Desc):
         raise ImportError("MotSplitX0Desc layout mismatch between include/mot.h and _capi.py")
+    if lib.mot_embed_mix_grads_once_size() != C.sizeof(MotEmbedMixGradsOnce):
+        raise ImportError("MotEmbedMixGradsOnce layout mismatch between include/mot.h and _capi.py")
     return lib
 
 

@@ -231,6 +231,16 @@ int mot_embed_mix_bwd(const MotEmbedMixDesc *desc, const MotEmbedMixGrads *grads
     return launch_embed_mix_bwd(d, *grads, (hipStream_t)stream);
 }
 
+size_t mot_embed_mix_grads_once_size(void) { return sizeof(MotEmbedMixGradsOnce); }
+
+size_t mot_embed_mix_bwd_once_workspace_bytes(const MotEmbedMixDesc *desc) { return embed_mix_bwd_once_workspace_bytes(desc); }
+
+int mot_embed_mix_bwd_once(const MotEmbedMixDesc *desc, const MotEmbedMixGradsOnce *grads, mot_stream_t stream) {
+    if (int rc = embed_mix_bwd_once_check(desc, grads)) return rc;
+    if (desc->n_rows == 0 || desc->tokens_per_row == 0) return MOT_OK;
+    return launch_embed_mix_bwd_once(*desc, *grads, (hipStream_t)stream);
+}
+
 int mot_embed_mix_fwd(const MotEmbedMixDesc *desc, mot_stream_t stream) {
     int rc = validate_embed_mix(desc);
     if (rc) return rc;

@@ -141,6 +141,16 @@ int launch_value_embeds_bwd(const MotValueEmbedsDesc &d, const MotValueEmbedsGra
 size_t token_sums_ws_bytes(int64_t n, int64_t rows, int dim, int dtype);
 int launch_token_sums_f32(const int32_t *tokens, int64_t n, int64_t rows, int dim, int dtype, const float *g, int g_ld, void *d_table,
                           const int32_t *order, bool prepare, char *ws, uint32_t *status, hipStream_t stream);
+// the two ends of those sums for a unit that forms the slice sums itself (mot_once.hip), over the same workspace: the order (unless
+// the caller brings one) and the canonical positions, then the closing rows kernel over the pieces at V.part ([slice][head, tail][dim])
+struct TokenSumsView { const int32_t *counts, *starts, *pos_sorted, *id_sorted; int32_t *canon; float *part; };
+int launch_token_canon(const int32_t *tokens, int64_t n, int64_t rows, int dim, int dtype, const int32_t *order, char *ws, uint32_t *status,
+                       hipStream_t stream, TokenSumsView *V);
+int launch_token_rows_close(const TokenSumsView &V, int64_t n, int64_t rows, int dim, int dtype, void *d_table, hipStream_t stream);
+// the write-once backward of the fused front-end (mot_once.hip): validation before any HIP call, then the launches
+int embed_mix_bwd_once_check(const MotEmbedMixDesc *d, const MotEmbedMixGradsOnce *g);
+size_t embed_mix_bwd_once_workspace_bytes(const MotEmbedMixDesc *d);   // 0 for a descriptor the call would refuse
+int launch_embed_mix_bwd_once(const MotEmbedMixDesc &d, const MotEmbedMixGradsOnce &g, hipStream_t stream);
 // mixture-of-tokenizers value embeddings (mot_valuemix.hip): validation before any HIP call (g: backward only), then the launches
 int value_mix_check(const MotValueMixDesc *d, const MotValueMixGrads *g, bool backward);
 size_t value_mix_workspace_bytes(const MotValueMixDesc *d, bool backward);   // 0 for a descriptor the call would refuse

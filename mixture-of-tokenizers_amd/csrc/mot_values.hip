@@ -499,4 +499,31 @@ int launch_token_sums_f32(const int32_t *tokens, int64_t n, int64_t rows, int di
     return bf ? ve_launch_sums<float, __bf16>(A, L.slices, stream) : ve_launch_sums<float, float>(A, L.slices, stream);
 }
 
+// ------------------------------------------------------------------------------------------ the two ends for a caller's own slices kernel (mot_once.hip)
+// The same workspace (token_sums_ws_bytes) for ONE table whose slice sums another unit forms: the order (unless the caller brings
+// one) and the canonical positions in front, the closing rows kernel behind.  The pieces lie at V.part as ve_bwd_slices_kernel lays
+// them out with one slot: [slice][2: head, tail][dim] fp32.
+int launch_token_canon(const int32_t *tokens, int64_t n, int64_t rows, int dim, int dtype, const int32_t *order, char *ws, uint32_t *status,
+                       hipStream_t stream, TokenSumsView *V) {
+    const VeLayout L = value_embeds_layout(token_sums_desc(n, rows, dim, dtype));
+    VeBwdArgs A{};
+    A.N = n; A.rows = (int)rows; A.D = A.g_ld = dim; A.nslot = 1;
+    if (int rc = ve_order_and_canon(A, L, tokens, order, ws, status, stream)) return rc;
+    *V = TokenSumsView{A.counts, A.starts, A.pos_sorted, A.id_sorted, A.canon, A.part};
+    return MOT_OK;
+}
+
+int launch_token_rows_close(const TokenSumsView &V, int64_t n, int64_t rows, int dim, int dtype, void *d_table, hipStream_t stream) {
+    const bool bf = dtype == MOT_BF16;
+    VeBwdArgs A{};
+    A.counts = V.counts; A.starts = V.starts; A.pos_sorted = V.pos_sorted; A.id_sorted = V.id_sorted; A.canon = V.canon; A.part = V.part;
+    A.N = n; A.rows = (int)rows; A.D = A.g_ld = dim; A.nslot = 1;
+    A.nck = (dim / (bf ? 8 : 4) + 63) / 64;
+    A.d[0] = d_table;
+    const dim3 rg((unsigned)(((int64_t)A.rows + kVeRowIds - 1) / kVeRowIds), (unsigned)A.nck);
+    if (bf) hipLaunchKernelGGL(ve_bwd_rows_kernel<__bf16>, rg, dim3(kThreads), 0, stream, A);
+    else hipLaunchKernelGGL(ve_bwd_rows_kernel<float>, rg, dim3(kThreads), 0, stream, A);
+    return check_launch("ve_bwd_rows_kernel");
+}
+
 }  // namespace mot

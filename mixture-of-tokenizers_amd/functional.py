@@ -8,6 +8,7 @@ them as opaque calls.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from dataclasses import dataclass
 
@@ -621,12 +622,135 @@ def embed_mix_backward(grad_out: torch.Tensor, tokens: torch.Tensor, tok_table: 
     return out
 
 
+_ONCE_MODES = ("sum", "noop", "concat")
+
+
+def _write_once_refusal(kw) -> str | None:
+    """Why mot_embed_mix_bwd_once would refuse these forward arguments (None: it takes them)."""
+    pre = "mixture-of-tokenizers_amd: embed_mix(write_once=True): "
+    mode = kw.get("mode")
+    if mode not in _ONCE_MODES:
+        return pre + f"mode '{mode}' is not built (embed_mix_bwd_once covers 'sum', 'noop' and 'concat'); use write_once=False"
+    if mode != "noop" and (kw.get("ids_b") is not None or kw.get("add_padded")):
+        return pre + "a second id tensor (ids_b / add_padded) is not built (embed_mix_bwd_once takes one id tensor); use write_once=False"
+    return None
+
+
+@torch.compiler.disable
+def embed_mix_backward_once(grad_out: torch.Tensor, tokens: torch.Tensor, tok_table: torch.Tensor, byte_table: torch.Tensor | None = None, *,
+                            mode: str, bpt: int = 0, ids_a: torch.Tensor | None = None,
+                            norm_tok: bool = False, norm_byte: bool = False, norm_out: bool = False, eps: float | None = None,
+                            scale_tok: torch.Tensor | None = None, scale_byte: torch.Tensor | None = None,
+                            token_order: torch.Tensor | None = None, out: dict | None = None, want_grads=None) -> dict:
+    """One call of mot_embed_mix_bwd_once.  Returns {tok_table (the table's dtype), byte_table (fp32), scale_tok, scale_byte (fp32)}:
+    every element written by the call (the byte table is cleared by a kernel first), so `out=` may name `torch.empty` buffers of those
+    dtypes and shapes.  The token-table gradient is the fp32 sum in ascending position order, rounded once, +0 where an id does not
+    occur: the same bits on every run.  `want_grads`: the keys to compute (default: all that apply); `token_order` as in
+    :func:`embed_mix_backward`."""
+    refusal = _write_once_refusal({"mode": mode})
+    if refusal:
+        raise NotImplementedError(refusal)
+    m = _MODES[mode]
+    if tokens.ndim == 1:
+        tokens = tokens[None]
+    dev = capi.require_device(grad_out, tokens, tok_table, byte_table, ids_a, scale_tok, scale_byte)
+    tok = _int32(tokens)
+    B, T = tok.shape
+    dt = tok_table.dtype
+    tt = _contig(tok_table, dt, "tok_table")
+    g = _contig(grad_out, dt, "grad_out")
+    d = capi.MotEmbedMixDesc()
+    d.struct_size = C.sizeof(capi.MotEmbedMixDesc)
+    d.dtype = capi.dtype_code(dt)
+    d.n_rows, d.tokens_per_row, d.bpt, d.mode = B, T, int(bpt), m
+    d.tokens = capi.ptr(tok)
+    d.tok_table, d.tok_rows, d.tok_dim, d.model_dim = capi.ptr(tt), tt.shape[0], tt.shape[1], tt.shape[1]
+    keep = [tok, tt, g]
+    shapes = {"tok_table": (tt.shape, dt)}
+    if m != capi.MIX_NOOP:
+        if byte_table is None or ids_a is None:
+            raise ValueError("byte_table and ids_a are required unless mode == 'noop'")
+        bt = _contig(byte_table, dt, "byte_table")
+        ia = _contig(ids_a, torch.int64, "ids_a")
+        if ia.numel() != B * T * int(bpt):
+            raise ValueError("byte ids must hold bytes_per_token ids per token")
+        keep += [bt, ia]
+        d.byte_table, d.byte_rows, d.byte_dim = capi.ptr(bt), bt.shape[0], bt.shape[1]
+        d.id_source, d.ids_a = capi.IDS_GIVEN, capi.ptr(ia)
+        shapes["byte_table"] = (bt.shape, torch.float32)
+        if m == capi.MIX_CONCAT:
+            d.model_dim = tt.shape[1] + int(bpt) * bt.shape[1]
+    if g.numel() != B * T * d.model_dim:
+        raise ValueError(f"grad_out must hold (B, T, {d.model_dim}) elements")
+    d.norm_tok, d.norm_byte, d.norm_out = int(norm_tok), int(norm_byte), int(norm_out)
+    d.eps = float(eps or 0.0)
+    d.scale_tok, d.scale_byte = capi.ptr(scale_tok), capi.ptr(scale_byte)
+    for k, sc in (("scale_tok", scale_tok), ("scale_byte", scale_byte)):
+        if sc is not None:
+            if sc.dtype != torch.float32 or sc.numel() != 1:
+                raise TypeError(f"{k}: expected a 1-element float32 device tensor, got {sc.dtype} x {sc.numel()}")
+            shapes[k] = ((1,), torch.float32)
+    want = set(shapes) if want_grads is None else set(want_grads)
+    if not want <= set(shapes):
+        raise ValueError(f"want_grads {sorted(want - set(shapes))} do not apply to this call (it has {sorted(shapes)})")
+    out = dict(out or {})
+    res = {}
+    for k in ("tok_table", "byte_table", "scale_tok", "scale_byte"):
+        if k not in want:
+            continue
+        shape, kdt = shapes[k]
+        buf = out.get(k)
+        if buf is None:
+            buf = torch.empty(shape, dtype=kdt, device=dev)
+        elif buf.dtype != kdt or buf.numel() != math.prod(shape) or not buf.is_contiguous() or buf.device != dev:
+            raise ValueError(f"out['{k}'] must be a contiguous {kdt} tensor of {tuple(shape)} on the inputs' device")
+        res[k] = buf
+    gr = capi.MotEmbedMixGradsOnce()
+    gr.struct_size = C.sizeof(capi.MotEmbedMixGradsOnce)
+    gr.grad_out = capi.ptr(g)
+    gr.d_tok_table, gr.d_byte_table = capi.ptr(res.get("tok_table")), capi.ptr(res.get("byte_table"))
+    gr.d_scale_tok, gr.d_scale_byte = capi.ptr(res.get("scale_tok")), capi.ptr(res.get("scale_byte"))
+    _bind_token_order(gr, keep, token_order, B * T, tt.shape[0], dev)
+    _launch(dev, d, capi.lib.mot_embed_mix_bwd_once, C.byref(gr), ws_bytes=capi.lib.mot_embed_mix_bwd_once_workspace_bytes)
+    return res
+
+
+class _EmbedMixOnceFn(torch.autograd.Function):
+    """Autograd node of the fused front-end with the write-once backward: forward = the launch of _EmbedMixFn, backward = one
+    mot_embed_mix_bwd_once call, whose token-table gradient is handed to autograd in the parameter's dtype as it stands."""
+
+    @staticmethod
+    def forward(ctx, tok_table, byte_table, scale_tok, scale_byte, tokens, kw):
+        return _EmbedMixFn.forward(ctx, tok_table, byte_table, scale_tok, scale_byte, None, None, tokens, kw)
+
+    @staticmethod
+    def backward(ctx, gx, *_):
+        tok_table, byte_table, scale_tok, scale_byte, tokens, ids_a = ctx.saved_tensors[:6]
+        params = {"tok_table": tok_table, "byte_table": byte_table, "scale_tok": scale_tok, "scale_byte": scale_byte}
+        want = [k for i, k in enumerate(params) if params[k] is not None and ctx.needs_input_grad[i]]
+        kw = {k: v for k, v in ctx.kw.items() if k != "bytes_first"}
+        g = embed_mix_backward_once(gx, tokens, tok_table.detach(), None if byte_table is None else byte_table.detach(),
+                                    ids_a=ids_a, token_order=_ready_order(ctx.order, gx.device),
+                                    scale_tok=None if scale_tok is None else scale_tok.detach(),
+                                    scale_byte=None if scale_byte is None else scale_byte.detach(), want_grads=want, **kw)
+        return tuple(_grad_like(g.get(k), p) if p is not None else None for k, p in params.items()) + (None, None)
+
+
 def embed_mix(tokens: torch.Tensor, tok_table: torch.Tensor, byte_table: torch.Tensor | None = None, *,
-              scale_tok: torch.Tensor | None = None, scale_byte: torch.Tensor | None = None, **kw):
+              scale_tok: torch.Tensor | None = None, scale_byte: torch.Tensor | None = None, write_once: bool = False, **kw):
     """The fused front-end (see `_embed_mix_fwd` for the arguments).  With autograd enabled and
     differentiable parameters it records one backward node: modes "sum", "noop", "concat", "concat_linear" with
     float32 or bfloat16 tables; "mean" without an output norm.  Anything else raises here,
-    at forward time, rather than in backward()."""
+    at forward time, rather than in backward().
+
+    `write_once=True` (modes "sum", "noop", "concat", one id tensor) gives the node the write-once backward
+    (:func:`embed_mix_backward_once`): the token-table gradient arrives in the parameter's dtype, written once from fp32 sums in
+    ascending position order -- no zeroed fp32 buffer, no atomics on it, no rounding pass, the same bits on every run -- and the
+    GradBucket in-place `+=` path is never taken.  What that call does not build raises NotImplementedError here."""
+    if write_once:
+        refusal = _write_once_refusal(kw)
+        if refusal:
+            raise NotImplementedError(refusal)
     params = (tok_table, byte_table, scale_tok, scale_byte, kw.get("weight"), kw.get("bias"))
     if torch.is_grad_enabled() and any(p is not None and p.requires_grad for p in params):
         if kw["mode"] not in _BWD_MODES:
@@ -639,7 +763,10 @@ def embed_mix(tokens: torch.Tensor, tok_table: torch.Tensor, byte_table: torch.T
                 "inference.py:267, has none; mot_embed_mix_bwd, include/mot.h); call it under torch.no_grad() or with frozen parameters")
         if kw.get("out") is not None or kw.get("counters") is not None:
             raise ValueError("out= / counters= cannot be combined with autograd")
-        r = _EmbedMixFn.apply(tok_table, byte_table, scale_tok, scale_byte, kw.get("weight"), kw.get("bias"), tokens, kw)
+        if write_once:
+            r = _EmbedMixOnceFn.apply(tok_table, byte_table, scale_tok, scale_byte, tokens, kw)
+        else:
+            r = _EmbedMixFn.apply(tok_table, byte_table, scale_tok, scale_byte, kw.get("weight"), kw.get("bias"), tokens, kw)
         if kw.get("return_ids"):
             return MixResult(*r)
         return r

@@ -648,12 +648,14 @@ class SumFrontEnd(nn.Module):
     (runs/71081_*.py:302-315).  byte_dim * bytes_per_token must equal model_dim."""
 
     def __init__(self, token_vocab_size: int, byte_vocab_size: int, model_dim: int, byte_dim: int, bytes_per_token: int = 16,
-                 variant: Literal["71", "71041", "71081"] = "71", ttb=None, pad_byte: int = 456, eot_byte: int = 457):
+                 variant: Literal["71", "71041", "71081"] = "71", ttb=None, pad_byte: int = 456, eot_byte: int = 457,
+                 write_once_grads: bool = False):
         super().__init__()
         assert byte_dim * bytes_per_token == model_dim
         self.embed_tokens = nn.Embedding(token_vocab_size, model_dim)
         self.embed_bytes = nn.Embedding(byte_vocab_size, byte_dim)
         self.variant, self.bpt, self.pad_byte, self.eot_byte = variant, bytes_per_token, pad_byte, eot_byte
+        self.write_once_grads = bool(write_once_grads)   # the write-once, bit-reproducible backward (functional.embed_mix, write_once)
         self.scalars = nn.Parameter(torch.ones(2)) if variant != "71" else None  # [-2] bytes, [-1] tokens
         self.register_buffer("ttb", _table_of(ttb).clone() if ttb is not None else None, persistent=False)
 
@@ -669,7 +671,8 @@ class SumFrontEnd(nn.Module):
         else:
             kw.update(ids_a=byte_inputs.to(torch.int64).reshape(1 if token_inputs.ndim == 1 else token_inputs.shape[0], -1))
         return F_mot.embed_mix(token_inputs, _f32(self.embed_tokens.weight, "token table"),
-                               _f32(self.embed_bytes.weight, "byte table"), mode="sum", bpt=self.bpt, **kw)
+                               _f32(self.embed_bytes.weight, "byte table"), mode="sum", bpt=self.bpt,
+                               write_once=self.write_once_grads, **kw)
 
 
 class SplitX0FrontEnd(nn.Module):
@@ -716,12 +719,13 @@ class ConcatFrontEnd(nn.Module):
     SumFrontEnd (SURVEY section 7, quirk iii).  The attribute names, and so the state-dict keys, are run 711's."""
 
     def __init__(self, token_vocab_size: int, byte_vocab_size: int, token_dim: int, byte_dim: int, bytes_per_token: int = 16,
-                 ttb=None, pad_byte: int = 456, eot_byte: int = 457):
+                 ttb=None, pad_byte: int = 456, eot_byte: int = 457, write_once_grads: bool = False):
         super().__init__()
         self.embed_tokens = nn.Embedding(token_vocab_size, token_dim)
         self.embed_bytes = nn.Embedding(byte_vocab_size, byte_dim)
         self.bpt, self.pad_byte, self.eot_byte = bytes_per_token, pad_byte, eot_byte
         self.model_dim = token_dim + bytes_per_token * byte_dim
+        self.write_once_grads = bool(write_once_grads)   # the write-once, bit-reproducible backward (functional.embed_mix, write_once)
         self.register_buffer("ttb", _table_of(ttb).clone() if ttb is not None else None, persistent=False)
 
     def forward(self, token_inputs: Tensor, byte_inputs: Tensor | None = None) -> Tensor:
@@ -735,7 +739,8 @@ class ConcatFrontEnd(nn.Module):
         else:
             kw.update(ids_a=byte_inputs.to(torch.int64).reshape(1 if token_inputs.ndim == 1 else token_inputs.shape[0], -1))
         return F_mot.embed_mix(token_inputs, _f32(self.embed_tokens.weight, "token table"),
-                               _f32(self.embed_bytes.weight, "byte table"), mode="concat", bpt=self.bpt, **kw)
+                               _f32(self.embed_bytes.weight, "byte table"), mode="concat", bpt=self.bpt,
+                               write_once=self.write_once_grads, **kw)
 
 
 class ByteFcFrontEnd(nn.Module):
