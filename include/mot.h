@@ -49,7 +49,7 @@ typedef enum MotStatus {
  * never fault -- the host shim turns a non-zero word into the reference's IndexError. */
 #define MOT_STATUS_TOKEN_OOR 1u /* token id outside [0, tok_rows) / [0, ttb_rows) */
 #define MOT_STATUS_BYTE_OOR 2u  /* byte id outside [0, byte_rows)                 */
-#define MOT_STATUS_TARGET_OOR 4u /* byte target outside [0, vocab) (mot_byte_head_*) */
+#define MOT_STATUS_TARGET_OOR 4u /* target outside [0, vocab) (mot_byte_head_*, mot_token_head_fwd) */
 
 typedef enum MotPullDir {
     MOT_PULL_NONE = 0,
@@ -528,6 +528,62 @@ int mot_byte_head_fwd(const MotByteHeadDesc *desc /* host */, mot_stream_t strea
  * OVERWRITTEN.  dx is written once per row (the same bits every run); dW sums products over the rows with fp32 atomics.
  */
 int mot_byte_head_bwd(const MotByteHeadDesc *desc /* host */, const float *grad_loss, void *dx, float *dW, mot_stream_t stream);
+
+/*
+ * Token-level output head, forward and backward in one call: replaces the last five lines of every training script
+ *   scaled-pre-train/train_gpt.py:619-623 with byte_mixout_method "noop"   (norm; lm_head; 30 sigmoid(l.float() / 7.5); cross_entropy)
+ *   modded-nanogpt/runs/71_*.py:331-334, and the other 49 runs alike       (norm; F.linear; 15 l rsqrt(l^2 + 225); cross_entropy)
+ * Per row r of x [n_rows, model_dim], weight [vocab, model_dim], targets [n_rows]:
+ *   c_r = (mean(x_r^2) + eps)^-1/2 with norm_in, else 1;   l = c_r (x_r W^T);   z = cap(l)  (MotSoftcap);
+ *   loss = (1 / n_rows) sum_r (lse(z_r) - z_r[y_r]), one fp32 scalar from a fixed-order sum: the same inputs give the same bits.
+ * There is no ignore_index (the reference passes none): a target outside [0, vocab), -100 included, addresses nothing.  Its term
+ * leaves the sum, its rows of the gradients are exactly zero, the mean still divides by n_rows, and MOT_STATUS_TARGET_OOR is ORed
+ * into `status`.  Rows 50 257 .. 50 303 of a 50 304-row weight are ordinary classes.
+ * With dx and dW NULL the call is the loss alone (eval, no_grad): one product per chunk, nothing written per logit.  With either set,
+ * the same pass over a chunk also forms the gradients FOR grad_loss = 1 (the caller scales them by the incoming gradient):
+ *   dx [n_rows, model_dim] in dtype, written once per row (the same bits every run);
+ *   dW [vocab, model_dim] fp32, zeroed by the call, then summed over the rows with fp32 atomics.
+ * So a chunk's logits are formed once, and a training step costs three products of 2 n_rows vocab model_dim FLOP.  No buffer of
+ * n_rows x vocab exists: the rows run in chunks of `chunk_rows`, and the workspace holds the logits of one chunk (fp32; bf16 in
+ * MOT_BF16, where the reference's lm_head returns bf16 too), and, when dx is set, the chunk's u = G W (fp32) and in MOT_BF16 a
+ * transposed copy of the weight.  chunk_rows = 0 is the library's choice: the largest multiple of 256 rows whose logits and u stay
+ * below 512 MiB (2560 rows of fp32 logits, 5120 of bf16, at 50 304 x 768), at least 256; a chunk never exceeds n_rows.
+ * dtype follows x: MOT_F32, or MOT_BF16 with `weight` already cast to bf16 (products on the bf16 MFMA with fp32 accumulation, the
+ * row pass in fp32).  Checked before any HIP call, with a message: vocab not a multiple of 128 or above 262 144, model_dim not a
+ * multiple of 16 or above 2048, an unknown dtype or softcap -> MOT_EUNSUPPORTED; chunk_rows neither 0 nor a multiple of 32 ->
+ * MOT_ESHAPE; chunk_rows x vocab above 2^31 -> MOT_EUNSUPPORTED.  The workspace query returns 0 for a descriptor the call refuses;
+ * it reads dx (set or NULL) and no other pointer.
+ */
+typedef enum MotSoftcap {
+    MOT_SOFTCAP_SIGMOID30 = 0, /* z = 30 sigmoid(l / 7.5), 0 < z < 30    (train_gpt.py:622)      */
+    MOT_SOFTCAP_RSQRT15 = 1    /* z = 15 l (l^2 + 225)^-1/2, |z| < 15    (runs/71_*.py:334)      */
+} MotSoftcap;
+
+typedef struct MotTokenHeadDesc {
+    uint32_t struct_size; /* sizeof(MotTokenHeadDesc) */
+    int32_t dtype;        /* MotDType of x, weight and dx */
+    int32_t softcap;      /* MotSoftcap */
+    int32_t norm_in;      /* 1: x is rms-normed first (line 619 / 331), 0: x is taken as it is */
+    int64_t n_rows;       /* B * T */
+    int32_t model_dim;    /* columns of x and of weight */
+    int32_t vocab;        /* rows of weight: 50 304 = next_multiple_of_n(50257, n=128) */
+    float eps;            /* of the norm; <= 0 -> FLT_EPSILON, as F.rms_norm(eps=None) takes it, on bf16 inputs too */
+    int32_t chunk_rows;   /* rows per chunk: 0 = the library's choice, else a multiple of 32 */
+    const void *x;        /* [n_rows, model_dim], 16-byte aligned */
+    const void *weight;   /* [vocab, model_dim] in dtype, 16-byte aligned */
+    const int64_t *targets; /* [n_rows] */
+    float *loss;          /* fp32 scalar */
+    float *row_stats;     /* optional [2 * n_rows] fp32: lse(z_r) of every row, then its norm factor c_r */
+    uint32_t *status;     /* optional, as in MotEmbedMixDesc */
+    void *workspace;      /* >= mot_token_head_workspace_bytes(desc), 16-byte aligned */
+    size_t workspace_bytes;
+    void *dx;             /* optional [n_rows, model_dim] in dtype, 16-byte aligned, OVERWRITTEN */
+    float *dW;            /* optional [vocab, model_dim] fp32, 16-byte aligned, OVERWRITTEN */
+} MotTokenHeadDesc;
+
+size_t mot_token_head_desc_size(void);
+size_t mot_token_head_workspace_bytes(const MotTokenHeadDesc *desc /* host */);
+int mot_token_head_fwd(const MotTokenHeadDesc *desc /* host */, mot_stream_t stream);
 
 /*
  * Byte self-attention in front of the concat mixin, forward: replaces ByteSelfAttn.forward with use_byte_self_attn on

@@ -34,6 +34,7 @@ MAX_BPT = 64
 ABI_VERSION = 13
 HEAD_COPY, HEAD_SPLIT = 0, 1
 HEAD_VOCAB = 512
+SOFTCAP_SIGMOID30, SOFTCAP_RSQRT15 = 0, 1
 FLAG_LINEAR_ONE_LAUNCH, FLAG_MEAN_GENERIC, FLAG_BWD_DU_FP32, FLAG_LINEAR_COMPOSED = 1, 2, 4, 8
 BYTE_FC_COMPOSED = 1
 BYTE_CAT_MAX_OUT = 4
@@ -56,6 +57,7 @@ EXPORTS = (
     "mot_cross_attn_bwd_workspace_bytes", "mot_cross_attn_bwd",
     "mot_char_swa_desc_size", "mot_char_swa_workspace_bytes", "mot_char_swa_fwd",
     "mot_byte_head_desc_size", "mot_byte_head_workspace_bytes", "mot_byte_head_fwd", "mot_byte_head_bwd",
+    "mot_token_head_desc_size", "mot_token_head_workspace_bytes", "mot_token_head_fwd",
     "mot_byte_self_attn_desc_size", "mot_byte_self_attn_saved_bytes", "mot_byte_self_attn_workspace_bytes",
     "mot_byte_self_attn_fwd", "mot_byte_self_attn_bwd",
     "mot_byte_fc_mix_desc_size", "mot_byte_fc_mix_workspace_bytes", "mot_byte_fc_mix_bwd_workspace_bytes",
@@ -154,6 +156,16 @@ class MotByteHeadDesc(C.Structure):
         ("model_dim", C.c_int32), ("n_layer_out", C.c_int32), ("vocab", C.c_int32), ("eps", C.c_float),
         ("x", C.c_void_p), ("weight", C.c_void_p), ("targets", C.c_void_p), ("loss", C.c_void_p), ("row_stats", C.c_void_p),
         ("status", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
+class MotTokenHeadDesc(C.Structure):
+    """Mirror of struct MotTokenHeadDesc (include/mot.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("dtype", C.c_int32), ("softcap", C.c_int32), ("norm_in", C.c_int32), ("n_rows", C.c_int64),
+        ("model_dim", C.c_int32), ("vocab", C.c_int32), ("eps", C.c_float), ("chunk_rows", C.c_int32),
+        ("x", C.c_void_p), ("weight", C.c_void_p), ("targets", C.c_void_p), ("loss", C.c_void_p), ("row_stats", C.c_void_p),
+        ("status", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("dx", C.c_void_p), ("dW", C.c_void_p),
     ]
 
 
@@ -343,6 +355,11 @@ def _load() -> C.CDLL:
     lib.mot_byte_head_fwd.restype = C.c_int
     lib.mot_byte_head_bwd.argtypes = [C.POINTER(MotByteHeadDesc), vp, vp, vp, vp]
     lib.mot_byte_head_bwd.restype = C.c_int
+    lib.mot_token_head_desc_size.restype = C.c_size_t
+    lib.mot_token_head_workspace_bytes.restype = C.c_size_t
+    lib.mot_token_head_workspace_bytes.argtypes = [C.POINTER(MotTokenHeadDesc)]
+    lib.mot_token_head_fwd.argtypes = [C.POINTER(MotTokenHeadDesc), vp]
+    lib.mot_token_head_fwd.restype = C.c_int
     lib.mot_byte_self_attn_desc_size.restype = C.c_size_t
     for name in ("mot_byte_self_attn_saved_bytes", "mot_byte_self_attn_workspace_bytes"):
         getattr(lib, name).restype = C.c_size_t
@@ -406,6 +423,8 @@ def _load() -> C.CDLL:
         raise ImportError("MotCrossAttnDesc layout mismatch between include/mot.h and _capi.py")
     if lib.mot_byte_head_desc_size() != C.sizeof(MotByteHeadDesc):
         raise ImportError("MotByteHeadDesc layout mismatch between include/mot.h and _capi.py")
+    if lib.mot_token_head_desc_size() != C.sizeof(MotTokenHeadDesc):
+        raise ImportError("MotTokenHeadDesc layout mismatch between include/mot.h and _capi.py")
     if lib.mot_byte_self_attn_desc_size() != C.sizeof(MotByteSelfAttnDesc):
         raise ImportError("MotByteSelfAttnDesc layout mismatch between include/mot.h and _capi.py")
     if lib.mot_byte_fc_mix_desc_size() != C.sizeof(MotByteFcMixDesc):

@@ -369,6 +369,19 @@ int mot_byte_head_bwd(const MotByteHeadDesc *desc, const float *grad_loss, void 
     return launch_byte_head_bwd(*desc, grad_loss, dx, dW, (hipStream_t)stream);
 }
 
+size_t mot_token_head_desc_size(void) { return sizeof(MotTokenHeadDesc); }
+
+size_t mot_token_head_workspace_bytes(const MotTokenHeadDesc *desc) {
+    if (token_head_check(desc)) return 0;
+    return token_head_workspace_bytes(*desc);
+}
+
+int mot_token_head_fwd(const MotTokenHeadDesc *desc, mot_stream_t stream) {
+    int rc = token_head_check(desc);
+    if (rc) return rc;
+    return launch_token_head_fwd(*desc, (hipStream_t)stream);
+}
+
 size_t mot_byte_self_attn_desc_size(void) { return sizeof(MotByteSelfAttnDesc); }
 
 // everything that does not need the pointers: also what the two size queries run

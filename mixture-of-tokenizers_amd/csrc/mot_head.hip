@@ -15,6 +15,7 @@
 // so no tensor of M x 512 exists in split mode.  The loss is a fixed-order double sum of per-row terms (per-workgroup partials over
 // fixed row ranges, then one ordered sum of the partials): the same bits every run.
 #include "mot_internal.hpp"
+#include "mot_rowloss.hpp"
 #include "mot_tile.hpp"
 
 namespace mot {
@@ -24,24 +25,6 @@ constexpr int kV = 512;                           // rows of W: next_multiple_of
 constexpr int kMaxK = 2048;
 constexpr int64_t kChunkBytes = 48ll << 20;       // per-chunk scratch: logits, bf16 G, u
 constexpr float kCap = 30.f, kInvDiv = 1.f / 7.5f;
-
-// norm(h_L) = c x_row and dc/dm0, for n_layer_out identity layers h <- h + norm(h) = h (1 + r), r = (mean(h^2) + eps)^-1/2:
-// each layer scales the row by (1 + r) and its mean square by (1 + r)^2; the derivative is carried forward alongside.
-__device__ __forceinline__ void row_scale(float m0, int L, float eps, float &c, float &dc) {
-    float m = m0, dm = 1.f;
-    c = 1.f;
-    dc = 0.f;
-    for (int i = 0; i < L; ++i) {
-        const float r = rsqrtf(m + eps), dr = -0.5f * r * r * r * dm, a = 1.f + r;
-        dc = dc * a + c * dr;
-        c *= a;
-        dm = dm * a * a + 2.f * m * a * dr;
-        m *= a * a;
-    }
-    const float r = rsqrtf(m + eps);
-    dc = dc * r - 0.5f * c * r * r * r * dm;
-    c *= r;
-}
 
 __device__ __forceinline__ float sigm(float l) { return 1.f / (1.f + __expf(-l * kInvDiv)); }
 
@@ -89,50 +72,6 @@ __global__ __launch_bounds__(kThreads) void head_fwd_rows(const float *__restric
         term[r] = (float)nv * l - tz;
         if (nv < tpr && status) atomicOr(status, (uint32_t)MOT_STATUS_TARGET_OOR);
     }
-}
-
-// The loss: per-row terms summed in a fixed order in double, in two launches.  Workgroup p of a grid that depends on the row count
-// only sums its fixed range of rows into part[p]; one workgroup then sums the parts in order and scales by 1 / M.
-constexpr int kLossParts = 512;
-
-__host__ __device__ inline int loss_parts(int64_t rows) {
-    const int64_t p = (rows + 2047) / 2048;
-    return (int)(p < 1 ? 1 : p > kLossParts ? kLossParts : p);
-}
-
-__device__ __forceinline__ double block_sum(double a, double *sh) {
-    sh[threadIdx.x] = a;
-    __syncthreads();
-    for (int o = kThreads / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    return sh[0];
-}
-
-__global__ __launch_bounds__(kThreads) void head_loss_parts(const float *__restrict__ term, int64_t rows, double *__restrict__ part) {
-    __shared__ double sh[kThreads];
-    const int64_t per = (rows + gridDim.x - 1) / gridDim.x, lo = (int64_t)blockIdx.x * per, hi = lo + per < rows ? lo + per : rows;
-    double a = 0.0;
-    int64_t i = lo + threadIdx.x;
-    for (; i + 3 * kThreads < hi; i += 4 * kThreads) {   // four loads in flight, summed in index order
-        const float t0 = term[i], t1 = term[i + kThreads], t2 = term[i + 2 * kThreads], t3 = term[i + 3 * kThreads];
-        a += (double)t0;
-        a += (double)t1;
-        a += (double)t2;
-        a += (double)t3;
-    }
-    for (; i < hi; i += kThreads) a += (double)term[i];
-    const double s = block_sum(a, sh);
-    if (threadIdx.x == 0) part[blockIdx.x] = s;
-}
-
-__global__ __launch_bounds__(kThreads) void head_loss_final(const double *__restrict__ part, int parts, double inv_m, float *__restrict__ loss) {
-    __shared__ double sh[kThreads];
-    double a = 0.0;
-    for (int i = threadIdx.x; i < parts; i += kThreads) a += part[i];
-    const double s = block_sum(a, sh);
-    if (threadIdx.x == 0) *loss = (float)(s * inv_m);
 }
 
 // G_r = c_r dL/dl_r from the row's logits s_r (read before G is written: G may alias S in fp32).  In bf16, G is rounded once to

@@ -1,0 +1,381 @@
+// mot_tokhead.hip -- the token-level output head, the last five lines of every training script of the reference:
+//   scaled-pre-train/train_gpt.py:619-623 (byte_mixout_method "noop"):  x = norm(x); l = lm_head(x); z = 30 sigmoid(l.float() / 7.5); CE(z, y)
+//   modded-nanogpt/runs/71_*.py:331-334 (all 50 runs):                 x = norm(x); l = x W^T;       z = 15 l rsqrt(l^2 + 225);   CE(z, y)
+// over a vocabulary of 50 304 rows, forward and backward in ONE call and without any N x V tensor.
+//
+// Per row r of x [N, D], W [V, D], y [N]:  c_r = (mean(x_r^2) + eps)^-1/2 (1 without norm_in),  l = c_r (x_r W^T),  z = cap(l).
+// z is bounded (0 < z < 30, |z| < 15), so lse = zmax + log sum exp(z - zmax) with the constant zmax: no max pass.
+//   loss    = (1 / N) sum_r (lse_r - z_r[y_r])                       fixed-order double sum (mot_rowloss.hpp)
+//   dL/dl_r = (1 / N) (softmax(z_r) - onehot(y_r)) dz/dl,   G_r = c_r dL/dl_r,   u = G W,   dW = G^T x,
+//   dx_r    = u_r - c_r^2 (x_r . u_r / D) x_r  (norm_in),  u_r (else)
+// A target outside [0, V) addresses nothing: its term leaves the sum (the mean still divides by N), its row of G is zero, so its row
+// of dx is exactly zero and it adds nothing to dW; MOT_STATUS_TARGET_OOR is raised.
+//
+// The rows run in chunks.  A chunk's logits s = x W^T are one product on the shared launchers into the chunk scratch S (fp32, or bf16
+// in bf16 mode: the reference's own rounding point, CastedLinear returns bf16).  tokhead_rows, the V-wide row pass and the new kernel
+// of this file, takes one row per workgroup: it loads the row's logits ONCE with 16-byte accesses into registers, forms c, sum exp,
+// z[y] and the row's loss term, and, when gradients are asked for, writes G in place over the logits from the same registers.  Then
+// u = G W and dW += G^T x are two more products on the shared launchers, and a wave-per-row kernel closes dx.  So a chunk's logits
+// are formed once and a training step costs three products.  The gradients are those of grad_loss = 1; the caller scales them.
+#include "mot_internal.hpp"
+#include "mot_rowloss.hpp"
+#include "mot_tile.hpp"
+
+namespace mot {
+namespace {
+
+constexpr int kMinV = 128, kMaxV = 262144, kMaxD = 2048;
+constexpr int64_t kChunkBytes = 512ll << 20;   // the library's chunk: logits and u of a chunk stay below this
+constexpr int kRowThreads = 1024;              // workgroup of the row pass at wide rows; kRowThreadsSmall when a row has <= 1024 vectors
+constexpr int kRowThreadsSmall = 256;
+constexpr int kRowWavesMax = kRowThreads / 64;
+constexpr int kRegV = 65536;                  // widest row the row pass keeps in registers between its two uses
+
+// z = cap(l) and dz/dl
+template <int CAP>
+__device__ __forceinline__ float softcap(float l, float &dz) {
+    if (CAP == MOT_SOFTCAP_SIGMOID30) {
+        const float s = 1.f / (1.f + __expf(-l * (1.f / 7.5f)));
+        dz = 4.f * s * (1.f - s);
+        return 30.f * s;
+    } else {
+        const float r = rsqrtf(l * l + 225.f);
+        dz = 3375.f * r * r * r;
+        return 15.f * l * r;
+    }
+}
+template <int CAP>
+__device__ __forceinline__ float softcap_max() { return CAP == MOT_SOFTCAP_SIGMOID30 ? 30.f : 15.f; }
+
+// 16 bytes of a row of logits: 4 fp32 or 8 bf16
+template <typename T>
+struct LogitVec;
+template <>
+struct LogitVec<float> {
+    static constexpr int N = 4;
+    float4 q;
+    __device__ __forceinline__ float get(int e) const { return e == 0 ? q.x : e == 1 ? q.y : e == 2 ? q.z : q.w; }
+    __device__ __forceinline__ void put(const float *v) { q = make_float4(v[0], v[1], v[2], v[3]); }
+};
+template <>
+struct LogitVec<__bf16> {
+    static constexpr int N = 8;
+    uint4 q;
+    __device__ __forceinline__ float get(int e) const {
+        const uint32_t w = e < 2 ? q.x : e < 4 ? q.y : e < 6 ? q.z : q.w;
+        return __uint_as_float((e & 1) ? (w & 0xffff0000u) : (w << 16));
+    }
+    static __device__ __forceinline__ uint32_t pack(float lo, float hi) {   // two roundings to nearest even
+        const __bf16 a = (__bf16)lo, b = (__bf16)hi;
+        return (uint32_t)__builtin_bit_cast(unsigned short, a) | ((uint32_t)__builtin_bit_cast(unsigned short, b) << 16);
+    }
+    __device__ __forceinline__ void put(const float *v) { q = make_uint4(pack(v[0], v[1]), pack(v[2], v[3]), pack(v[4], v[5]), pack(v[6], v[7])); }
+};
+
+// sum over the workgroup in a fixed order: the waves' DPP sums, then the waves in index order.  `sh` holds one float per wave and is
+// used by one sum only, so a single barrier suffices.
+__device__ __forceinline__ float rows_block_sum(float v, float *sh) {
+    const int nw = blockDim.x >> 6;
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float s = 0.f;
+    for (int w = 0; w < nw; ++w) s += sh[w];
+    return s;
+}
+
+// sum exp(z - zmax) over one vector, and z[y] when the vector holds class y (ey: its element there, else -1)
+template <typename T, int CAP>
+__device__ __forceinline__ float vec_stats(const LogitVec<T> &a, float c, int ey, float &zy) {
+    float se = 0.f;
+#pragma unroll
+    for (int e = 0; e < LogitVec<T>::N; ++e) {
+        float dz;
+        const float z = softcap<CAP>(c * a.get(e), dz);
+        se += __expf(z - softcap_max<CAP>());
+        if (e == ey) zy = z;
+    }
+    return se;
+}
+
+// G = c (1 / N) dz/dl (exp(z - lse) - onehot) over one vector; `scale` = c / N, or 0 for a dropped row
+template <typename T, int CAP>
+__device__ __forceinline__ void vec_grad(LogitVec<T> &a, float c, float lse, float scale, int ey) {
+    float g[LogitVec<T>::N];
+#pragma unroll
+    for (int e = 0; e < LogitVec<T>::N; ++e) {
+        float dz;
+        const float z = softcap<CAP>(c * a.get(e), dz);
+        const float p = __expf(z - lse);
+        g[e] = scale * dz * (p - (e == ey ? 1.f : 0.f));
+    }
+    a.put(g);
+}
+
+// One workgroup per row of the chunk.  NV > 0: the row's vectors (nvec = V / N <= NV * blockDim.x) stay in registers between the
+// two uses, vector i of thread t is number t + i * blockDim.x, so a wave's 64 lanes touch 1 KiB at a time and the ragged last
+// round is a predicate.  NV == 0: rows too wide for the register file (V above kRegV) are read a second time.
+template <typename T, int CAP, int NV, bool GRAD>
+__global__ __launch_bounds__(kRowThreads) void tokhead_rows(T *S, int V, const T *__restrict__ x, int K, int norm_in, float eps,
+                                                            const int64_t *__restrict__ tgt, int64_t rows, float inv_n, float *__restrict__ term,
+                                                            float *__restrict__ row_stats, int64_t stats_stride, uint32_t *status) {
+    typedef LogitVec<T> Vec;
+    __shared__ float sh_ss[kRowWavesMax], sh_se[kRowWavesMax], sh_zy[kRowWavesMax];
+    const int64_t r = blockIdx.x;
+    if (r >= rows) return;
+    const int tid = threadIdx.x, nt = blockDim.x, nvec = V / Vec::N;
+    Vec *row = (Vec *)(S + r * (int64_t)V);
+    Vec a[NV > 0 ? NV : 1];
+    if (NV > 0) {   // every load of the row is in flight before anything waits
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int idx = tid + i * nt;
+            if (idx < nvec) a[i] = row[idx];
+        }
+    }
+    float c = 1.f;
+    if (norm_in) {
+        float ss = 0.f;
+        for (int k = tid; k < K; k += nt) {
+            const float v = (float)x[r * K + k];
+            ss += v * v;
+        }
+        float dc;
+        row_scale(rows_block_sum(ss, sh_ss) / (float)K, 0, eps, c, dc);
+    }
+    const int64_t y = tgt[r];
+    const bool in_range = y >= 0 && y < V;
+    const int yvec = in_range ? (int)(y / Vec::N) : -1, yel = in_range ? (int)(y % Vec::N) : -1;
+    float se = 0.f, zy = 0.f;
+    if (NV > 0) {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int idx = tid + i * nt;
+            if (idx < nvec) se += vec_stats<T, CAP>(a[i], c, idx == yvec ? yel : -1, zy);
+        }
+    } else {
+        for (int idx = tid; idx < nvec; idx += nt) {
+            const Vec v = row[idx];
+            se += vec_stats<T, CAP>(v, c, idx == yvec ? yel : -1, zy);
+        }
+    }
+    se = rows_block_sum(se, sh_se);
+    zy = rows_block_sum(zy, sh_zy);   // one thread holds z[y], the others 0
+    const float lse = softcap_max<CAP>() + __logf(se);
+    if (tid == 0) {
+        term[r] = in_range ? lse - zy : 0.f;
+        if (row_stats) {
+            row_stats[r] = lse;
+            row_stats[stats_stride + r] = c;
+        }
+        if (!in_range && status) atomicOr(status, (uint32_t)MOT_STATUS_TARGET_OOR);
+    }
+    if (!GRAD) return;
+    const float scale = in_range ? c * inv_n : 0.f;
+    if (NV > 0) {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int idx = tid + i * nt;
+            if (idx < nvec) {
+                vec_grad<T, CAP>(a[i], c, lse, scale, idx == yvec ? yel : -1);
+                row[idx] = a[i];
+            }
+        }
+    } else {
+        for (int idx = tid; idx < nvec; idx += nt) {
+            Vec v = row[idx];
+            vec_grad<T, CAP>(v, c, lse, scale, idx == yvec ? yel : -1);
+            row[idx] = v;
+        }
+    }
+}
+
+// dx_r = u_r - c_r^2 (x_r . u_r / K) x_r with norm_in (row_scale's dc at L = 0, as the byte head's chain), else u_r; one wave per row
+template <typename T>
+__global__ __launch_bounds__(kThreads) void tokhead_chain_rows(const T *__restrict__ x, const float *__restrict__ u, int K, int64_t rows, int norm_in,
+                                                               float eps, T *__restrict__ dx) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const T *xr = x + r * K;
+    const float *ur = u + r * K;
+    float coef = 0.f;
+    if (norm_in) {
+        float ss = 0.f, xu = 0.f;
+        for (int k = lane; k < K; k += 64) {
+            const float a = (float)xr[k];
+            ss += a * a;
+            xu += a * ur[k];
+        }
+        ss = wave_sum(ss);
+        xu = wave_sum(xu);
+        float c, dc;
+        row_scale(ss / (float)K, 0, eps, c, dc);
+        coef = dc * (2.f / (float)K) * xu / c;
+    }
+    for (int k = lane; k < K; k += 64) dx[r * K + k] = (T)(norm_in ? ur[k] + coef * (float)xr[k] : ur[k]);
+}
+
+struct TokGeom {
+    int64_t rows, chunk;
+    int K, V, norm_in;
+    bool bf16, grad_x;
+    float eps;
+};
+
+struct TokWs {   // carve of the workspace, offsets in bytes
+    size_t term, part, S, u, WT, total;
+};
+
+TokWs tok_ws(const TokGeom &g) {
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t e = g.bf16 ? 2 : 4;
+    TokWs w{};
+    size_t o = 0;
+    w.term = o, o += up((size_t)g.rows * 4);
+    w.part = o, o += up((size_t)kLossParts * 8);
+    w.S = o, o += up((size_t)g.chunk * g.V * e);
+    w.u = o, o += g.grad_x ? up((size_t)g.chunk * g.K * 4) : 0;
+    w.WT = o, o += g.grad_x && g.bf16 ? up((size_t)g.V * g.K * 2) : 0;
+    w.total = o;
+    return w;
+}
+
+// the row pass of one chunk: the workgroup size and the registers per thread follow the row's number of 16-byte vectors
+template <typename T, int CAP, bool GRAD>
+int launch_rows(T *S, const TokGeom &g, const T *x, const int64_t *tgt, int64_t n, float inv_n, float *term, float *row_stats, uint32_t *status,
+                hipStream_t stream) {
+    const int nvec = g.V / LogitVec<T>::N;
+    const int nt = nvec <= 4 * kRowThreadsSmall ? kRowThreadsSmall : kRowThreads;
+    const int nv = (nvec + nt - 1) / nt;
+#define MOT_TOKHEAD_ROWS(NV)                                                                                                                          \
+    hipLaunchKernelGGL((tokhead_rows<T, CAP, NV, GRAD>), dim3((unsigned)n), dim3(nt), 0, stream, S, g.V, x, g.K, g.norm_in, g.eps, tgt, n, inv_n, \
+                       term, row_stats, g.rows, status)
+    // registers hold a row of up to kRegV classes (16 vectors a thread in fp32, 8 in bf16); a wider row is read twice
+    if (nv <= 4) MOT_TOKHEAD_ROWS(4);
+    else if (nv <= 8) MOT_TOKHEAD_ROWS(8);
+    else if (g.V <= kRegV) MOT_TOKHEAD_ROWS(kRegV / (kRowThreads * LogitVec<T>::N));   // 16 in fp32 (bf16 rows this wide took 8 above)
+    else MOT_TOKHEAD_ROWS(0);
+#undef MOT_TOKHEAD_ROWS
+    return check_launch("tokhead_rows");
+}
+
+}  // namespace
+
+static int token_head_geom(const MotTokenHeadDesc *d, TokGeom *out) {
+    if (!d) return set_error(MOT_EINVAL, "token_head: null descriptor");
+    if (d->struct_size != sizeof(MotTokenHeadDesc))
+        return set_error(MOT_EINVAL, "token_head: struct_size %u != %zu (ABI mismatch)", d->struct_size, sizeof(MotTokenHeadDesc));
+    if (d->dtype != MOT_F32 && d->dtype != MOT_BF16) return set_error(MOT_EUNSUPPORTED, "token_head: dtype %d is not built", d->dtype);
+    if (d->softcap != MOT_SOFTCAP_SIGMOID30 && d->softcap != MOT_SOFTCAP_RSQRT15)
+        return set_error(MOT_EUNSUPPORTED, "token_head: softcap %d is not built (sigmoid30 and rsqrt15 are)", d->softcap);
+    if (d->n_rows < 0 || d->n_rows > 0x7fffffffLL || d->model_dim <= 0 || d->vocab <= 0)
+        return set_error(MOT_ESHAPE, "token_head: n_rows %lld, model_dim %d, vocab %d", (long long)d->n_rows, d->model_dim, d->vocab);
+    if (d->vocab % kMinV || d->vocab > kMaxV)
+        return set_error(MOT_EUNSUPPORTED, "token_head: vocab %d must be a multiple of %d and at most %d", d->vocab, kMinV, kMaxV);
+    if (d->model_dim % 16 || d->model_dim > kMaxD)
+        return set_error(MOT_EUNSUPPORTED, "token_head: model_dim %d must be a multiple of 16 and at most %d", d->model_dim, kMaxD);
+    if (d->chunk_rows < 0 || d->chunk_rows % 32)
+        return set_error(MOT_ESHAPE, "token_head: chunk_rows %d must be 0 (the library's choice) or a multiple of 32", d->chunk_rows);
+    if ((int64_t)d->chunk_rows * d->vocab > 0x7fffffffLL)
+        return set_error(MOT_EUNSUPPORTED, "token_head: chunk_rows %d x vocab %d exceeds 2^31 logits a chunk", d->chunk_rows, d->vocab);
+    TokGeom &g = *out;
+    g.rows = d->n_rows;
+    g.K = d->model_dim;
+    g.V = d->vocab;
+    g.norm_in = d->norm_in ? 1 : 0;
+    g.bf16 = d->dtype == MOT_BF16;
+    g.grad_x = d->dx != nullptr;
+    g.eps = d->eps > 0.f ? d->eps : 1.1920928955078125e-07f;   // F.rms_norm(eps=None): the fp32 opmath epsilon, bf16 inputs included
+    int64_t ch = d->chunk_rows;
+    if (ch == 0) {   // the largest multiple of 256 rows whose logits and u stay below kChunkBytes, at least 256
+        const int64_t per_row = (int64_t)g.V * (g.bf16 ? 2 : 4) + (int64_t)g.K * 4;
+        ch = kChunkBytes / per_row / 256 * 256;
+        if (ch < 256) ch = 256;
+    }
+    g.chunk = g.rows < ch ? g.rows : ch;
+    return MOT_OK;
+}
+
+int token_head_check(const MotTokenHeadDesc *d) {
+    TokGeom g;
+    return token_head_geom(d, &g);
+}
+
+size_t token_head_workspace_bytes(const MotTokenHeadDesc &d) {
+    TokGeom g;
+    if (token_head_geom(&d, &g) || g.rows == 0) return 0;
+    return tok_ws(g).total;
+}
+
+template <typename T, int CAP>
+static int token_head_run(const MotTokenHeadDesc &d, const TokGeom &g, const TokWs &w, hipStream_t stream) {
+    constexpr bool BF = sizeof(T) == 2;
+    unsigned char *ws = (unsigned char *)d.workspace;
+    float *term = (float *)(ws + w.term), *u = (float *)(ws + w.u);
+    T *S = (T *)(ws + w.S);
+    void *WT = ws + w.WT;
+    const T *X = (const T *)d.x, *W = (const T *)d.weight;
+    const bool grad = d.dx || d.dW;
+    const float inv_n = (float)(1.0 / (double)g.rows);
+    int rc;
+    if (d.dW && (rc = launch_zero_words(d.dW, (int64_t)g.V * g.K, stream))) return rc;
+    if (BF && d.dx && (rc = launch_transpose_bf16(W, g.V, g.K, WT, stream))) return rc;   // WT[k][v]: the operand of u = G W on the bf16 launcher
+    for (int64_t r0 = 0; r0 < g.rows; r0 += g.chunk) {
+        const int64_t n = g.rows - r0 < g.chunk ? g.rows - r0 : g.chunk;
+        const T *x = X + r0 * g.K;
+        // s = x W^T for the chunk's rows
+        if (BF)
+            rc = launch_gemm_rows_bf16(x, g.K, n, W, g.K, g.K, g.V, S, g.V, true, nullptr, stream);
+        else
+            rc = launch_gemm_rows((const float *)x, g.K, n, (const float *)W, g.K, g.K, g.V, (float *)S, g.V, true, stream);
+        if (rc) return rc;
+        float *stats = d.row_stats ? d.row_stats + r0 : nullptr;
+        if (grad)
+            rc = launch_rows<T, CAP, true>(S, g, x, d.targets + r0, n, inv_n, term + r0, stats, d.status, stream);
+        else
+            rc = launch_rows<T, CAP, false>(S, g, x, d.targets + r0, n, inv_n, term + r0, stats, d.status, stream);
+        if (rc) return rc;
+        if (d.dx) {   // u = G W, then the row chain
+            if (BF)
+                rc = launch_gemm_rows_bf16(S, g.V, n, WT, g.V, g.V, g.K, u, g.K, false, nullptr, stream);
+            else
+                rc = launch_gemm_rows((const float *)S, g.V, n, (const float *)W, g.K, g.V, g.K, u, g.K, false, stream);
+            if (rc) return rc;
+            hipLaunchKernelGGL(tokhead_chain_rows<T>, dim3((unsigned)((n + kWaves - 1) / kWaves)), dim3(kThreads), 0, stream, x, u, g.K, n, g.norm_in, g.eps,
+                               (T *)d.dx + r0 * g.K);
+            if ((rc = check_launch("tokhead_chain_rows"))) return rc;
+        }
+        if (d.dW) {   // dW += G^T x
+            if (BF)
+                rc = launch_gemm_tn_bf16((const __bf16 *)S, g.V, g.V, (const __bf16 *)x, g.K, g.K, n, d.dW, g.K, stream);
+            else
+                rc = launch_gemm_tn((const float *)S, g.V, g.V, (const float *)x, g.K, g.K, n, d.dW, g.K, stream);
+            if (rc) return rc;
+        }
+    }
+    double *part = (double *)(ws + w.part);
+    const int parts = loss_parts(g.rows);
+    hipLaunchKernelGGL(head_loss_parts, dim3(parts), dim3(kThreads), 0, stream, term, g.rows, part);
+    if ((rc = check_launch("head_loss_parts"))) return rc;
+    hipLaunchKernelGGL(head_loss_final, dim3(1), dim3(kThreads), 0, stream, part, parts, 1.0 / (double)g.rows, d.loss);
+    return check_launch("head_loss_final");
+}
+
+int launch_token_head_fwd(const MotTokenHeadDesc &d, hipStream_t stream) {
+    TokGeom g;
+    int rc = token_head_geom(&d, &g);
+    if (rc) return rc;
+    if (!d.x || !d.weight || !d.targets || !d.loss) return set_error(MOT_EINVAL, "token_head: null x / weight / targets / loss");
+    if (g.rows == 0) return set_error(MOT_ESHAPE, "token_head: no rows (the mean over zero targets is undefined)");
+    const TokWs w = tok_ws(g);
+    if (!d.workspace || d.workspace_bytes < w.total)
+        return set_error(MOT_EWORKSPACE, "token_head: workspace %zu bytes < %zu", d.workspace ? d.workspace_bytes : (size_t)0, w.total);
+    if (((uintptr_t)d.x & 15) || ((uintptr_t)d.weight & 15) || ((uintptr_t)d.workspace & 15) || ((uintptr_t)d.dx & 15) || ((uintptr_t)d.dW & 15))
+        return set_error(MOT_EUNSUPPORTED, "token_head: x, weight, workspace, dx and dW must be 16-byte aligned");
+    const bool sig = d.softcap == MOT_SOFTCAP_SIGMOID30;
+    if (g.bf16) return sig ? token_head_run<__bf16, MOT_SOFTCAP_SIGMOID30>(d, g, w, stream) : token_head_run<__bf16, MOT_SOFTCAP_RSQRT15>(d, g, w, stream);
+    return sig ? token_head_run<float, MOT_SOFTCAP_SIGMOID30>(d, g, w, stream) : token_head_run<float, MOT_SOFTCAP_RSQRT15>(d, g, w, stream);
+}
+
+}  // namespace mot

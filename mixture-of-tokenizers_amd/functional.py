@@ -1113,6 +1113,90 @@ def byte_head_loss(x: torch.Tensor, weight: torch.Tensor, targets: torch.Tensor,
 
 
 # ----------------------------------------------------------------------------------------------
+# token-level output head: norm + lm_head + softcap + cross-entropy, train_gpt.py:619-623 (noop mixout), runs/71_*.py:331-334
+# ----------------------------------------------------------------------------------------------
+_SOFTCAPS = {"sigmoid30": capi.SOFTCAP_SIGMOID30, "rsqrt15": capi.SOFTCAP_RSQRT15}
+
+
+def _token_head_call(x2, w, t, softcap, norm_in, chunk_rows, dx, dw):
+    """One mot_token_head_fwd: the loss, and the gradients for grad_loss = 1 into dx / dw where given."""
+    dev = capi.require_device(x2, w, t)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    d = capi.MotTokenHeadDesc()
+    d.struct_size = C.sizeof(capi.MotTokenHeadDesc)
+    d.dtype, d.softcap, d.norm_in, d.chunk_rows = capi.dtype_code(x2.dtype), _SOFTCAPS[softcap], int(bool(norm_in)), int(chunk_rows or 0)
+    d.n_rows, d.model_dim, d.vocab, d.eps = x2.shape[0], x2.shape[1], w.shape[0], 0.0
+    d.x, d.weight, d.targets, d.loss = capi.ptr(x2), capi.ptr(w), capi.ptr(t), capi.ptr(loss)
+    d.dx, d.dW = capi.ptr(dx), capi.ptr(dw)
+    _launch(dev, d, capi.lib.mot_token_head_fwd, ws_bytes=capi.lib.mot_token_head_workspace_bytes)
+    return loss
+
+
+def _token_head_operands(x, weight, targets, softcap):
+    if softcap not in _SOFTCAPS:
+        raise ValueError(f"token_head_loss: softcap must be 'sigmoid30' or 'rsqrt15', got {softcap!r}")
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"token_head_loss: x must be float32 or bfloat16, got {x.dtype}")
+    if weight.ndim != 2 or weight.shape[1] != x.shape[-1]:
+        raise ValueError(f"token_head_loss: weight must be (vocab, {x.shape[-1]}), got {tuple(weight.shape)}")
+    if targets.dtype not in (torch.int64, torch.int32):
+        raise TypeError(f"token_head_loss: targets must be int64 or int32, got {targets.dtype}")
+    capi.require_device(x, weight, targets)
+    x2 = _contig(x.detach().reshape(-1, x.shape[-1]), x.dtype, "x")
+    w = _contig(weight.detach().to(x2.dtype), x2.dtype, "weight")   # CastedLinear / lm_head_w.bfloat16(): the weight in x's dtype, cast once
+    t = _contig(targets.reshape(-1).to(torch.int64), torch.int64, "targets")
+    if t.numel() != x2.shape[0]:
+        raise ValueError(f"token_head_loss: {t.numel()} targets for {x2.shape[0]} rows")
+    return x2, w, t
+
+
+class _TokenHeadFn(torch.autograd.Function):
+    """forward = one mot_token_head_fwd that also forms dx and the fp32 dW for grad_loss = 1; backward multiplies them by the incoming
+    grad_loss on the device, out of place (a retained graph runs backward again on the same saved gradients)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, targets, softcap, norm_in, chunk_rows):
+        x2, w, t = _token_head_operands(x, weight, targets, softcap)
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        dx = torch.empty_like(x2) if need_x else None
+        dw = torch.empty(w.shape, dtype=torch.float32, device=x2.device) if need_w else None
+        loss = _token_head_call(x2, w, t, softcap, norm_in, chunk_rows, dx, dw)
+        ctx.save_for_backward(dx, dw)
+        ctx.cfg = (x.shape, weight.dtype)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss):
+        dx, dw = ctx.saved_tensors
+        xshape, wdtype = ctx.cfg
+        go = grad_loss.detach().reshape(1, 1).float()
+        gx = gw = None
+        if dx is not None:   # one elementwise pass: fp32 factor, fp32 product, one rounding on store, no fp32 copy of dx
+            gx = torch.mul(dx, go, out=torch.empty_like(dx)).reshape(xshape)
+        if dw is not None:
+            gw = torch.mul(dw, go, out=torch.empty(dw.shape, dtype=wdtype, device=dw.device))
+        return gx, gw, None, None, None, None
+
+
+@torch.compiler.disable
+def token_head_loss(x: torch.Tensor, weight: torch.Tensor, targets: torch.Tensor, *, softcap: str = "sigmoid30", norm_in: bool = True,
+                    chunk_rows: int | None = None) -> torch.Tensor:
+    """The token-level output head, fused: cross_entropy(cap(F.linear(norm(x), weight).float()), targets) as an fp32 scalar, with
+    cap = 30 sigmoid(l / 7.5) ("sigmoid30", scaled-pre-train/train_gpt.py:619-623 with byte_mixout_method "noop") or
+    15 l rsqrt(l^2 + 225) ("rsqrt15", modded-nanogpt/runs/71_*.py:331-334); norm_in=False takes x as already normed.
+    x (..., model_dim) float32 or bfloat16; weight (vocab, model_dim), cast once to x's dtype as CastedLinear does; targets int64 or
+    int32 (...).  No logits tensor of rows x vocab exists: the rows run in chunks (chunk_rows rows, a multiple of 32; None: the
+    library's choice).  Differentiable in x and weight (the weight's gradient in the weight's dtype, summed in fp32): with grad mode
+    on, the one call forms both gradients beside the loss; under no_grad it is the loss alone, with the same bits.
+    A target outside [0, vocab) raises the status bit that check_status() reports; its term is left out of the sum."""
+    if not torch.is_grad_enabled() or not (x.requires_grad or weight.requires_grad):
+        x2, w, t = _token_head_operands(x, weight, targets, softcap)
+        return _token_head_call(x2, w, t, softcap, norm_in, chunk_rows, None, None)
+    return _TokenHeadFn.apply(x, weight, targets, softcap, bool(norm_in), chunk_rows)
+
+
+# ----------------------------------------------------------------------------------------------
 # byte self-attention in front of the concat mixin: ByteSelfAttn with use_byte_self_attn, train_gpt.py:382-418
 # ----------------------------------------------------------------------------------------------
 def _byte_self_attn_desc(x3, qkv_w, proj_w, lam, cos, sin, bpt, window, block_causal, out, saved):

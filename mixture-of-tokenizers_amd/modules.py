@@ -429,7 +429,8 @@ class _ByteMixoutNoop(nn.Module):  # train_gpt.py:530-535
 class ByteMixout(nn.Module):  # train_gpt.py:530-542
     """The reference's ByteMixout with identity ByteSelfAttn layers (the only kind its runs build at the output).
     forward(x) returns the byte-level states in plain torch ops, so an unmodified GPT.forward still works;
-    loss(x, lm_head, target_seq) is the fused head, one mot_byte_head_fwd / _bwd pair in place of train_gpt.py:618-623."""
+    loss(x, lm_head, target_seq) is the fused head in place of train_gpt.py:618-623: one mot_byte_head_fwd / _bwd pair for copy and
+    split, one mot_token_head_fwd for noop (the token-level head over lm_head's 50 304 rows)."""
 
     def __init__(self, dims: ModelDims, max_seq_len: int, byte_params: ByteHyperparameters):
         super().__init__()
@@ -449,8 +450,8 @@ class ByteMixout(nn.Module):  # train_gpt.py:530-542
 
     def loss(self, x: Tensor, lm_head: nn.Module, target_seq: Tensor) -> Tensor:
         """cross_entropy(30 sigmoid(lm_head(norm(self(x))).float() / 7.5), target_seq), fused; x (..., T, model_dim)."""
-        if self.method == "noop":
-            raise NotImplementedError("the token-level head of byte_mixout_method='noop' (vocabulary 50 304) is not part of the byte head")
+        if self.method == "noop":   # the token-level head: targets are tokens, one per row of x
+            return F_mot.token_head_loss(x, lm_head.weight, target_seq, softcap="sigmoid30", norm_in=True)
         return F_mot.byte_head_loss(x, lm_head.weight, target_seq, method=self.method, bytes_per_token=self.bpt, n_layer_out=self.n_layer_out)
 
 
