@@ -1,7 +1,9 @@
 // mot_convert.hip -- element-type and layout conversions between the fp32 and bf16 sides of a pass: widen (bf16 -> fp32),
 // narrow (fp32 -> bf16), transpose_bf16 and narrow_transpose (k-major copies of a weight for the bf16 products).
 // Callers: the CONCAT_LINEAR backward (mot_bwd_linear.hip: widen, narrow, transpose_bf16), the MEAN backward (mot_bwd_mean.hip:
-// widen), cross-attention (mot_attn.hip: narrow, narrow_transpose) and the character mixer (mot_swa.hip: narrow).
+// widen), cross-attention (mot_attn.hip: narrow, narrow_transpose), the character mixer (mot_swa.hip: narrow), and for transpose_bf16
+// the linear-on-bytes mixin (mot_bytefc.hip), the MoT value embeddings (mot_valuemix.hip) and the two output heads (mot_head.hip,
+// mot_tokhead.hip).
 #include "mot_mix.hpp"
 
 namespace mot {

@@ -1,6 +1,7 @@
 // mot_desc.hpp -- host-side pieces that the descriptor front-ends share (mot_bytefc.hip, mot_bytecat.hip, mot_values.hip,
 // mot_valuemix.hip, mot_splitx0.hip): the workspace arena, the view of a descriptor's byte-id source with its checks, the
 // workspace check, and the byte ids from the token->byte table.  No device code.  A new front-end uses these.
+// The output heads carve their workspaces with the arena too (mot_headcore.hpp).
 #pragma once
 #include "mot_internal.hpp"
 #include "mot_tile.hpp"   // kPull*

@@ -12,11 +12,10 @@
 // launchers; a wave-per-row epilogue applies c, the softcap and the loss.  The backward recomputes the chunk's logits, writes
 // G_r = c_r dL/dl_r (overwriting the logits in fp32, a bf16 copy in bf16), then u = G W (= c dL/dnorm(h)), the row chain
 // dx_r = u_r + (dc/dm0) (2 / K) (x_r . u_r / c_r) x_r, and dW += G^T x.  Every buffer of the chunk is bounded by kChunkBytes,
-// so no tensor of M x 512 exists in split mode.  The loss is a fixed-order double sum of per-row terms (per-workgroup partials over
-// fixed row ranges, then one ordered sum of the partials): the same bits every run.
-#include "mot_internal.hpp"
-#include "mot_rowloss.hpp"
-#include "mot_tile.hpp"
+// so no tensor of M x 512 exists in split mode.  The loss is a fixed-order double sum of per-row terms: the same bits every run.
+// This unit holds the two 512-wide row passes, head_fwd_rows and head_grad_rows, the checks and the carve; row_scale, the products,
+// the chunk rule, the row chain and the loss's sum are the heads' shared ones (mot_headcore.hpp).
+#include "mot_headcore.hpp"
 
 namespace mot {
 namespace {
@@ -104,37 +103,6 @@ __global__ __launch_bounds__(kThreads) void head_grad_rows(const float *S, const
     }
 }
 
-// dx_r = u_r + (dc/dm0) (2 / K) (x_r . u_r / c_r) x_r
-template <typename T>
-__global__ __launch_bounds__(kThreads) void head_chain_rows(const T *__restrict__ x, const float *__restrict__ u, int K, int64_t rows, int L, float eps,
-                                                            T *__restrict__ dx) {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
-    if (r >= rows) return;
-    const T *xr = x + r * K;
-    const float *ur = u + r * K;
-    float ss = 0.f, xu = 0.f;
-    for (int k = lane; k < K; k += 64) {
-        const float a = (float)xr[k];
-        ss += a * a;
-        xu += a * ur[k];
-    }
-    ss = wave_sum(ss);
-    xu = wave_sum(xu);
-    float c, dc;
-    row_scale(ss / (float)K, L, eps, c, dc);
-    const float coef = dc * (2.f / (float)K) * xu / c;
-    for (int k = lane; k < K; k += 64) dx[r * K + k] = (T)(ur[k] + coef * (float)xr[k]);
-}
-
-// WT[k][v] = W[v][k] (bf16), the transposed operand of u = G W on the bf16 launcher
-__global__ __launch_bounds__(kThreads) void head_transpose_bf16(const __bf16 *__restrict__ W, int K, __bf16 *__restrict__ WT) {
-    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (i >= (int64_t)kV * K) return;
-    const int v = (int)(i / K), k = (int)(i % K);
-    WT[(int64_t)k * kV + v] = W[i];
-}
-
 struct HeadGeom {
     int64_t rows;   // R: tokens (copy) or byte rows (split)
     int K;          // row width
@@ -150,16 +118,15 @@ struct HeadWs {   // carve of the workspace, offsets in bytes
 };
 
 HeadWs head_ws(const HeadGeom &g) {
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    Arena a;
     HeadWs w{};
-    size_t o = 0;
-    w.term = o, o += up((size_t)g.rows * 4);
-    w.part = o, o += up((size_t)kLossParts * 8);
-    w.S = o, o += up((size_t)g.chunk * kV * 4);
-    w.G16 = o, o += g.bf16 ? up((size_t)g.chunk * kV * 2) : 0;
-    w.u = o, o += up((size_t)g.chunk * g.K * 4);
-    w.WT = o, o += g.bf16 ? up((size_t)kV * g.K * 2) : 0;
-    w.total = o;
+    w.term = a.take((size_t)g.rows * 4);
+    w.part = a.take((size_t)kLossParts * 8);
+    w.S = a.take((size_t)g.chunk * kV * 4);
+    w.G16 = a.take(g.bf16 ? (size_t)g.chunk * kV * 2 : 0);
+    w.u = a.take((size_t)g.chunk * g.K * 4);
+    w.WT = a.take(g.bf16 ? (size_t)kV * g.K * 2 : 0);
+    w.total = a.o;
     return w;
 }
 
@@ -189,11 +156,8 @@ static int byte_head_geom(const MotByteHeadDesc *d, HeadGeom *geom_out) {
     g.tpr = split ? 1 : d->bpt;
     g.M = M;
     g.bf16 = d->dtype == MOT_BF16;
-    g.eps = d->eps > 0.f ? d->eps : 1.1920928955078125e-07f;   // F.rms_norm(eps=None): the fp32 opmath epsilon, bf16 inputs included
-    const int64_t per_row = (int64_t)kV * 4 + (g.bf16 ? kV * 2 : 0) + (int64_t)K * 4;
-    int64_t ch = kChunkBytes / per_row / 256 * 256;
-    if (ch < 256) ch = 256;
-    g.chunk = g.rows < ch ? g.rows : ch;
+    g.eps = d->eps > 0.f ? d->eps : kHeadEps;
+    g.chunk = head_chunk_rows(kChunkBytes, (int64_t)kV * 4 + (g.bf16 ? kV * 2 : 0) + (int64_t)K * 4, g.rows);
     return MOT_OK;
 }
 
@@ -216,11 +180,21 @@ static int head_check_ptrs(const MotByteHeadDesc &d, const HeadGeom &g, size_t n
     return MOT_OK;
 }
 
-// s = x W^T for rows [r0, r0 + n) of the chunk into S (fp32 [n][512])
-static int head_logits(const MotByteHeadDesc &d, const HeadGeom &g, int64_t r0, int64_t n, float *S, hipStream_t stream) {
-    if (g.bf16)
-        return launch_gemm_rows_bf16((const __bf16 *)d.x + r0 * g.K, g.K, n, d.weight, g.K, g.K, kV, S, kV, false, nullptr, stream);
-    return launch_gemm_rows((const float *)d.x + r0 * g.K, g.K, n, (const float *)d.weight, g.K, g.K, kV, S, kV, true, stream);
+template <typename T>
+static int byte_head_fwd_run(const MotByteHeadDesc &d, const HeadGeom &g, const HeadWs &w, hipStream_t stream) {
+    unsigned char *ws = (unsigned char *)d.workspace;
+    float *term = (float *)(ws + w.term), *S = (float *)(ws + w.S);
+    float *lse = d.row_stats, *cst = d.row_stats + g.rows;
+    int rc;
+    for (int64_t r0 = 0; r0 < g.rows; r0 += g.chunk) {
+        const int64_t n = g.rows - r0 < g.chunk ? g.rows - r0 : g.chunk;
+        const T *x = (const T *)d.x + r0 * g.K;
+        if ((rc = head_logits<T>(x, (const T *)d.weight, n, g.K, kV, S, false, stream))) return rc;
+        hipLaunchKernelGGL(head_fwd_rows<T>, dim3((unsigned)((n + kWaves - 1) / kWaves)), dim3(kThreads), 0, stream, S, x, g.K, d.targets + r0 * g.tpr, g.tpr, n,
+                           d.n_layer_out, g.eps, lse + r0, cst + r0, term + r0, d.status);
+        if ((rc = check_launch("head_fwd_rows"))) return rc;
+    }
+    return launch_head_loss(term, g.rows, (double *)(ws + w.part), 1.0 / (double)g.M, d.loss, stream);
 }
 
 int launch_byte_head_fwd(const MotByteHeadDesc &d, hipStream_t stream) {
@@ -231,28 +205,34 @@ int launch_byte_head_fwd(const MotByteHeadDesc &d, hipStream_t stream) {
     if (g.rows == 0) return set_error(MOT_ESHAPE, "byte_head: no targets (the mean over zero targets is undefined)");
     const HeadWs w = head_ws(g);
     if ((rc = head_check_ptrs(d, g, w.total))) return rc;
+    return g.bf16 ? byte_head_fwd_run<__bf16>(d, g, w, stream) : byte_head_fwd_run<float>(d, g, w, stream);
+}
+
+// In fp32 G overwrites the chunk's logits S; in bf16 it is the bf16 copy G16, and u = G W reads the k-major copy WT of W.
+template <typename T>
+static int byte_head_bwd_run(const MotByteHeadDesc &d, const HeadGeom &g, const HeadWs &w, const float *grad_loss, T *dx, float *dW, hipStream_t stream) {
+    constexpr bool BF = sizeof(T) == 2;
     unsigned char *ws = (unsigned char *)d.workspace;
-    float *term = (float *)(ws + w.term), *S = (float *)(ws + w.S);
-    float *lse = d.row_stats, *cst = d.row_stats + g.rows;
+    float *S = (float *)(ws + w.S), *u = (float *)(ws + w.u);
+    T *G = (T *)(ws + (BF ? w.G16 : w.S)), *WT = (T *)(ws + w.WT);
+    const T *W = (const T *)d.weight;
+    const float *lse = d.row_stats, *cst = d.row_stats + g.rows;
+    const float inv_m = (float)(1.0 / (double)g.M);
+    int rc;
+    if ((rc = launch_zero_words(dW, (int64_t)kV * g.K, stream))) return rc;
+    if (BF && (rc = launch_transpose_bf16(W, kV, g.K, WT, stream))) return rc;
     for (int64_t r0 = 0; r0 < g.rows; r0 += g.chunk) {
         const int64_t n = g.rows - r0 < g.chunk ? g.rows - r0 : g.chunk;
-        if ((rc = head_logits(d, g, r0, n, S, stream))) return rc;
-        const unsigned blocks = (unsigned)((n + kWaves - 1) / kWaves);
-        const int64_t *tg = d.targets + r0 * g.tpr;
-        if (g.bf16)
-            hipLaunchKernelGGL(head_fwd_rows<__bf16>, dim3(blocks), dim3(kThreads), 0, stream, S, (const __bf16 *)d.x + r0 * g.K, g.K, tg, g.tpr, n,
-                               d.n_layer_out, g.eps, lse + r0, cst + r0, term + r0, d.status);
-        else
-            hipLaunchKernelGGL(head_fwd_rows<float>, dim3(blocks), dim3(kThreads), 0, stream, S, (const float *)d.x + r0 * g.K, g.K, tg, g.tpr, n,
-                               d.n_layer_out, g.eps, lse + r0, cst + r0, term + r0, d.status);
-        if ((rc = check_launch("head_fwd_rows"))) return rc;
+        const T *x = (const T *)d.x + r0 * g.K;
+        if ((rc = head_logits<T>(x, W, n, g.K, kV, S, false, stream))) return rc;
+        hipLaunchKernelGGL(head_grad_rows<T>, dim3((unsigned)((n + kWaves - 1) / kWaves)), dim3(kThreads), 0, stream, S, d.targets + r0 * g.tpr, g.tpr, n,
+                           lse + r0, cst + r0, grad_loss, inv_m, G);
+        if ((rc = check_launch("head_grad_rows"))) return rc;
+        if ((rc = head_gw<T>(G, BF ? WT : W, n, kV, g.K, u, stream))) return rc;
+        if ((rc = head_dw<T>(G, x, n, kV, g.K, dW, stream))) return rc;
+        if ((rc = launch_head_chain<T>(x, u, g.K, n, d.n_layer_out, 1, g.eps, dx + r0 * g.K, stream))) return rc;
     }
-    double *part = (double *)(ws + w.part);
-    const int parts = loss_parts(g.rows);
-    hipLaunchKernelGGL(head_loss_parts, dim3(parts), dim3(kThreads), 0, stream, term, g.rows, part);
-    if ((rc = check_launch("head_loss_parts"))) return rc;
-    hipLaunchKernelGGL(head_loss_final, dim3(1), dim3(kThreads), 0, stream, part, parts, 1.0 / (double)g.M, d.loss);
-    return check_launch("head_loss_final");
+    return MOT_OK;
 }
 
 int launch_byte_head_bwd(const MotByteHeadDesc &d, const float *grad_loss, void *dx, float *dW, hipStream_t stream) {
@@ -264,40 +244,7 @@ int launch_byte_head_bwd(const MotByteHeadDesc &d, const float *grad_loss, void 
     const HeadWs w = head_ws(g);
     if ((rc = head_check_ptrs(d, g, w.total))) return rc;
     if ((uintptr_t)dx & 15) return set_error(MOT_EUNSUPPORTED, "byte_head: dx must be 16-byte aligned");
-    unsigned char *ws = (unsigned char *)d.workspace;
-    float *S = (float *)(ws + w.S), *u = (float *)(ws + w.u);
-    __bf16 *G16 = (__bf16 *)(ws + w.G16), *WT = (__bf16 *)(ws + w.WT);
-    const float *lse = d.row_stats, *cst = d.row_stats + g.rows;
-    const float inv_m = (float)(1.0 / (double)g.M);
-    if ((rc = launch_zero_words(dW, (int64_t)kV * g.K, stream))) return rc;
-    if (g.bf16) {
-        hipLaunchKernelGGL(head_transpose_bf16, dim3((unsigned)((kV * g.K + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, (const __bf16 *)d.weight,
-                           g.K, WT);
-        if ((rc = check_launch("head_transpose_bf16"))) return rc;
-    }
-    for (int64_t r0 = 0; r0 < g.rows; r0 += g.chunk) {
-        const int64_t n = g.rows - r0 < g.chunk ? g.rows - r0 : g.chunk;
-        const unsigned blocks = (unsigned)((n + kWaves - 1) / kWaves);
-        const int64_t *tg = d.targets + r0 * g.tpr;
-        if ((rc = head_logits(d, g, r0, n, S, stream))) return rc;
-        if (g.bf16) {
-            const __bf16 *x = (const __bf16 *)d.x + r0 * g.K;
-            hipLaunchKernelGGL(head_grad_rows<__bf16>, dim3(blocks), dim3(kThreads), 0, stream, S, tg, g.tpr, n, lse + r0, cst + r0, grad_loss, inv_m, G16);
-            if ((rc = check_launch("head_grad_rows"))) return rc;
-            if ((rc = launch_gemm_rows_bf16(G16, kV, n, WT, kV, kV, g.K, u, g.K, false, nullptr, stream))) return rc;
-            if ((rc = launch_gemm_tn_bf16(G16, kV, kV, x, g.K, g.K, n, dW, g.K, stream))) return rc;
-            hipLaunchKernelGGL(head_chain_rows<__bf16>, dim3(blocks), dim3(kThreads), 0, stream, x, u, g.K, n, d.n_layer_out, g.eps, (__bf16 *)dx + r0 * g.K);
-        } else {
-            const float *x = (const float *)d.x + r0 * g.K;
-            hipLaunchKernelGGL(head_grad_rows<float>, dim3(blocks), dim3(kThreads), 0, stream, S, tg, g.tpr, n, lse + r0, cst + r0, grad_loss, inv_m, S);
-            if ((rc = check_launch("head_grad_rows"))) return rc;
-            if ((rc = launch_gemm_rows(S, kV, n, (const float *)d.weight, g.K, kV, g.K, u, g.K, false, stream))) return rc;
-            if ((rc = launch_gemm_tn(S, kV, kV, x, g.K, g.K, n, dW, g.K, stream))) return rc;
-            hipLaunchKernelGGL(head_chain_rows<float>, dim3(blocks), dim3(kThreads), 0, stream, x, u, g.K, n, d.n_layer_out, g.eps, (float *)dx + r0 * g.K);
-        }
-        if ((rc = check_launch("head_chain_rows"))) return rc;
-    }
-    return MOT_OK;
+    return g.bf16 ? byte_head_bwd_run<__bf16>(d, g, w, grad_loss, (__bf16 *)dx, dW, stream) : byte_head_bwd_run<float>(d, g, w, grad_loss, (float *)dx, dW, stream);
 }
 
 }  // namespace mot

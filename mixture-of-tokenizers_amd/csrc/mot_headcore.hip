@@ -1,0 +1,93 @@
+// mot_headcore.hip -- the kernels the output heads share (mot_headcore.hpp), each with its launcher: head_chain_rows, the
+// wave-per-row chain that closes dx behind u = G W, and head_loss_parts / head_loss_final, the loss as a sum of per-row terms.
+#include "mot_headcore.hpp"
+
+namespace mot {
+
+// dx_r = u_r + (dc/dm0) (2 / K) (x_r . u_r / c_r) x_r; at L = 0 that is u_r - c_r^2 (x_r . u_r / K) x_r, the plain norm's.  Without
+// norm_in the row is u_r itself (not u_r + 0 x_r: a non-finite x stays out of dx).
+template <typename T>
+__global__ __launch_bounds__(kThreads) void head_chain_rows(const T *__restrict__ x, const float *__restrict__ u, int K, int64_t rows, int L, int norm_in,
+                                                            float eps, T *__restrict__ dx) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const T *xr = x + r * K;
+    const float *ur = u + r * K;
+    if (!norm_in) {
+        for (int k = lane; k < K; k += 64) dx[r * K + k] = (T)ur[k];
+        return;
+    }
+    float ss = 0.f, xu = 0.f;
+    for (int k = lane; k < K; k += 64) {
+        const float a = (float)xr[k];
+        ss += a * a;
+        xu += a * ur[k];
+    }
+    ss = wave_sum(ss);
+    xu = wave_sum(xu);
+    float c, dc;
+    row_scale(ss / (float)K, L, eps, c, dc);
+    const float coef = dc * (2.f / (float)K) * xu / c;
+    for (int k = lane; k < K; k += 64) dx[r * K + k] = (T)(ur[k] + coef * (float)xr[k]);
+}
+
+template <typename T>
+int launch_head_chain(const T *x, const float *u, int K, int64_t n, int L, int norm_in, float eps, T *dx, hipStream_t stream) {
+    hipLaunchKernelGGL(head_chain_rows<T>, dim3((unsigned)((n + kWaves - 1) / kWaves)), dim3(kThreads), 0, stream, x, u, K, n, L, norm_in, eps, dx);
+    return check_launch("head_chain_rows");
+}
+template int launch_head_chain<float>(const float *, const float *, int, int64_t, int, int, float, float *, hipStream_t);
+template int launch_head_chain<__bf16>(const __bf16 *, const float *, int, int64_t, int, int, float, __bf16 *, hipStream_t);
+
+// The loss: per-row terms summed in a fixed order in double, in two launches.  Workgroup p of a grid that depends on the row count
+// only sums its fixed range of rows into part[p]; one workgroup then sums the parts in order and scales by 1 / M.
+static int loss_parts(int64_t rows) {
+    const int64_t p = (rows + 2047) / 2048;
+    return (int)(p < 1 ? 1 : p > kLossParts ? kLossParts : p);
+}
+
+static __device__ __forceinline__ double block_sum(double a, double *sh) {
+    sh[threadIdx.x] = a;
+    __syncthreads();
+    for (int o = kThreads / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+        __syncthreads();
+    }
+    return sh[0];
+}
+
+__global__ __launch_bounds__(kThreads) void head_loss_parts(const float *__restrict__ term, int64_t rows, double *__restrict__ part) {
+    __shared__ double sh[kThreads];
+    const int64_t per = (rows + gridDim.x - 1) / gridDim.x, lo = (int64_t)blockIdx.x * per, hi = lo + per < rows ? lo + per : rows;
+    double a = 0.0;
+    int64_t i = lo + threadIdx.x;
+    for (; i + 3 * kThreads < hi; i += 4 * kThreads) {   // four loads in flight, summed in index order
+        const float t0 = term[i], t1 = term[i + kThreads], t2 = term[i + 2 * kThreads], t3 = term[i + 3 * kThreads];
+        a += (double)t0;
+        a += (double)t1;
+        a += (double)t2;
+        a += (double)t3;
+    }
+    for (; i < hi; i += kThreads) a += (double)term[i];
+    const double s = block_sum(a, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(kThreads) void head_loss_final(const double *__restrict__ part, int parts, double inv_m, float *__restrict__ loss) {
+    __shared__ double sh[kThreads];
+    double a = 0.0;
+    for (int i = threadIdx.x; i < parts; i += kThreads) a += part[i];
+    const double s = block_sum(a, sh);
+    if (threadIdx.x == 0) *loss = (float)(s * inv_m);
+}
+
+int launch_head_loss(const float *term, int64_t rows, double *part, double inv_m, float *loss, hipStream_t stream) {
+    const int parts = loss_parts(rows);
+    hipLaunchKernelGGL(head_loss_parts, dim3(parts), dim3(kThreads), 0, stream, term, rows, part);
+    if (int rc = check_launch("head_loss_parts")) return rc;
+    hipLaunchKernelGGL(head_loss_final, dim3(1), dim3(kThreads), 0, stream, part, parts, inv_m, loss);
+    return check_launch("head_loss_final");
+}
+
+}  // namespace mot

@@ -1,0 +1,64 @@
+// mot_headcore.hpp -- what the output heads (mot_head.hip: the 512-row byte head, mot_tokhead.hip: the token-level head) share:
+// the factor of the row's closing rms-norm with its derivative (device inline), the three products of a chunk on the shared GEMM
+// launchers, the chunk rule, and the launchers of mot_headcore.hip: the row chain for dx and the loss's fixed-order double sum.
+#pragma once
+#include "mot_desc.hpp"   // up256, Arena: the heads' workspace carves
+
+namespace mot {
+
+constexpr float kHeadEps = 1.1920928955078125e-07f;   // F.rms_norm(eps=None): the fp32 opmath epsilon, bf16 inputs included
+constexpr int kLossParts = 512;                       // doubles of the loss's partial sums in a head's workspace
+
+// norm(h_L) = c x_row and dc/dm0, for n_layer_out identity layers h <- h + norm(h) = h (1 + r), r = (mean(h^2) + eps)^-1/2:
+// each layer scales the row by (1 + r) and its mean square by (1 + r)^2; the derivative is carried forward alongside.
+// L = 0 is the plain norm: c = (m0 + eps)^-1/2, dc = -c^3 / 2.
+__device__ __forceinline__ void row_scale(float m0, int L, float eps, float &c, float &dc) {
+    float m = m0, dm = 1.f;
+    c = 1.f;
+    dc = 0.f;
+    for (int i = 0; i < L; ++i) {
+        const float r = rsqrtf(m + eps), dr = -0.5f * r * r * r * dm, a = 1.f + r;
+        dc = dc * a + c * dr;
+        c *= a;
+        dm = dm * a * a + 2.f * m * a * dr;
+        m *= a * a;
+    }
+    const float r = rsqrtf(m + eps);
+    dc = dc * r - 0.5f * c * r * r * r * dm;
+    c *= r;
+}
+
+// rows per chunk: the largest multiple of 256 rows of per_row_bytes of scratch under the budget, at least 256, never more than the rows
+inline int64_t head_chunk_rows(int64_t budget_bytes, int64_t per_row_bytes, int64_t rows) {
+    int64_t ch = budget_bytes / per_row_bytes / 256 * 256;
+    if (ch < 256) ch = 256;
+    return rows < ch ? rows : ch;
+}
+
+// The products of n rows of a chunk, T = float or __bf16 (x, W and G in T unless said).  G may alias S: no __restrict__ here.
+// s = x W^T into S [n][V]: fp32, or bf16 from bf16 operands when out_bf16
+template <typename T>
+int head_logits(const T *x, const T *W, int64_t n, int K, int V, void *S, bool out_bf16, hipStream_t stream) {
+    if constexpr (sizeof(T) == 2) return launch_gemm_rows_bf16(x, K, n, W, K, K, V, S, V, out_bf16, nullptr, stream);
+    else return launch_gemm_rows(x, K, n, W, K, K, V, (float *)S, V, true, stream);
+}
+// u = G W into fp32 [n][K]; fp32 takes W [V][K] itself, bf16 its k-major copy WT [K][V]
+template <typename T>
+int head_gw(const T *G, const T *W_or_WT, int64_t n, int V, int K, float *u, hipStream_t stream) {
+    if constexpr (sizeof(T) == 2) return launch_gemm_rows_bf16(G, V, n, W_or_WT, V, V, K, u, K, false, nullptr, stream);
+    else return launch_gemm_rows(G, V, n, W_or_WT, K, V, K, u, K, false, stream);
+}
+// dW += G^T x, fp32 [V][K]
+template <typename T>
+int head_dw(const T *G, const T *x, int64_t n, int V, int K, float *dW, hipStream_t stream) {
+    if constexpr (sizeof(T) == 2) return launch_gemm_tn_bf16(G, V, V, x, K, K, n, dW, K, stream);
+    else return launch_gemm_tn(G, V, V, x, K, K, n, dW, K, stream);
+}
+
+// dx_r = u_r + (dc/dm0) (2 / K) (x_r . u_r / c_r) x_r over n rows with row_scale(L) (norm_in), else dx_r = u_r; float and __bf16
+template <typename T>
+int launch_head_chain(const T *x, const float *u, int K, int64_t n, int L, int norm_in, float eps, T *dx, hipStream_t stream);
+// *loss = inv_m * (sum of term[0, rows)) in a fixed order in double; part: kLossParts doubles
+int launch_head_loss(const float *term, int64_t rows, double *part, double inv_m, float *loss, hipStream_t stream);
+
+}  // namespace mot

@@ -5,7 +5,7 @@
 //
 // Per row r of x [N, D], W [V, D], y [N]:  c_r = (mean(x_r^2) + eps)^-1/2 (1 without norm_in),  l = c_r (x_r W^T),  z = cap(l).
 // z is bounded (0 < z < 30, |z| < 15), so lse = zmax + log sum exp(z - zmax) with the constant zmax: no max pass.
-//   loss    = (1 / N) sum_r (lse_r - z_r[y_r])                       fixed-order double sum (mot_rowloss.hpp)
+//   loss    = (1 / N) sum_r (lse_r - z_r[y_r])                       fixed-order double sum (mot_headcore.hip)
 //   dL/dl_r = (1 / N) (softmax(z_r) - onehot(y_r)) dz/dl,   G_r = c_r dL/dl_r,   u = G W,   dW = G^T x,
 //   dx_r    = u_r - c_r^2 (x_r . u_r / D) x_r  (norm_in),  u_r (else)
 // A target outside [0, V) addresses nothing: its term leaves the sum (the mean still divides by N), its row of G is zero, so its row
@@ -15,11 +15,11 @@
 // in bf16 mode: the reference's own rounding point, CastedLinear returns bf16).  tokhead_rows, the V-wide row pass and the new kernel
 // of this file, takes one row per workgroup: it loads the row's logits ONCE with 16-byte accesses into registers, forms c, sum exp,
 // z[y] and the row's loss term, and, when gradients are asked for, writes G in place over the logits from the same registers.  Then
-// u = G W and dW += G^T x are two more products on the shared launchers, and a wave-per-row kernel closes dx.  So a chunk's logits
-// are formed once and a training step costs three products.  The gradients are those of grad_loss = 1; the caller scales them.
-#include "mot_internal.hpp"
-#include "mot_rowloss.hpp"
-#include "mot_tile.hpp"
+// u = G W and dW += G^T x are two more products on the shared launchers, and the heads' wave-per-row chain closes dx.  So a chunk's
+// logits are formed once and a training step costs three products.  The gradients are those of grad_loss = 1; the caller scales them.
+// This unit holds tokhead_rows, the checks and the carve; row_scale, the products, the chunk rule, the chain and the loss's sum are
+// the heads' shared ones (mot_headcore.hpp).
+#include "mot_headcore.hpp"
 
 namespace mot {
 namespace {
@@ -190,32 +190,6 @@ __global__ __launch_bounds__(kRowThreads) void tokhead_rows(T *S, int V, const T
     }
 }
 
-// dx_r = u_r - c_r^2 (x_r . u_r / K) x_r with norm_in (row_scale's dc at L = 0, as the byte head's chain), else u_r; one wave per row
-template <typename T>
-__global__ __launch_bounds__(kThreads) void tokhead_chain_rows(const T *__restrict__ x, const float *__restrict__ u, int K, int64_t rows, int norm_in,
-                                                               float eps, T *__restrict__ dx) {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
-    if (r >= rows) return;
-    const T *xr = x + r * K;
-    const float *ur = u + r * K;
-    float coef = 0.f;
-    if (norm_in) {
-        float ss = 0.f, xu = 0.f;
-        for (int k = lane; k < K; k += 64) {
-            const float a = (float)xr[k];
-            ss += a * a;
-            xu += a * ur[k];
-        }
-        ss = wave_sum(ss);
-        xu = wave_sum(xu);
-        float c, dc;
-        row_scale(ss / (float)K, 0, eps, c, dc);
-        coef = dc * (2.f / (float)K) * xu / c;
-    }
-    for (int k = lane; k < K; k += 64) dx[r * K + k] = (T)(norm_in ? ur[k] + coef * (float)xr[k] : ur[k]);
-}
-
 struct TokGeom {
     int64_t rows, chunk;
     int K, V, norm_in;
@@ -228,16 +202,14 @@ struct TokWs {   // carve of the workspace, offsets in bytes
 };
 
 TokWs tok_ws(const TokGeom &g) {
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t e = g.bf16 ? 2 : 4;
+    Arena a;
     TokWs w{};
-    size_t o = 0;
-    w.term = o, o += up((size_t)g.rows * 4);
-    w.part = o, o += up((size_t)kLossParts * 8);
-    w.S = o, o += up((size_t)g.chunk * g.V * e);
-    w.u = o, o += g.grad_x ? up((size_t)g.chunk * g.K * 4) : 0;
-    w.WT = o, o += g.grad_x && g.bf16 ? up((size_t)g.V * g.K * 2) : 0;
-    w.total = o;
+    w.term = a.take((size_t)g.rows * 4);
+    w.part = a.take((size_t)kLossParts * 8);
+    w.S = a.take((size_t)g.chunk * g.V * (g.bf16 ? 2 : 4));
+    w.u = a.take(g.grad_x ? (size_t)g.chunk * g.K * 4 : 0);
+    w.WT = a.take(g.grad_x && g.bf16 ? (size_t)g.V * g.K * 2 : 0);
+    w.total = a.o;
     return w;
 }
 
@@ -286,14 +258,11 @@ static int token_head_geom(const MotTokenHeadDesc *d, TokGeom *out) {
     g.norm_in = d->norm_in ? 1 : 0;
     g.bf16 = d->dtype == MOT_BF16;
     g.grad_x = d->dx != nullptr;
-    g.eps = d->eps > 0.f ? d->eps : 1.1920928955078125e-07f;   // F.rms_norm(eps=None): the fp32 opmath epsilon, bf16 inputs included
-    int64_t ch = d->chunk_rows;
-    if (ch == 0) {   // the largest multiple of 256 rows whose logits and u stay below kChunkBytes, at least 256
-        const int64_t per_row = (int64_t)g.V * (g.bf16 ? 2 : 4) + (int64_t)g.K * 4;
-        ch = kChunkBytes / per_row / 256 * 256;
-        if (ch < 256) ch = 256;
-    }
-    g.chunk = g.rows < ch ? g.rows : ch;
+    g.eps = d->eps > 0.f ? d->eps : kHeadEps;
+    if (d->chunk_rows)
+        g.chunk = g.rows < d->chunk_rows ? g.rows : d->chunk_rows;
+    else   // the library's choice: a chunk's logits and u stay below kChunkBytes
+        g.chunk = head_chunk_rows(kChunkBytes, (int64_t)g.V * (g.bf16 ? 2 : 4) + (int64_t)g.K * 4, g.rows);
     return MOT_OK;
 }
 
@@ -313,8 +282,7 @@ static int token_head_run(const MotTokenHeadDesc &d, const TokGeom &g, const Tok
     constexpr bool BF = sizeof(T) == 2;
     unsigned char *ws = (unsigned char *)d.workspace;
     float *term = (float *)(ws + w.term), *u = (float *)(ws + w.u);
-    T *S = (T *)(ws + w.S);
-    void *WT = ws + w.WT;
+    T *S = (T *)(ws + w.S), *WT = (T *)(ws + w.WT);
     const T *X = (const T *)d.x, *W = (const T *)d.weight;
     const bool grad = d.dx || d.dW;
     const float inv_n = (float)(1.0 / (double)g.rows);
@@ -324,42 +292,20 @@ static int token_head_run(const MotTokenHeadDesc &d, const TokGeom &g, const Tok
     for (int64_t r0 = 0; r0 < g.rows; r0 += g.chunk) {
         const int64_t n = g.rows - r0 < g.chunk ? g.rows - r0 : g.chunk;
         const T *x = X + r0 * g.K;
-        // s = x W^T for the chunk's rows
-        if (BF)
-            rc = launch_gemm_rows_bf16(x, g.K, n, W, g.K, g.K, g.V, S, g.V, true, nullptr, stream);
-        else
-            rc = launch_gemm_rows((const float *)x, g.K, n, (const float *)W, g.K, g.K, g.V, (float *)S, g.V, true, stream);
-        if (rc) return rc;
+        if ((rc = head_logits<T>(x, W, n, g.K, g.V, S, BF, stream))) return rc;   // s = x W^T for the chunk's rows, in T
         float *stats = d.row_stats ? d.row_stats + r0 : nullptr;
         if (grad)
             rc = launch_rows<T, CAP, true>(S, g, x, d.targets + r0, n, inv_n, term + r0, stats, d.status, stream);
         else
             rc = launch_rows<T, CAP, false>(S, g, x, d.targets + r0, n, inv_n, term + r0, stats, d.status, stream);
         if (rc) return rc;
-        if (d.dx) {   // u = G W, then the row chain
-            if (BF)
-                rc = launch_gemm_rows_bf16(S, g.V, n, WT, g.V, g.V, g.K, u, g.K, false, nullptr, stream);
-            else
-                rc = launch_gemm_rows((const float *)S, g.V, n, (const float *)W, g.K, g.V, g.K, u, g.K, false, stream);
-            if (rc) return rc;
-            hipLaunchKernelGGL(tokhead_chain_rows<T>, dim3((unsigned)((n + kWaves - 1) / kWaves)), dim3(kThreads), 0, stream, x, u, g.K, n, g.norm_in, g.eps,
-                               (T *)d.dx + r0 * g.K);
-            if ((rc = check_launch("tokhead_chain_rows"))) return rc;
+        if (d.dx) {   // u = G W, then the row chain of the plain norm (L = 0)
+            if ((rc = head_gw<T>(S, BF ? WT : W, n, g.V, g.K, u, stream))) return rc;
+            if ((rc = launch_head_chain<T>(x, u, g.K, n, 0, g.norm_in, g.eps, (T *)d.dx + r0 * g.K, stream))) return rc;
         }
-        if (d.dW) {   // dW += G^T x
-            if (BF)
-                rc = launch_gemm_tn_bf16((const __bf16 *)S, g.V, g.V, (const __bf16 *)x, g.K, g.K, n, d.dW, g.K, stream);
-            else
-                rc = launch_gemm_tn((const float *)S, g.V, g.V, (const float *)x, g.K, g.K, n, d.dW, g.K, stream);
-            if (rc) return rc;
-        }
+        if (d.dW && (rc = head_dw<T>(S, x, n, g.V, g.K, d.dW, stream))) return rc;   // dW += G^T x
     }
-    double *part = (double *)(ws + w.part);
-    const int parts = loss_parts(g.rows);
-    hipLaunchKernelGGL(head_loss_parts, dim3(parts), dim3(kThreads), 0, stream, term, g.rows, part);
-    if ((rc = check_launch("head_loss_parts"))) return rc;
-    hipLaunchKernelGGL(head_loss_final, dim3(1), dim3(kThreads), 0, stream, part, parts, 1.0 / (double)g.rows, d.loss);
-    return check_launch("head_loss_final");
+    return launch_head_loss(term, g.rows, (double *)(ws + w.part), 1.0 / (double)g.rows, d.loss, stream);
 }
 
 int launch_token_head_fwd(const MotTokenHeadDesc &d, hipStream_t stream) {

@@ -1059,15 +1059,21 @@ def _byte_head_desc(x, w, targets, method, bpt, n_layer_out, row_stats, loss):
     return d, dev
 
 
+def _head_operands(fn, x, weight, targets, per_row, rows_as):
+    """What the two output heads do to their operands once their own checks have passed: x flat and detached, the weight cast once
+    to x's dtype as CastedLinear does (train_gpt.py:185-186, lm_head_w.bfloat16()), the int64 targets flat, per_row to a row of x."""
+    x2 = _contig(x.detach().reshape(-1, x.shape[-1]), x.dtype, "x")
+    w = _contig(weight.detach().to(x2.dtype), x2.dtype, "weight")
+    t = _contig(targets.reshape(-1), torch.int64, "targets")
+    if t.numel() != x2.shape[0] * per_row:
+        raise ValueError(f"{fn}: {t.numel()} targets for {x2.shape[0]} {rows_as}")
+    return x2, w, t
+
+
 def _byte_head_operands(x, weight, targets, bpt):
     if x.dtype not in (torch.float32, torch.bfloat16):
         raise TypeError(f"byte_head_loss: x must be float32 or bfloat16, got {x.dtype}")
-    D = x.shape[-1]
-    x2 = _contig(x.detach().reshape(-1, D), x.dtype, "x")
-    w = _contig(weight.detach().to(x2.dtype), x2.dtype, "weight")   # CastedLinear: the weight in x's dtype (train_gpt.py:185-186)
-    t = _contig(targets.reshape(-1), torch.int64, "targets")
-    if t.numel() != x2.shape[0] * bpt:
-        raise ValueError(f"byte_head_loss: {t.numel()} targets for {x2.shape[0]} tokens x {bpt} bytes")
+    x2, w, t = _head_operands("byte_head_loss", x, weight, targets, bpt, f"tokens x {bpt} bytes")   # non-int64 targets are refused there
     if w.ndim != 2:
         raise ValueError("byte_head_loss: weight must be (vocab, in_features)")
     return x2, w, t
@@ -1142,12 +1148,7 @@ def _token_head_operands(x, weight, targets, softcap):
     if targets.dtype not in (torch.int64, torch.int32):
         raise TypeError(f"token_head_loss: targets must be int64 or int32, got {targets.dtype}")
     capi.require_device(x, weight, targets)
-    x2 = _contig(x.detach().reshape(-1, x.shape[-1]), x.dtype, "x")
-    w = _contig(weight.detach().to(x2.dtype), x2.dtype, "weight")   # CastedLinear / lm_head_w.bfloat16(): the weight in x's dtype, cast once
-    t = _contig(targets.reshape(-1).to(torch.int64), torch.int64, "targets")
-    if t.numel() != x2.shape[0]:
-        raise ValueError(f"token_head_loss: {t.numel()} targets for {x2.shape[0]} rows")
-    return x2, w, t
+    return _head_operands("token_head_loss", x, weight, targets.to(torch.int64), 1, "rows")
 
 
 class _TokenHeadFn(torch.autograd.Function):
