@@ -1,15 +1,16 @@
-// mot_bwd_linear.hip -- backward of the CONCAT_LINEAR mixin (x = rms_norm?(W.cat(a, b_*) + bias)): dy, dbias, dW and du as dense
-// products (mot_gemm_f32.hip, mot_gemm_bf16.hip; bf16 operands widened or narrowed by mot_convert.hip), then the table gradients
+// mot_bwd_linear.hip -- backward of the CONCAT_LINEAR mixin (x = rms_norm?(W.cat(a, b_*) + bias)): dy by the shared norm backward
+// (mot_lincore.hip), dbias, dW and du as dense products (mot_gemm_f32.hip, mot_gemm_bf16.hip; bf16 operands widened or narrowed by mot_convert.hip), then the table gradients
 // from du through the scatter stage of mot_backward.hip (run_scatter, mot_bwd.hpp).  Called by launch_embed_mix_bwd only.
 #include <stdlib.h>
 
 #include "mot_bwd.hpp"
+#include "mot_lincore.hpp"
 
 namespace mot {
 
 // ==========================================================================================
 // CONCAT_LINEAR backward:  x = rms_norm?(y), y = W u + bias, u = cat(a, b_*)
-//   dy = r_y (g - x mean(g x))                      dy_kernel (one wave per row)
+//   dy = r_y (g - x mean(g x))                      launch_rows_norm_bwd (mot_lincore.hip; fp32, or bf16 from bf16 g and x)
 //   du = dy . W          (N x Dm) @ (Dm x K)        the forward MFMA kernel with dy as dense "token rows";
 //                                                   W in nn.Linear layout IS the k-major operand it wants
 //   dW += dy^T . u       (Dm x N) @ (N x K)         gemm_tn_kernel: split over tokens, fp32 MFMA, atomic accumulate;
@@ -17,48 +18,6 @@ namespace mot {
 //   dbias += colsum(dy)                             colsum_kernel
 //   table gradients: the scatter stage (run_scatter) on du (row layout = the concat layout)
 // ==========================================================================================
-__global__ __launch_bounds__(kThreads) void dy_kernel(const float *__restrict__ g, const float *__restrict__ x,
-                                                      const float *__restrict__ rnorm, int64_t n, int Dm, float *__restrict__ dy) {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
-    if (r >= n) return;
-    const float *gr = g + r * Dm, *xr = x + r * Dm;
-    float m = 0.f;
-    for (int j = lane; j < Dm; j += 64) m += gr[j] * xr[j];
-    m = wave_sum(m) / (float)Dm;
-    const float ry = rnorm[r];
-    for (int j = lane; j < Dm; j += 64) dy[r * Dm + j] = ry * (gr[j] - xr[j] * m);
-}
-
-// the same from bf16 g and x, result in bf16 (the bf16 route never needs an fp32 dy): Dm a multiple of 8, <= 4096
-__global__ __launch_bounds__(kThreads) void dy16_kernel(const __bf16 *__restrict__ g, const __bf16 *__restrict__ x, const float *__restrict__ rnorm, int64_t n,
-                                                        int Dm, __bf16 *__restrict__ dy) {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
-    if (r >= n) return;
-    const __bf16 *gr = g + r * Dm, *xr = x + r * Dm;
-    float8v gv[8], xv[8];
-    float m = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int c = 8 * (lane + 64 * i);
-        gv[i] = (float8v)(0.f); xv[i] = (float8v)(0.f);
-        if (c < Dm) {
-            gv[i] = Elem<__bf16>::loadv(gr + c);
-            xv[i] = Elem<__bf16>::loadv(xr + c);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) m += gv[i][e] * xv[i][e];
-        }
-    }
-    m = wave_sum(m) / (float)Dm;
-    const float ry = rnorm[r];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int c = 8 * (lane + 64 * i);
-        if (c < Dm) Elem<__bf16>::storev_nt(dy + r * Dm + c, (gv[i] - xv[i] * m) * ry);
-    }
-}
-
 __global__ __launch_bounds__(kThreads) void colsum_kernel(const float *__restrict__ a, int64_t n, int cols, float *__restrict__ out) {
     // each workgroup sums a strip of rows for every column, then one atomic per column
     const int64_t rows_per = (n + gridDim.x - 1) / gridDim.x, lo = blockIdx.x * rows_per, hi = min(n, lo + rows_per);
@@ -205,16 +164,12 @@ int launch_embed_mix_bwd_linear(const MotEmbedMixDesc &d, const MotEmbedMixGrads
         dy16p = (const __bf16 *)g16;
         if (d.norm_out) {
             __bf16 *dy16 = (__bf16 *)(ws16 + U.dy16);
-            hipLaunchKernelGGL(dy16_kernel, dim3((unsigned)((N + kWaves - 1) / kWaves)), dim3(kThreads), 0, stream, (const __bf16 *)g16, (const __bf16 *)x16,
-                               d.out_row_rnorm, N, Dm, dy16);
-            if ((rc = check_launch("dy16_kernel"))) return rc;
+            if ((rc = launch_rows_norm_bwd(g16, x16, d.out_row_rnorm, N, Dm, 1, dy16, Dm, nullptr, 0, MOT_BF16, stream))) return rc;
             dy16p = dy16;
         }
         dyp = nullptr;
     } else if (d.norm_out) {
-        hipLaunchKernelGGL(dy_kernel, dim3((unsigned)((N + kWaves - 1) / kWaves)), dim3(kThreads), 0, stream, (const float *)gr.grad_out,
-                           (const float *)d.out, d.out_row_rnorm, N, Dm, dy);
-        if ((rc = check_launch("dy_kernel"))) return rc;
+        if ((rc = launch_rows_norm_bwd(gr.grad_out, d.out, d.out_row_rnorm, N, Dm, 1, dy, Dm, nullptr, 0, MOT_F32, stream))) return rc;
         dyp = dy;
     }
     if (gr.d_bias) {

@@ -1,114 +1,23 @@
 // mot_bytefc.hip -- the linear-on-bytes mixin of modded-nanogpt/runs/71051_mot-in_toks-valemb.py:225-229 (call site 312-314):
 //     u_n = cat_k E_byte[ids[n, k]],   x_n = rms_norm?(E_tok[tok_n] + byte_fc u_n),   byte_fc [model_dim, K = bpt * byte_dim]
 // forward and backward, fp32 and bf16 (include/mot.h, MotByteFcMixDesc).  Composed from the shared pieces -- the index kernels
-// (mot_index.hip), the placed gather (mot_embed.hip), the matrix-product launchers (mot_gemm_f32.hip, mot_gemm_bf16.hip) and the
-// table-gradient scatter (run_scatter, mot_backward.hip) -- plus three kernels of its own: the row pass that finishes the forward
-// in place (adds the token row, rounds where the reference's bf16 run rounds, normalises), the norm's backward, and the id
-// statistics.  The operand u and the gradient rows live in the caller's workspace, slab by slab.
+// (mot_index.hip), the placed gather (mot_embed.hip), the three products (launch_product_nt / _nn / _tn, mot_internal.hpp), the
+// linear front-ends' row passes and pad count (mot_lincore.hip: the finishing pass in its token-row form, the norm's backward for
+// fp32 tensors) and the table-gradient scatter (run_scatter, mot_backward.hip) -- plus one kernel of its own, the norm's backward
+// for bf16 tensors from the pre-norm row.  The operand u and the gradient rows live in the caller's workspace, slab by slab.
 #include "mot_bwd.hpp"
+#include "mot_lincore.hpp"
 
 namespace mot {
 
 constexpr int64_t kFcFwdSlab = 16384;   // rows of u per forward slab: 64 MiB of fp32 at K 1024; 64 x 4 product tiles of 256 x 256 fill the chip once
 constexpr int64_t kFcBwdSlab = 65536;   // rows of [ds | du] per backward slab (run 71051's whole shard: the caller's token order applies)
-constexpr int kFcMaxDim = 2048;
+constexpr int kFcMaxDim = kRowMaxDim;   // the row passes keep a row of model_dim columns in registers (mot_lincore.hip)
 
-// ------------------------------------------------------------------------------------------ kernels
-// The forward's last pass, in place on the product rows p = byte_fc u (one wave per token, a lane owns 16-byte chunks lane,
-// lane + 64, ...): s = tok + p, r = rsqrt(mean(s^2) + eps), x = r s, r kept for the backward.  16 * model_dim bytes of traffic
-// per fp32 token (row in, token row in, row out).  bf16: p arrives rounded by the product kernel, s is rounded before the squares
-// are taken and x on store -- the roundings of the reference's bf16 run (F.linear, the add, rms_norm's result).
-template <typename T>
-__global__ __launch_bounds__(kThreads) void bytefc_finish_kernel(T *__restrict__ out, const int32_t *__restrict__ tokens, int64_t n,
-                                                                 const T *__restrict__ tok_table, int64_t tok_rows, int Dm, int norm_out, float eps,
-                                                                 float *__restrict__ row_rnorm, uint32_t *status) {
-    using vec_t = typename Elem<T>::vec;
-    constexpr int VEC = Elem<T>::kVec, NCH = kFcMaxDim / VEC / 64;   // chunks a lane holds: 8 of 4 floats, 4 of 8 bf16
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
-    if (r >= n) return;
-    int tok = __builtin_amdgcn_readfirstlane(tokens[r]);   // wave-uniform: the token row's base stays in scalar registers
-    if ((uint64_t)(uint32_t)tok >= (uint64_t)tok_rows) {
-        if (status && lane == 0) atomicOr(status, kStatusTokenOor);
-        tok = 0;
-    }
-    const T *trow = tok_table + (int64_t)tok * Dm;
-    T *p = out + r * Dm;
-    const int nv = Dm / VEC;
-    vec_t s[NCH];
-    float ss = 0.f;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-        const int j = lane + 64 * i;
-        s[i] = (vec_t)(0.f);
-        if (j < nv) {
-            vec_t v = Elem<T>::loadv(p + VEC * j) + Elem<T>::loadv(trow + VEC * j);
-            if constexpr (sizeof(T) == 2) v = __builtin_convertvector(__builtin_convertvector(v, bf16x8v), float8v);   // s = bf16(tok + p)
-            s[i] = v;
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) ss += v[e] * v[e];
-        }
-    }
-    const float rs = norm_out ? rms_scale(wave_sum(ss), Dm, eps) : 1.0f;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-        const int j = lane + 64 * i;
-        if (j < nv) Elem<T>::storev_nt(p + VEC * j, s[i] * rs);
-    }
-    if (row_rnorm && lane == 0) row_rnorm[r] = rs;
-}
-
-// Back through the norm (dy_kernel's arithmetic, mot_bwd_linear.hip) from the saved fp32 output: ds = r (g - x mean(g x)), or
-// ds = g without the norm (both dtypes), written in fp32 into columns [0, Dm) of the gradient rows (row stride ld) and, for the bf16
-// products, once more as bf16.
-template <typename T>
-__global__ __launch_bounds__(kThreads) void bytefc_ds_kernel(const T *__restrict__ g, const T *__restrict__ x, const float *__restrict__ rnorm, int64_t n,
-                                                             int Dm, int norm_out, float *__restrict__ ds, int ld, __bf16 *__restrict__ ds16) {
-    using vec_t = typename Elem<T>::vec;
-    constexpr int VEC = Elem<T>::kVec, NCH = kFcMaxDim / VEC / 64;
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
-    if (r >= n) return;
-    const T *gr = g + r * Dm, *xr = x + r * Dm;
-    const int nv = Dm / VEC;
-    vec_t gv[NCH], xv[NCH];
-    float m = 0.f;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-        const int j = lane + 64 * i;
-        gv[i] = (vec_t)(0.f); xv[i] = (vec_t)(0.f);
-        if (j < nv) {
-            gv[i] = Elem<T>::loadv(gr + VEC * j);
-            if (norm_out) {
-                xv[i] = Elem<T>::loadv(xr + VEC * j);
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) m += gv[i][e] * xv[i][e];
-            }
-        }
-    }
-    float ry = 1.0f;
-    if (norm_out) {
-        m = wave_sum(m) / (float)Dm;
-        ry = rnorm[r];
-    }
-    float *dr = ds + r * (int64_t)ld;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-        const int j = lane + 64 * i;
-        if (j < nv) {
-            const vec_t d = norm_out ? (gv[i] - xv[i] * m) * ry : gv[i];
-#pragma unroll
-            for (int q = 0; q < VEC / 4; ++q) *(float4v *)(dr + VEC * j + 4 * q) = float4v{d[4 * q], d[4 * q + 1], d[4 * q + 2], d[4 * q + 3]};
-            if constexpr (sizeof(T) == 2) {
-                if (ds16) Elem<__bf16>::storev_nt(ds16 + r * Dm + VEC * j, d);
-            }
-        }
-    }
-}
-
-// The same for bf16 tensors, from the pre-norm row instead of the saved output: the forward's x is a bf16 tensor, three roundings
-// (2^-9 each) away from the exact row, and r (g - x mean(g x)) built on it misses the exact ds by 2e-4 .. 8e-4 of its largest
-// element -- the token-table gradient, a plain sum of ds rows, would carry that (measured on the host at model_dim 64 .. 1024).
+// ------------------------------------------------------------------------------------------ kernel
+// The norm's backward for bf16 tensors, from the pre-norm row instead of the saved output (which launch_rows_norm_bwd, the fp32
+// tensors' way, reads): the forward's x is a bf16 tensor, three roundings (2^-9 each) away from the exact row, and
+// r (g - x mean(g x)) built on it misses the exact ds by 2e-4 .. 8e-4 of its largest element -- the token-table gradient, a plain sum of ds rows, would carry that (measured on the host at model_dim 64 .. 1024).
 // So the backward forms p = byte_fc u once more, keeps its fp32 sums (they sit in columns [0, Dm) of the gradient rows when this
 // kernel starts), and takes s = tok + p, r and x = r s in fp32 from there: ds then agrees with the float64 gradient at the
 // bf16-valued operands like the fp32 path does, for one more product of the forward's size.  Written in place, and as bf16.
@@ -149,29 +58,6 @@ __global__ __launch_bounds__(kThreads) void bytefc_ds16_kernel(const __bf16 *__r
             *(float4v *)(pr + 8 * j + 4) = float4v{d[4], d[5], d[6], d[7]};
             Elem<__bf16>::storev_nt(ds16 + r * Dm + 8 * j, d);
         }
-    }
-}
-
-// the statistics of runs/79_*.py:484-488 as the fused front-end counts them: tokens, byte slots and, with ids from the
-// token->byte table, pads before and after the pull (padded == nullptr: ids given, the first two only)
-__global__ __launch_bounds__(kThreads) void bytefc_count_kernel(const int64_t *__restrict__ padded, const int64_t *__restrict__ after, int64_t n_slots,
-                                                                int64_t pad, int64_t n_tokens, int64_t *counters) {
-    if (padded) {
-        int before = 0, aft = 0;
-        for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n_slots; i += (int64_t)gridDim.x * kThreads) {
-            before += padded[i] == pad;
-            aft += after[i] == pad;
-        }
-        before = (int)wave_sum((float)before);   // <= 64 * a few thousand per wave: exact in fp32
-        aft = (int)wave_sum((float)aft);
-        if ((threadIdx.x & 63) == 0) {
-            atomicAdd((unsigned long long *)counters + 2, (unsigned long long)before);
-            atomicAdd((unsigned long long *)counters + 3, (unsigned long long)aft);
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        atomicAdd((unsigned long long *)counters + 0, (unsigned long long)n_tokens);
-        atomicAdd((unsigned long long *)counters + 1, (unsigned long long)n_slots);
     }
 }
 
@@ -299,10 +185,7 @@ int launch_byte_fc_mix_fwd(const MotByteFcMixDesc &d, hipStream_t stream) {
                 if ((rc = launch_wave_ids16(e, ids16, stream))) return rc;
                 return launch_concat16(e, d.tokens, nullptr, ids16, N, nullptr, d.out, d.out_row_rnorm, stream, true);
             }
-            if (d.counters) {
-                hipLaunchKernelGGL(bytefc_count_kernel, dim3(1), dim3(kThreads), 0, stream, (const int64_t *)nullptr, d.ids, slots, (int64_t)d.pad_byte, N, d.counters);
-                if ((rc = check_launch("bytefc_count_kernel"))) return rc;
-            }
+            if (d.counters && (rc = launch_count_pads(nullptr, d.ids, slots, d.pad_byte, N, d.counters, stream))) return rc;
             return launch_concat16(e, d.tokens, d.ids, nullptr, N, nullptr, d.out, d.out_row_rnorm, stream, true);
         }
     }
@@ -317,12 +200,7 @@ int launch_byte_fc_mix_fwd(const MotByteFcMixDesc &d, hipStream_t stream) {
         if (d.pull_dir == MOT_PULL_NONE && d.out_ids_pulled)   // nothing is pulled: that output is the padded tensor again
             if ((rc = launch_tokens_to_bytes(d.tokens, N, d.ttb, d.ttb_elem_bytes, d.ttb_rows, bpt, d.out_ids_pulled, nullptr, stream))) return rc;
     }
-    if (d.counters) {
-        int64_t blocks = padded_c ? (slots + kThreads * 16 - 1) / (kThreads * 16) : 1;
-        if (blocks > 1024) blocks = 1024;
-        hipLaunchKernelGGL(bytefc_count_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, stream, padded_c, ids, slots, (int64_t)d.pad_byte, N, d.counters);
-        if ((rc = check_launch("bytefc_count_kernel"))) return rc;
-    }
+    if (d.counters && (rc = launch_count_pads(padded_c, ids, slots, d.pad_byte, N, d.counters, stream))) return rc;
     // 2. slab by slab: u = the token's byte rows side by side, p = u byte_fc^T into `out`, then the row pass in place
     char *u = ws + L.u;
     for (int64_t r0 = 0; r0 < N; r0 += kFcFwdSlab) {
@@ -331,17 +209,9 @@ int launch_byte_fc_mix_fwd(const MotByteFcMixDesc &d, hipStream_t stream) {
                                             kStatusByteOor, d.dtype, stream))) return rc;
         char *out = (char *)d.out + (size_t)r0 * Dm * esz;
         float *rr = d.out_row_rnorm ? d.out_row_rnorm + r0 : nullptr;
-        const unsigned nb = (unsigned)((n + kWaves - 1) / kWaves);
-        if (bf) {
-            if ((rc = launch_gemm_rows_bf16(u, K, n, d.byte_fc, K, K, Dm, out, Dm, true, nullptr, stream))) return rc;
-            hipLaunchKernelGGL(bytefc_finish_kernel<__bf16>, dim3(nb), dim3(kThreads), 0, stream, (__bf16 *)out, d.tokens + r0, n, (const __bf16 *)d.tok_table,
-                               d.tok_rows, Dm, d.norm_out, eps, rr, d.status);
-        } else {
-            if ((rc = launch_gemm_rows((const float *)u, K, n, (const float *)d.byte_fc, K, K, Dm, (float *)out, Dm, true, stream))) return rc;
-            hipLaunchKernelGGL(bytefc_finish_kernel<float>, dim3(nb), dim3(kThreads), 0, stream, (float *)out, d.tokens + r0, n, (const float *)d.tok_table,
-                               d.tok_rows, Dm, d.norm_out, eps, rr, d.status);
-        }
-        if ((rc = check_launch("bytefc_finish_kernel"))) return rc;
+        if ((rc = launch_product_nt(d.dtype, u, K, n, d.byte_fc, K, K, Dm, out, Dm, bf, nullptr, false, stream))) return rc;
+        // s = tok + p, x = r s: 16 * model_dim bytes of traffic per fp32 token (row in, token row in, row out)
+        if ((rc = launch_rows_finish_tok(out, d.tokens + r0, d.tok_table, d.tok_rows, n, Dm, d.norm_out, eps, rr, d.status, d.dtype, stream))) return rc;
     }
     return MOT_OK;
 }
@@ -373,10 +243,9 @@ int launch_byte_fc_mix_bwd(const MotByteFcMixDesc &d, const MotByteFcMixGrads &g
     const int per = scatter_split_per(Dm, Db, bpt);
     for (int64_t r0 = 0; r0 < N; r0 += L.slab) {
         const int64_t n = N - r0 < L.slab ? N - r0 : L.slab;
-        const unsigned nb = (unsigned)((n + kWaves - 1) / kWaves);
         const char *g = (const char *)gr.grad_out + (size_t)r0 * Dm * esz;
         const bool saved = d.norm_out && !bf;   // the fp32 backward reads the forward's x and r
-        const char *x = saved ? (const char *)d.out + (size_t)r0 * Dm * esz : g;
+        const char *x = saved ? (const char *)d.out + (size_t)r0 * Dm * esz : nullptr;
         const float *rn = saved ? d.out_row_rnorm + r0 : nullptr;
         const int64_t *ids = d.ids + r0 * bpt;
         // 1. u again; 2. ds into columns [0, Dm) of the gradient rows; 3. du = ds byte_fc into columns [Dm, Dm + K); 4. d_byte_fc += ds^T u
@@ -384,23 +253,16 @@ int launch_byte_fc_mix_bwd(const MotByteFcMixDesc &d, const MotByteFcMixGrads &g
                                             d.dtype, stream))) return rc;
         if (bf && d.norm_out) {   // from the pre-norm row: p = u byte_fc^T again, fp32 sums kept (see bytefc_ds16_kernel)
             if ((rc = launch_gemm_rows_bf16(u, K, n, d.byte_fc, K, K, Dm, rows, ld, false, nullptr, stream))) return rc;
-            hipLaunchKernelGGL(bytefc_ds16_kernel, dim3(nb), dim3(kThreads), 0, stream, (const __bf16 *)g, d.tokens + r0, n, (const __bf16 *)d.tok_table, d.tok_rows,
-                               Dm, eps, rows, ld, ds16);
-        } else if (bf) {
-            hipLaunchKernelGGL(bytefc_ds_kernel<__bf16>, dim3(nb), dim3(kThreads), 0, stream, (const __bf16 *)g, (const __bf16 *)g, (const float *)nullptr, n, Dm, 0,
-                               rows, ld, ds16);
-        } else {
-            hipLaunchKernelGGL(bytefc_ds_kernel<float>, dim3(nb), dim3(kThreads), 0, stream, (const float *)g, (const float *)x, rn, n, Dm, d.norm_out, rows, ld,
-                               (__bf16 *)nullptr);
+            hipLaunchKernelGGL(bytefc_ds16_kernel, dim3((unsigned)((n + kWaves - 1) / kWaves)), dim3(kThreads), 0, stream, (const __bf16 *)g, d.tokens + r0, n,
+                               (const __bf16 *)d.tok_table, d.tok_rows, Dm, eps, rows, ld, ds16);
+            if ((rc = check_launch("bytefc_ds16_kernel"))) return rc;
+        } else if ((rc = launch_rows_norm_bwd(g, x, rn, n, Dm, saved, bf ? ds16 : nullptr, Dm, rows, ld, d.dtype, stream))) {   // fp32, or ds = g
+            return rc;
         }
-        if ((rc = check_launch("bytefc_ds_kernel"))) return rc;
-        if (bf) {
-            if ((rc = launch_gemm_rows_bf16(ds16, Dm, n, wt16, Dm, Dm, K, rows + Dm, ld, false, nullptr, stream))) return rc;
-            if ((rc = launch_gemm_tn_bf16(ds16, Dm, Dm, (const __bf16 *)u, K, K, n, dW, K, stream))) return rc;
-        } else {
-            if ((rc = launch_gemm_rows(rows, ld, n, (const float *)d.byte_fc, K, Dm, K, rows + Dm, ld, false, stream))) return rc;
-            if ((rc = launch_gemm_tn(rows, ld, Dm, (const float *)u, K, K, n, dW, K, stream))) return rc;
-        }
+        const void *ds = bf ? (const void *)ds16 : rows;   // the products' operand: the bf16 copy, or columns [0, Dm) of the rows
+        const int ld_ds = bf ? Dm : ld;
+        if ((rc = launch_product_nn(d.dtype, ds, ld_ds, n, bf ? (const void *)wt16 : d.byte_fc, bf ? Dm : K, Dm, K, rows + Dm, ld, stream))) return rc;
+        if ((rc = launch_product_tn(d.dtype, ds, ld_ds, Dm, u, K, K, n, dW, K, stream))) return rc;
         // 5. the table gradients from [ds | du]
         MotEmbedMixDesc e{};
         e.struct_size = sizeof(MotEmbedMixDesc); e.dtype = MOT_F32; e.mode = MOT_MIX_CONCAT_LINEAR;

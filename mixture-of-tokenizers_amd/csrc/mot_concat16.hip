@@ -3,7 +3,7 @@
 // (ByteMixinConcat on FlexibleEmbedding's outputs, scaled-pre-train/train_gpt.py:342-379, 430-443, CastedLinear 185-186;
 //  DigitMixinConcat, mathblations/model.py:256-268), bf16 tables / weight / output, fp32 accumulation.
 //
-// The composed path (index kernels -> concat_rows_kernel -> gemm_rows_bf16_kernel -> rows_rms_inplace_kernel) spends 40 % of
+// The composed path (index kernels -> concat_rows_kernel -> gemm_rows_bf16_kernel -> rows_finish_kernel) spends 40 % of
 // its time outside the contraction and runs the contraction itself at 23 % of the bf16 MFMA peak: 128 x 128 blocks read one
 // 16-byte LDS fragment per MFMA, and the concat operand makes two trips through HBM.  Here
 //   * a workgroup owns WHOLE output rows (64 MT tokens x all Dm = 128 NT columns; 8 waves as 2 x 4, a wave 32 MT x 32 NT), so

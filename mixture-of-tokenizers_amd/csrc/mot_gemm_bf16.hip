@@ -385,7 +385,7 @@ int launch_gemm_rows_bf16(const void *A_, int lda, int64_t n, const void *B_, in
     return check_launch("gemm_rows_bf16_kernel");
 }
 
-// C[m][k] += sum_n A[n][m] * B[n][k]   (A: rows x M, B: rows x Kc, both bf16 ROW-major as the forward and dy_kernel leave them;
+// C[m][k] += sum_n A[n][m] * B[n][k]   (A: rows x M, B: rows x Kc, both bf16 ROW-major as the forward and rows_norm_bwd_kernel leave them;
 // C fp32, leading dimension ldc) on v_mfma_f32_32x32x16_bf16: dW = dy^T u with the token index as the contraction index.
 // Both MFMA operands want 8 consecutive CONTRACTION elements per lane, i.e. a column of the row-major tiles: the tiles go into
 // LDS as they are (64 token rows x 128 columns, rows padded to 320 bytes) and are read back with ds_read_b64_tr_b16, the

@@ -189,7 +189,7 @@ static int byte_head_fwd_run(const MotByteHeadDesc &d, const HeadGeom &g, const 
     for (int64_t r0 = 0; r0 < g.rows; r0 += g.chunk) {
         const int64_t n = g.rows - r0 < g.chunk ? g.rows - r0 : g.chunk;
         const T *x = (const T *)d.x + r0 * g.K;
-        if ((rc = head_logits<T>(x, (const T *)d.weight, n, g.K, kV, S, false, stream))) return rc;
+        if ((rc = launch_product_nt(head_dtype<T>, x, g.K, n, d.weight, g.K, g.K, kV, S, kV, false, nullptr, false, stream))) return rc;
         hipLaunchKernelGGL(head_fwd_rows<T>, dim3((unsigned)((n + kWaves - 1) / kWaves)), dim3(kThreads), 0, stream, S, x, g.K, d.targets + r0 * g.tpr, g.tpr, n,
                            d.n_layer_out, g.eps, lse + r0, cst + r0, term + r0, d.status);
         if ((rc = check_launch("head_fwd_rows"))) return rc;
@@ -224,12 +224,12 @@ static int byte_head_bwd_run(const MotByteHeadDesc &d, const HeadGeom &g, const 
     for (int64_t r0 = 0; r0 < g.rows; r0 += g.chunk) {
         const int64_t n = g.rows - r0 < g.chunk ? g.rows - r0 : g.chunk;
         const T *x = (const T *)d.x + r0 * g.K;
-        if ((rc = head_logits<T>(x, W, n, g.K, kV, S, false, stream))) return rc;
+        if ((rc = launch_product_nt(head_dtype<T>, x, g.K, n, W, g.K, g.K, kV, S, kV, false, nullptr, false, stream))) return rc;
         hipLaunchKernelGGL(head_grad_rows<T>, dim3((unsigned)((n + kWaves - 1) / kWaves)), dim3(kThreads), 0, stream, S, d.targets + r0 * g.tpr, g.tpr, n,
                            lse + r0, cst + r0, grad_loss, inv_m, G);
         if ((rc = check_launch("head_grad_rows"))) return rc;
-        if ((rc = head_gw<T>(G, BF ? WT : W, n, kV, g.K, u, stream))) return rc;
-        if ((rc = head_dw<T>(G, x, n, kV, g.K, dW, stream))) return rc;
+        if ((rc = launch_product_nn(head_dtype<T>, G, kV, n, BF ? WT : W, BF ? kV : g.K, kV, g.K, u, g.K, stream))) return rc;
+        if ((rc = launch_product_tn(head_dtype<T>, G, kV, kV, x, g.K, g.K, n, dW, g.K, stream))) return rc;
         if ((rc = launch_head_chain<T>(x, u, g.K, n, d.n_layer_out, 1, g.eps, dx + r0 * g.K, stream))) return rc;
     }
     return MOT_OK;

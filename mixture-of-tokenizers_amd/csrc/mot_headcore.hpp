@@ -1,6 +1,7 @@
 // mot_headcore.hpp -- what the output heads (mot_head.hip: the 512-row byte head, mot_tokhead.hip: the token-level head) share:
-// the factor of the row's closing rms-norm with its derivative (device inline), the three products of a chunk on the shared GEMM
-// launchers, the chunk rule, and the launchers of mot_headcore.hip: the row chain for dx and the loss's fixed-order double sum.
+// the factor of the row's closing rms-norm with its derivative (device inline), the chunk rule, and the launchers of
+// mot_headcore.hip: the row chain for dx and the loss's fixed-order double sum.
+// Their products are launch_product_nt / _nn / _tn (mot_internal.hpp).
 #pragma once
 #include "mot_desc.hpp"   // up256, Arena: the heads' workspace carves
 
@@ -35,25 +36,8 @@ inline int64_t head_chunk_rows(int64_t budget_bytes, int64_t per_row_bytes, int6
     return rows < ch ? rows : ch;
 }
 
-// The products of n rows of a chunk, T = float or __bf16 (x, W and G in T unless said).  G may alias S: no __restrict__ here.
-// s = x W^T into S [n][V]: fp32, or bf16 from bf16 operands when out_bf16
-template <typename T>
-int head_logits(const T *x, const T *W, int64_t n, int K, int V, void *S, bool out_bf16, hipStream_t stream) {
-    if constexpr (sizeof(T) == 2) return launch_gemm_rows_bf16(x, K, n, W, K, K, V, S, V, out_bf16, nullptr, stream);
-    else return launch_gemm_rows(x, K, n, W, K, K, V, (float *)S, V, true, stream);
-}
-// u = G W into fp32 [n][K]; fp32 takes W [V][K] itself, bf16 its k-major copy WT [K][V]
-template <typename T>
-int head_gw(const T *G, const T *W_or_WT, int64_t n, int V, int K, float *u, hipStream_t stream) {
-    if constexpr (sizeof(T) == 2) return launch_gemm_rows_bf16(G, V, n, W_or_WT, V, V, K, u, K, false, nullptr, stream);
-    else return launch_gemm_rows(G, V, n, W_or_WT, K, V, K, u, K, false, stream);
-}
-// dW += G^T x, fp32 [V][K]
-template <typename T>
-int head_dw(const T *G, const T *x, int64_t n, int V, int K, float *dW, hipStream_t stream) {
-    if constexpr (sizeof(T) == 2) return launch_gemm_tn_bf16(G, V, V, x, K, K, n, dW, K, stream);
-    else return launch_gemm_tn(G, V, V, x, K, K, n, dW, K, stream);
-}
+// the `dtype` argument of those products for T = float or __bf16
+template <typename T> constexpr int head_dtype = sizeof(T) == 2 ? MOT_BF16 : MOT_F32;
 
 // dx_r = u_r + (dc/dm0) (2 / K) (x_r . u_r / c_r) x_r over n rows with row_scale(L) (norm_in), else dx_r = u_r; float and __bf16
 template <typename T>

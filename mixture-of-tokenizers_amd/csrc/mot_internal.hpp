@@ -85,6 +85,25 @@ int launch_gemm_rows_f32_256(const float *A, int lda, int64_t n, const float *B,
                              hipStream_t stream);
 // C[m][k] += sum_n A[n][m] * B[n][k]  (bf16 row-major operands, fp32 atomics into C; mot_gemm_bf16.hip); lda / ldb / M / Kc multiples of 8
 int launch_gemm_tn_bf16(const __bf16 *A, int lda, int M, const __bf16 *B, int ldb, int Kc, int64_t rows, float *C, int ldc, hipStream_t stream);
+// The three products of a linear layer over n rows, on the fp32 or the bf16 launcher above by `dtype` (what A and B hold).
+// None says __restrict__: the heads' G aliases their S.
+// C[n][c] = sum_r A[n][r] B[c][r] (+ bias[c]; += with accumulate).  C is fp32, or bf16 from bf16 operands when out_bf16.
+inline int launch_product_nt(int dtype, const void *A, int lda, int64_t n, const void *B, int ldb, int R, int Nc, void *C, int ldc, bool out_bf16,
+                             const void *bias, bool accumulate, hipStream_t stream) {
+    if (dtype == MOT_BF16) return launch_gemm_rows_bf16(A, lda, n, B, ldb, R, Nc, C, ldc, out_bf16, bias, stream, accumulate);
+    return launch_gemm_rows((const float *)A, lda, n, (const float *)B, ldb, R, Nc, (float *)C, ldc, true, stream, (const float *)bias, accumulate);
+}
+// C[n][c] = sum_r A[n][r] B[r][c] into fp32.  fp32 takes B [R][ldb] itself, bf16 its k-major copy [Nc][ldb].
+inline int launch_product_nn(int dtype, const void *A, int lda, int64_t n, const void *B_or_BT, int ldb, int R, int Nc, float *C, int ldc,
+                             hipStream_t stream) {
+    if (dtype == MOT_BF16) return launch_gemm_rows_bf16(A, lda, n, B_or_BT, ldb, R, Nc, C, ldc, false, nullptr, stream);
+    return launch_gemm_rows((const float *)A, lda, n, (const float *)B_or_BT, ldb, R, Nc, C, ldc, false, stream);
+}
+// C[m][c] += sum_n A[n][m] B[n][c] into fp32 (atomics)
+inline int launch_product_tn(int dtype, const void *A, int lda, int M, const void *B, int ldb, int Nc, int64_t n, float *C, int ldc, hipStream_t stream) {
+    if (dtype == MOT_BF16) return launch_gemm_tn_bf16((const __bf16 *)A, lda, M, (const __bf16 *)B, ldb, Nc, n, C, ldc, stream);
+    return launch_gemm_tn((const float *)A, lda, M, (const float *)B, ldb, Nc, n, C, ldc, stream);
+}
 int launch_transpose_f32(const float *src, int rows, int cols, float *dst, hipStream_t stream);                        // dst[c][r] = src[r][c]  (mot_gemm_f32.hip)
 // conversions between the fp32 and bf16 sides (mot_convert.hip)
 int launch_widen(const void *src_bf16, size_t n, float *dst, hipStream_t stream);                                    // dst[i] = float(src[i])

@@ -5,7 +5,7 @@
 // (mathblations/model.py:256-268, 323-327: digits first, bias, no norms).
 //
 // Two implementations live here.  The DEFAULT is composed from plain kernels (see "composed path" below: index kernels, seam
-// gather writing the concat operand, dense MFMA kernel, row norm; fp32 and bf16) and runs 20-30 % faster; the one-launch fused
+// gather writing the concat operand, dense MFMA kernel, and the row pass and pad count of mot_lincore.hip; fp32 and bf16) and runs 20-30 % faster; the one-launch fused
 // tile kernel described next was the first path and is kept for learned embedding scalars and behind MOT_LIN_FUSED=1.
 //
 // This mode is a dense contraction over K = Dt + bpt*Db per token (~285 FLOP/B at
@@ -24,6 +24,7 @@
 // before the current step's MFMAs and written to the other buffer after them; one barrier per step.
 #include <stdlib.h>
 
+#include "mot_lincore.hpp"
 #include "mot_mix.hpp"
 
 namespace mot {
@@ -358,7 +359,7 @@ static int nt_of(int Dm) {
 // With the byte ids already in HBM (the module seam: FlexibleEmbedding hands them over as the reference's loader made
 // them) the forward is composed from three plain kernels: the seam gather writes the normalised concat operand u
 // [tokens, K] (token part and byte part placed side by side), gemm_rows_kernel contracts it with W at ~68 % of the fp32
-// MFMA peak (the fused tile kernel below reaches 48 %), and a row pass applies the output norm.  u costs two extra passes
+// MFMA peak (the fused tile kernel below reaches 48 %), and the shared row pass (launch_rows_finish) applies the output norm.  u costs two extra passes
 // over tokens x K floats, which the faster contraction more than pays for; it is built in slabs of kSlabRows rows so the
 // scratch stays bounded.  The fused kernel remains the path for ids pulled in-kernel from the token->byte table.
 constexpr int64_t kSlabRows = 65536;
@@ -378,70 +379,6 @@ static size_t composed_rnorm_floats(const MotEmbedMixDesc &d) { return ((size_t)
 // buffers when it asked for them, else into scratch behind u (2 x tokens x bpt int64)
 static size_t composed_id_words(const MotEmbedMixDesc &d) {
     return d.id_source == MOT_IDS_FROM_TTB ? 2 * (size_t)(d.n_rows * d.tokens_per_row) * (size_t)d.bpt : 0;
-}
-
-// x[r] *= rsqrt(mean(x[r]^2) + eps) in place, one wave per row; the factor is kept for the backward.  For bf16 the row IS
-// the bf16 tensor the reference's CastedLinear returns (train_gpt.py:185-186); norm() upcasts it (172-173), one rounding on store.
-template <typename T>
-__global__ __launch_bounds__(kThreads) void rows_rms_inplace_kernel(T *__restrict__ x, int64_t n, int dim, float eps, float *__restrict__ row_rnorm) {
-    using vec_t = typename Elem<T>::vec;            // 16 bytes: 4 floats / 8 bf16, widened to floats
-    constexpr int VEC = Elem<T>::kVec, kKeep = 4;    // a lane keeps up to kKeep vectors of the row between the two passes
-    auto sumsq = [](const vec_t &v) {
-        float t = 0.f;
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) t += v[e] * v[e];
-        return t;
-    };
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
-    if (r >= n) return;
-    T *p = x + r * dim;
-    if ((dim % VEC) == 0 && (((uintptr_t)x | ((size_t)dim * sizeof(T))) & 15) == 0) {
-        const int nv = dim / VEC;
-        vec_t keep[kKeep];
-        float ss = 0.f;
-#pragma unroll
-        for (int i = 0; i < kKeep; ++i) {
-            const int j = lane + 64 * i;
-            keep[i] = j < nv ? Elem<T>::loadv(p + VEC * j) : (vec_t)(0.f);
-            ss += sumsq(keep[i]);
-        }
-        for (int j = lane + 64 * kKeep; j < nv; j += 64) ss += sumsq(Elem<T>::loadv(p + VEC * j));
-        const float rs = rms_scale(wave_sum(ss), dim, eps);
-#pragma unroll
-        for (int i = 0; i < kKeep; ++i) {
-            const int j = lane + 64 * i;
-            if (j < nv) Elem<T>::storev_nt(p + VEC * j, keep[i] * rs);
-        }
-        for (int j = lane + 64 * kKeep; j < nv; j += 64) Elem<T>::storev_nt(p + VEC * j, Elem<T>::loadv(p + VEC * j) * rs);
-        if (row_rnorm && lane == 0) row_rnorm[r] = rs;
-        return;
-    }
-    float ss = 0.f;
-    for (int j = lane; j < dim; j += 64) { const float v = (float)p[j]; ss += v * v; }
-    const float rs = rms_scale(wave_sum(ss), dim, eps);
-    for (int j = lane; j < dim; j += 64) p[j] = (T)((float)p[j] * rs);
-    if (row_rnorm && lane == 0) row_rnorm[r] = rs;
-}
-
-// the statistics of runs/79_*.py:484-488 from the two id tensors: tokens, byte slots, pads before the pull, pads after
-__global__ __launch_bounds__(kThreads) void count_pads_kernel(const int64_t *__restrict__ padded, const int64_t *__restrict__ after, int64_t n_slots,
-                                                              int64_t pad, int64_t n_tokens, int64_t *counters) {
-    int before = 0, aft = 0;
-    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n_slots; i += (int64_t)gridDim.x * kThreads) {
-        before += padded[i] == pad;
-        aft += after[i] == pad;
-    }
-    before = (int)wave_sum((float)before);   // <= 64 * a few thousand per wave: exact in fp32
-    aft = (int)wave_sum((float)aft);
-    if ((threadIdx.x & 63) == 0) {
-        atomicAdd((unsigned long long *)counters + 2, (unsigned long long)before);
-        atomicAdd((unsigned long long *)counters + 3, (unsigned long long)aft);
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        atomicAdd((unsigned long long *)counters + 0, (unsigned long long)n_tokens);
-        atomicAdd((unsigned long long *)counters + 1, (unsigned long long)n_slots);
-    }
 }
 
 static int launch_composed(const MotEmbedMixDesc &d, hipStream_t stream);
@@ -475,13 +412,7 @@ static int launch_composed_from_ttb(const MotEmbedMixDesc &d, hipStream_t stream
     } else if (d.out_ids_pulled) {   // nothing is pulled: that output is the padded tensor again
         if ((rc = launch_tokens_to_bytes(d.tokens, N, d.ttb, d.ttb_elem_bytes, d.ttb_rows, d.bpt, d.out_ids_pulled, nullptr, stream))) return rc;
     }
-    if (d.counters) {
-        int64_t blocks = (slots + kThreads * 16 - 1) / (kThreads * 16);
-        if (blocks > 1024) blocks = 1024;
-        if (blocks < 1) blocks = 1;
-        hipLaunchKernelGGL(count_pads_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, stream, padded, after, slots, (int64_t)d.pad_byte, N, d.counters);
-        if ((rc = check_launch("count_pads_kernel"))) return rc;
-    }
+    if (d.counters && (rc = launch_count_pads(padded, after, slots, d.pad_byte, N, d.counters, stream))) return rc;
     MotEmbedMixDesc g = d;
     g.id_source = MOT_IDS_GIVEN;
     g.ids_a = after;
@@ -530,15 +461,9 @@ static int launch_composed(const MotEmbedMixDesc &d, hipStream_t stream) {
         }
         char *out = (char *)d.out + r0 * Dm * esz;
         float *rr = d.out_row_rnorm ? d.out_row_rnorm + r0 : nullptr;
-        const unsigned nb = (unsigned)((n + kWaves - 1) / kWaves);
-        if (bf) {
-            if ((rc = launch_gemm_rows_bf16(u, K, n, d.weight, K, K, Dm, out, Dm, true, d.bias, stream))) return rc;
-            if (d.norm_out) hipLaunchKernelGGL(rows_rms_inplace_kernel<__bf16>, dim3(nb), dim3(kThreads), 0, stream, (__bf16 *)out, n, Dm, eps, rr);
-        } else {
-            if ((rc = launch_gemm_rows((const float *)u, K, n, (const float *)d.weight, K, K, Dm, (float *)out, Dm, true, stream, (const float *)d.bias))) return rc;
-            if (d.norm_out) hipLaunchKernelGGL(rows_rms_inplace_kernel<float>, dim3(nb), dim3(kThreads), 0, stream, (float *)out, n, Dm, eps, rr);
-        }
-        if (d.norm_out && (rc = check_launch("rows_rms_inplace_kernel"))) return rc;
+        if ((rc = launch_product_nt(d.dtype, u, K, n, d.weight, K, K, Dm, out, Dm, bf, d.bias, false, stream))) return rc;
+        // bf16: the row IS the bf16 tensor the reference's CastedLinear returns (train_gpt.py:185-186); norm() upcasts it (172-173)
+        if (d.norm_out && (rc = launch_rows_finish(out, n, Dm, 1, eps, rr, d.dtype, stream))) return rc;
     }
     return MOT_OK;
 }

@@ -292,7 +292,7 @@ static int token_head_run(const MotTokenHeadDesc &d, const TokGeom &g, const Tok
     for (int64_t r0 = 0; r0 < g.rows; r0 += g.chunk) {
         const int64_t n = g.rows - r0 < g.chunk ? g.rows - r0 : g.chunk;
         const T *x = X + r0 * g.K;
-        if ((rc = head_logits<T>(x, W, n, g.K, g.V, S, BF, stream))) return rc;   // s = x W^T for the chunk's rows, in T
+        if ((rc = launch_product_nt(head_dtype<T>, x, g.K, n, W, g.K, g.K, g.V, S, g.V, BF, nullptr, false, stream))) return rc;   // s = x W^T for the chunk's rows, in T
         float *stats = d.row_stats ? d.row_stats + r0 : nullptr;
         if (grad)
             rc = launch_rows<T, CAP, true>(S, g, x, d.targets + r0, n, inv_n, term + r0, stats, d.status, stream);
@@ -300,10 +300,10 @@ static int token_head_run(const MotTokenHeadDesc &d, const TokGeom &g, const Tok
             rc = launch_rows<T, CAP, false>(S, g, x, d.targets + r0, n, inv_n, term + r0, stats, d.status, stream);
         if (rc) return rc;
         if (d.dx) {   // u = G W, then the row chain of the plain norm (L = 0)
-            if ((rc = head_gw<T>(S, BF ? WT : W, n, g.V, g.K, u, stream))) return rc;
+            if ((rc = launch_product_nn(head_dtype<T>, S, g.V, n, BF ? WT : W, BF ? g.V : g.K, g.V, g.K, u, g.K, stream))) return rc;
             if ((rc = launch_head_chain<T>(x, u, g.K, n, 0, g.norm_in, g.eps, (T *)d.dx + r0 * g.K, stream))) return rc;
         }
-        if (d.dW && (rc = head_dw<T>(S, x, n, g.V, g.K, d.dW, stream))) return rc;   // dW += G^T x
+        if (d.dW && (rc = launch_product_tn(head_dtype<T>, S, g.V, g.V, x, g.K, g.K, n, d.dW, g.K, stream))) return rc;   // dW += G^T x
     }
     return launch_head_loss(term, g.rows, (double *)(ws + w.part), 1.0 / (double)g.rows, d.loss, stream);
 }

@@ -5,88 +5,21 @@
 //   ids        given, or made once for all slots by the index kernels (mot_index.hip);
 //   forward    bf16 at the gather-GEMM's shapes: ONE launch of the concat + linear gather-GEMM over a (token tile, slot) grid
 //              (mot_concat16.hip: u is never built, W is read in place, the norm is its epilogue); everything else per slot and
-//              slab: the concat operand (mot_embed.hip), the matrix-product launchers, and the row pass below;
-//   backward   per slot over one workspace: dy from the saved output and row factors (below), du = dy W and dW += dy^T u on the
-//              launchers with u gathered again slab by slab, the byte part of du through the LDS fixed-point sums of the byte
+//              slab: the concat operand (mot_embed.hip), the product (launch_product_nt), and the row pass of mot_lincore.hip;
+//   backward   per slot over one workspace: dy from the saved output and row factors (mot_lincore.hip), du = dy W and dW += dy^T u
+//              (launch_product_nn / _tn) with u gathered again slab by slab, the byte part of du through the LDS fixed-point sums of the byte
 //              value embeddings (mot_bytecat.hip), the token part through the order, canon, slices and rows kernels of the token
 //              value embeddings (mot_values.hip) from fp32 rows: every token-table gradient is written once in the tables' dtype.
 #include <float.h>
 
+#include "mot_lincore.hpp"
 #include "mot_mix.hpp"
 
 namespace mot {
 
 constexpr int64_t kVmSlab = 16384;   // rows of u (and of dy, du's byte part) per slab: 64 MiB of bf16 at K 2048
-constexpr int kVmMaxDim = 2048;
+constexpr int kVmMaxDim = kRowMaxDim;   // the row passes keep a row of out_dim columns in registers (mot_lincore.hip)
 constexpr int kVmSlots = MOT_VALUE_MIX_MAX_SLOTS;
-
-// ------------------------------------------------------------------------------------------ kernels
-// The forward's last pass, in place on the product rows y = W u (one wave per token, a lane owns 16-byte chunks lane, lane + 64,
-// ...): r = rsqrt(mean(y^2) + eps), out = r y, r kept for the backward.  bf16: y arrives rounded by the product kernel and out is
-// rounded on store -- the roundings of the reference's bf16 run (F.linear, rms_norm's result).
-template <typename T>
-__global__ __launch_bounds__(kThreads) void valuemix_finish_kernel(T *__restrict__ out, int64_t n, int Do, float eps, float *__restrict__ row_rnorm) {
-    using vec_t = typename Elem<T>::vec;
-    constexpr int VEC = Elem<T>::kVec, NCH = kVmMaxDim / VEC / 64;
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
-    if (r >= n) return;
-    T *p = out + r * Do;
-    const int nv = Do / VEC;
-    vec_t y[NCH];
-    float ss = 0.f;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-        const int j = lane + 64 * i;
-        y[i] = (vec_t)(0.f);
-        if (j < nv) {
-            y[i] = Elem<T>::loadv(p + VEC * j);
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) ss += y[i][e] * y[i][e];
-        }
-    }
-    const float rs = rms_scale(wave_sum(ss), Do, eps);
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-        const int j = lane + 64 * i;
-        if (j < nv) Elem<T>::storev_nt(p + VEC * j, y[i] * rs);
-    }
-    if (row_rnorm && lane == 0) row_rnorm[r] = rs;
-}
-
-// Back through the norm from the saved output (dy_kernel's / dy16_kernel's arithmetic, mot_bwd_linear.hip):
-// dy = r (g - x mean(g x)), fp32 for fp32 tensors, bf16 for bf16 ones (the operand of the two bf16 products).
-template <typename T>
-__global__ __launch_bounds__(kThreads) void valuemix_dy_kernel(const T *__restrict__ g, const T *__restrict__ x, const float *__restrict__ rnorm, int64_t n,
-                                                               int Do, T *__restrict__ dy) {
-    using vec_t = typename Elem<T>::vec;
-    constexpr int VEC = Elem<T>::kVec, NCH = kVmMaxDim / VEC / 64;
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
-    if (r >= n) return;
-    const T *gr = g + r * Do, *xr = x + r * Do;
-    const int nv = Do / VEC;
-    vec_t gv[NCH], xv[NCH];
-    float m = 0.f;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-        const int j = lane + 64 * i;
-        gv[i] = (vec_t)(0.f); xv[i] = (vec_t)(0.f);
-        if (j < nv) {
-            gv[i] = Elem<T>::loadv(gr + VEC * j);
-            xv[i] = Elem<T>::loadv(xr + VEC * j);
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) m += gv[i][e] * xv[i][e];
-        }
-    }
-    m = wave_sum(m) / (float)Do;
-    const float ry = rnorm[r];
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-        const int j = lane + 64 * i;
-        if (j < nv) Elem<T>::storev_nt(dy + r * Do + VEC * j, (gv[i] - xv[i] * m) * ry);
-    }
-}
 
 // ------------------------------------------------------------------------------------------ validation (no HIP call)
 
@@ -233,15 +166,9 @@ int launch_value_mix_fwd(const MotValueMixDesc &d, hipStream_t stream) {
             if ((rc = launch_concat_rows(d.tokens + r0, ids + r0 * bpt, n, s.tok_table, d.tok_rows, Dt, s.byte_table, d.byte_rows, Db, bpt, 0, nullptr, eps, u,
                                          K, 0, Dt, d.status, d.dtype, stream))) return rc;
             char *out = (char *)s.out + (size_t)r0 * Do * esz;
-            if (bf) rc = launch_gemm_rows_bf16(u, K, n, s.weight, K, K, Do, out, Do, true, nullptr, stream);
-            else rc = launch_gemm_rows((const float *)u, K, n, (const float *)s.weight, K, K, Do, (float *)out, Do, true, stream);
-            if (rc) return rc;
-            if (!d.norm_out) continue;
-            float *rr = s.out_row_rnorm ? s.out_row_rnorm + r0 : nullptr;
-            const unsigned nb = (unsigned)((n + kWaves - 1) / kWaves);
-            if (bf) hipLaunchKernelGGL(valuemix_finish_kernel<__bf16>, dim3(nb), dim3(kThreads), 0, stream, (__bf16 *)out, n, Do, eps, rr);
-            else hipLaunchKernelGGL(valuemix_finish_kernel<float>, dim3(nb), dim3(kThreads), 0, stream, (float *)out, n, Do, eps, rr);
-            if ((rc = check_launch("valuemix_finish_kernel"))) return rc;
+            if ((rc = launch_product_nt(d.dtype, u, K, n, s.weight, K, K, Do, out, Do, bf, nullptr, false, stream))) return rc;
+            // bf16: y arrives rounded by the product and r y is rounded on store -- the roundings of the reference's bf16 run
+            if (d.norm_out && (rc = launch_rows_finish(out, n, Do, 1, eps, s.out_row_rnorm ? s.out_row_rnorm + r0 : nullptr, d.dtype, stream))) return rc;
         }
     }
     return MOT_OK;
@@ -265,37 +192,27 @@ int launch_value_mix_bwd(const MotValueMixDesc &d, const MotValueMixGrads &gr, h
         const MotValueMixSlot &s = d.slot[j];
         const MotValueMixGradSlot &q = gr.slot[j];
         if (!q.grad_out) continue;
-        // du[n][k] = sum_m dy[n][m] W[m][k]: for the bf16 launcher W^T is the [K, out_dim] "weight"
+        // du[n][k] = sum_m dy[n][m] W[m][k]: fp32 reads W [out_dim, K] itself, the bf16 launcher its k-major copy W^T [K, out_dim];
+        // Wb is the byte part of either, columns [Dt, K) of W or rows [Dt, K) of W^T
         if (bf && (rc = launch_transpose_bf16(s.weight, Do, K, wt16, stream))) return rc;
+        const void *Wd = bf ? (const void *)wt16 : s.weight, *Wb = bf ? (const void *)(wt16 + (size_t)Dt * Do) : (const float *)s.weight + Dt;
+        const int ldw = bf ? Do : K;
         for (int64_t r0 = 0; r0 < N; r0 += L.slab) {
             const int64_t n = N - r0 < L.slab ? N - r0 : L.slab;
-            const unsigned nb = (unsigned)((n + kWaves - 1) / kWaves);
             const char *g = (const char *)q.grad_out + (size_t)r0 * Do * esz;
             const int64_t *ids = d.ids + r0 * bpt;
             // 1. u again; 2. dy; 3. du = dy W, token part for the whole batch, byte part for the slab; 4. d_weight += dy^T u
             if ((rc = launch_concat_rows(d.tokens + r0, ids, n, s.tok_table, d.tok_rows, Dt, s.byte_table, d.byte_rows, Db, bpt, 0, nullptr, eps, u, K, 0, Dt,
                                          d.status, d.dtype, stream))) return rc;
             const char *dy = g;   // without the norm dy is g
-            if (d.norm_out) {
+            if (d.norm_out) {   // bf16 tensors: dy in bf16, the operand of the two bf16 products
                 const char *x = (const char *)s.out + (size_t)r0 * Do * esz;
-                if (bf) hipLaunchKernelGGL(valuemix_dy_kernel<__bf16>, dim3(nb), dim3(kThreads), 0, stream, (const __bf16 *)g, (const __bf16 *)x, s.out_row_rnorm + r0,
-                                           n, Do, (__bf16 *)dyws);
-                else hipLaunchKernelGGL(valuemix_dy_kernel<float>, dim3(nb), dim3(kThreads), 0, stream, (const float *)g, (const float *)x, s.out_row_rnorm + r0, n,
-                                        Do, (float *)dyws);
-                if ((rc = check_launch("valuemix_dy_kernel"))) return rc;
+                if ((rc = launch_rows_norm_bwd(g, x, s.out_row_rnorm + r0, n, Do, 1, dyws, Do, nullptr, 0, d.dtype, stream))) return rc;
                 dy = dyws;
             }
-            float *dut_r = dut + r0 * Dt;
-            if (bf) {
-                if ((rc = launch_gemm_rows_bf16(dy, Do, n, wt16, Do, Do, Dt, dut_r, Dt, false, nullptr, stream))) return rc;
-                if ((rc = launch_gemm_rows_bf16(dy, Do, n, wt16 + (size_t)Dt * Do, Do, Do, Kb, dub, Kb, false, nullptr, stream))) return rc;
-                if ((rc = launch_gemm_tn_bf16((const __bf16 *)dy, Do, Do, (const __bf16 *)u, K, K, n, (float *)q.d_weight, K, stream))) return rc;
-            } else {
-                const float *W = (const float *)s.weight;
-                if ((rc = launch_gemm_rows((const float *)dy, Do, n, W, K, Do, Dt, dut_r, Dt, false, stream))) return rc;
-                if ((rc = launch_gemm_rows((const float *)dy, Do, n, W + Dt, K, Do, Kb, dub, Kb, false, stream))) return rc;
-                if ((rc = launch_gemm_tn((const float *)dy, Do, Do, (const float *)u, K, K, n, (float *)q.d_weight, K, stream))) return rc;
-            }
+            if ((rc = launch_product_nn(d.dtype, dy, Do, n, Wd, ldw, Do, Dt, dut + r0 * Dt, Dt, stream))) return rc;
+            if ((rc = launch_product_nn(d.dtype, dy, Do, n, Wb, ldw, Do, Kb, dub, Kb, stream))) return rc;
+            if ((rc = launch_product_tn(d.dtype, dy, Do, Do, u, K, K, n, (float *)q.d_weight, K, stream))) return rc;
             // 5. d_byte += the byte part, as the gradient of an un-normed fp32 byte_cat over this slab
             MotByteCatDesc c{};
             c.struct_size = sizeof(MotByteCatDesc); c.dtype = MOT_F32; c.n_rows = 1; c.tokens_per_row = n; c.bpt = bpt; c.byte_dim = Db; c.n_out = 1;
