@@ -49,7 +49,7 @@ typedef enum MotStatus {
  * never fault -- the host shim turns a non-zero word into the reference's IndexError. */
 #define MOT_STATUS_TOKEN_OOR 1u /* token id outside [0, tok_rows) / [0, ttb_rows) */
 #define MOT_STATUS_BYTE_OOR 2u  /* byte id outside [0, byte_rows)                 */
-#define MOT_STATUS_TARGET_OOR 4u /* target outside [0, vocab) (mot_byte_head_*, mot_token_head_fwd) */
+#define MOT_STATUS_TARGET_OOR 4u /* target outside [0, vocab) (mot_byte_head_*, mot_token_head_*) */
 
 typedef enum MotPullDir {
     MOT_PULL_NONE = 0,
@@ -584,6 +584,45 @@ typedef struct MotTokenHeadDesc {
 size_t mot_token_head_desc_size(void);
 size_t mot_token_head_workspace_bytes(const MotTokenHeadDesc *desc /* host */);
 int mot_token_head_fwd(const MotTokenHeadDesc *desc /* host */, mot_stream_t stream);
+
+/*
+ * Evaluation form of the two output heads: the pass of the loss call without gradients over the same chunks, which also writes
+ * what it knows about every row.  A row is a token for the token-level head and a byte position for the byte head (n_tokens * bpt
+ * of them, token-major, as `targets` are; in copy mode the head still computes one row per token and writes it out per position).
+ * `desc` is the descriptor of the loss call: desc->loss receives the same fixed-order sum with the same bits as mot_token_head_fwd
+ * with dx = dW = NULL / mot_byte_head_fwd on the same inputs.  No gradients are formed and nothing of rows x vocab exists.
+ *   row_loss[r] = lse(z_r) - z_r[y_r] in fp32: the term the loss sums.
+ *   pred[r]     = the class with the largest logit, taken on the chunk's stored product s = x W^T (fp32; bf16 in the token-level
+ *                 head's MOT_BF16 mode, compared as stored) in front of the row factor c_r > 0 and the strictly increasing softcap:
+ *                 the argmax of z_r, an exact function of what the product stored.  Ties go to the lowest class index; the padded
+ *                 classes (50 257 .. 50 303, 458 .. 511) are ordinary classes, as in the loss.
+ *   rank[r]     = the number of classes whose stored s is strictly greater than the target's: 0 = the target is (one of) the
+ *                 largest; rank < k is top-k accuracy, 1 / (1 + rank) the reciprocal rank.
+ *   counts      = int64 [n_rows_counted, n_top1] on the device: the rows with a target inside [0, vocab), and those of them with
+ *                 pred == target.  mot_byte_head_eval writes a third: n_tokens_all_correct, the tokens whose bpt byte predictions
+ *                 all equal their targets.  Integer sums: the same on every run.  Never read on the host: the call is capturable.
+ * A target outside [0, vocab) is handled as in the loss call (its term leaves the sum, MOT_STATUS_TARGET_OOR is raised), and here
+ * row_loss = 0, rank = -1, pred is still written, the row is left out of both counts and its token cannot be all-correct.
+ * Each output pointer may be NULL, except that `counts` is closed from `pred` and the targets, so counts needs pred.  Every output
+ * is written once per row with plain stores.  row_loss, pred and rank must be 4-byte aligned, counts 8-byte aligned.
+ * Workspace: that of the loss call without gradients, i.e. mot_token_head_workspace_bytes(desc) with desc->dx == NULL (the query
+ * reads no other pointer) and mot_byte_head_workspace_bytes(desc).  desc->row_stats is optional in both calls.
+ * Checked before any HIP call, with a message that starts with the function's name: a null descriptor or out struct, a wrong
+ * struct_size, reserved != 0, a misaligned pointer, counts without pred, dx or dW set in the token descriptor (the call forms no
+ * gradients) -> MOT_EINVAL; every shape and dtype refusal of the loss call, with its codes.
+ */
+typedef struct MotHeadEvalOut {
+    uint32_t struct_size; /* sizeof(MotHeadEvalOut) */
+    uint32_t reserved;    /* 0 */
+    float *row_loss;      /* optional [rows] fp32 */
+    int32_t *pred;        /* optional [rows] */
+    int32_t *rank;        /* optional [rows] */
+    int64_t *counts;      /* optional [2] (token-level head) or [3] (byte head); needs pred */
+} MotHeadEvalOut;
+
+size_t mot_head_eval_out_size(void);
+int mot_token_head_eval(const MotTokenHeadDesc *desc /* host */, const MotHeadEvalOut *out /* host */, mot_stream_t stream);
+int mot_byte_head_eval(const MotByteHeadDesc *desc /* host */, const MotHeadEvalOut *out /* host */, mot_stream_t stream);
 
 /*
  * Byte self-attention in front of the concat mixin, forward: replaces ByteSelfAttn.forward with use_byte_self_attn on

@@ -5,6 +5,7 @@ Python layer mirrors the reference's interfaces for this path and nothing else:
 
   data_creation   make_embedding / tokens_to_bytes / pull_from_left / pull_from_right / create_batch
   functional      tensor-level wrappers (embed_mix = the fused gather + mix forward; byte_head_loss = the mixout byte head; token_head_loss = the token-level head;
+                  token_head_eval / byte_head_eval = the heads' evaluation form: per-row loss, top-1 prediction, target rank, counts;
                   byte_self_attn = the sliding-window byte self-attention layer of the concat mixin;
                   byte_fc_mix = the linear-on-bytes mixin of run 71051; byte_cat = the bytes-only front-end and byte value embeddings
                   of runs 2, 4, 5, 6, 8; value_embeds = the token value embeddings of train_gpt.py:566/600 and the *_toks-valemb runs;
@@ -22,9 +23,9 @@ from . import _capi
 from . import data_creation, functional, grad_sync, loader, modules
 from ._capi import build_info, check_status, set_debug_ids
 from .modules import ByteFcFrontEnd, BytesFrontEnd, ConcatFrontEnd, MotValueEmbeds, SplitX0FrontEnd, ValueEmbeds
-from .functional import byte_cat, byte_fc_mix, byte_head_loss, byte_self_attn, create_batch, embed_mix, embed_mix_plan, gather_rows, pull_bytes, split_x0, token_head_loss, tokens_to_bytes, value_embeds, value_mix
+from .functional import HeadEval, byte_cat, byte_fc_mix, byte_head_eval, byte_head_loss, byte_self_attn, create_batch, embed_mix, embed_mix_plan, gather_rows, pull_bytes, split_x0, token_head_eval, token_head_loss, tokens_to_bytes, value_embeds, value_mix
 
 __all__ = [
     "build_info", "check_status", "set_debug_ids", "ByteFcFrontEnd", "BytesFrontEnd", "ConcatFrontEnd", "MotValueEmbeds", "SplitX0FrontEnd", "ValueEmbeds", "data_creation", "functional", "grad_sync", "loader", "modules",
-    "byte_cat", "byte_fc_mix", "byte_head_loss", "byte_self_attn", "create_batch", "embed_mix", "embed_mix_plan", "gather_rows", "pull_bytes", "split_x0", "token_head_loss", "tokens_to_bytes", "value_embeds", "value_mix",
+    "HeadEval", "byte_cat", "byte_fc_mix", "byte_head_eval", "byte_head_loss", "byte_self_attn", "create_batch", "embed_mix", "embed_mix_plan", "gather_rows", "pull_bytes", "split_x0", "token_head_eval", "token_head_loss", "tokens_to_bytes", "value_embeds", "value_mix",
 ]

@@ -58,6 +58,7 @@ EXPORTS = (
     "mot_char_swa_desc_size", "mot_char_swa_workspace_bytes", "mot_char_swa_fwd",
     "mot_byte_head_desc_size", "mot_byte_head_workspace_bytes", "mot_byte_head_fwd", "mot_byte_head_bwd",
     "mot_token_head_desc_size", "mot_token_head_workspace_bytes", "mot_token_head_fwd",
+    "mot_head_eval_out_size", "mot_token_head_eval", "mot_byte_head_eval",
     "mot_byte_self_attn_desc_size", "mot_byte_self_attn_saved_bytes", "mot_byte_self_attn_workspace_bytes",
     "mot_byte_self_attn_fwd", "mot_byte_self_attn_bwd",
     "mot_byte_fc_mix_desc_size", "mot_byte_fc_mix_workspace_bytes", "mot_byte_fc_mix_bwd_workspace_bytes",
@@ -166,6 +167,14 @@ class MotTokenHeadDesc(C.Structure):
         ("model_dim", C.c_int32), ("vocab", C.c_int32), ("eps", C.c_float), ("chunk_rows", C.c_int32),
         ("x", C.c_void_p), ("weight", C.c_void_p), ("targets", C.c_void_p), ("loss", C.c_void_p), ("row_stats", C.c_void_p),
         ("status", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("dx", C.c_void_p), ("dW", C.c_void_p),
+    ]
+
+
+class MotHeadEvalOut(C.Structure):
+    """Mirror of struct MotHeadEvalOut (include/mot.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("row_loss", C.c_void_p), ("pred", C.c_void_p), ("rank", C.c_void_p),
+        ("counts", C.c_void_p),
     ]
 
 
@@ -360,6 +369,11 @@ def _load() -> C.CDLL:
     lib.mot_token_head_workspace_bytes.argtypes = [C.POINTER(MotTokenHeadDesc)]
     lib.mot_token_head_fwd.argtypes = [C.POINTER(MotTokenHeadDesc), vp]
     lib.mot_token_head_fwd.restype = C.c_int
+    lib.mot_head_eval_out_size.restype = C.c_size_t
+    lib.mot_token_head_eval.argtypes = [C.POINTER(MotTokenHeadDesc), C.POINTER(MotHeadEvalOut), vp]
+    lib.mot_token_head_eval.restype = C.c_int
+    lib.mot_byte_head_eval.argtypes = [C.POINTER(MotByteHeadDesc), C.POINTER(MotHeadEvalOut), vp]
+    lib.mot_byte_head_eval.restype = C.c_int
     lib.mot_byte_self_attn_desc_size.restype = C.c_size_t
     for name in ("mot_byte_self_attn_saved_bytes", "mot_byte_self_attn_workspace_bytes"):
         getattr(lib, name).restype = C.c_size_t
@@ -425,6 +439,8 @@ def _load() -> C.CDLL:
         raise ImportError("MotByteHeadDesc layout mismatch between include/mot.h and _capi.py")
     if lib.mot_token_head_desc_size() != C.sizeof(MotTokenHeadDesc):
         raise ImportError("MotTokenHeadDesc layout mismatch between include/mot.h and _capi.py")
+    if lib.mot_head_eval_out_size() != C.sizeof(MotHeadEvalOut):
+        raise ImportError("MotHeadEvalOut layout mismatch between include/mot.h and _capi.py")
     if lib.mot_byte_self_attn_desc_size() != C.sizeof(MotByteSelfAttnDesc):
         raise ImportError("MotByteSelfAttnDesc layout mismatch between include/mot.h and _capi.py")
     if lib.mot_byte_fc_mix_desc_size() != C.sizeof(MotByteFcMixDesc):

@@ -369,6 +369,10 @@ int mot_byte_head_bwd(const MotByteHeadDesc *desc, const float *grad_loss, void 
     return launch_byte_head_bwd(*desc, grad_loss, dx, dW, (hipStream_t)stream);
 }
 
+int mot_byte_head_eval(const MotByteHeadDesc *desc, const MotHeadEvalOut *out, mot_stream_t stream) {
+    return launch_byte_head_eval(desc, out, (hipStream_t)stream);
+}
+
 size_t mot_token_head_desc_size(void) { return sizeof(MotTokenHeadDesc); }
 
 size_t mot_token_head_workspace_bytes(const MotTokenHeadDesc *desc) {
@@ -380,6 +384,12 @@ int mot_token_head_fwd(const MotTokenHeadDesc *desc, mot_stream_t stream) {
     int rc = token_head_check(desc);
     if (rc) return rc;
     return launch_token_head_fwd(*desc, (hipStream_t)stream);
+}
+
+size_t mot_head_eval_out_size(void) { return sizeof(MotHeadEvalOut); }
+
+int mot_token_head_eval(const MotTokenHeadDesc *desc, const MotHeadEvalOut *out, mot_stream_t stream) {
+    return launch_token_head_eval(desc, out, (hipStream_t)stream);
 }
 
 size_t mot_byte_self_attn_desc_size(void) { return sizeof(MotByteSelfAttnDesc); }

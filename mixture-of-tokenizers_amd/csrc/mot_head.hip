@@ -13,6 +13,8 @@
 // G_r = c_r dL/dl_r (overwriting the logits in fp32, a bf16 copy in bf16), then u = G W (= c dL/dnorm(h)), the row chain
 // dx_r = u_r + (dc/dm0) (2 / K) (x_r . u_r / c_r) x_r, and dW += G^T x.  Every buffer of the chunk is bounded by kChunkBytes,
 // so no tensor of M x 512 exists in split mode.  The loss is a fixed-order double sum of per-row terms: the same bits every run.
+// mot_byte_head_eval is the forward whose row pass (head_fwd_rows<T, true>) also writes, per byte position, the loss term, the class
+// of the largest stored logit and the number of stored logits above the target's (include/mot.h).
 // This unit holds the two 512-wide row passes, head_fwd_rows and head_grad_rows, the checks and the carve; row_scale, the products,
 // the chunk rule, the row chain and the loss's sum are the heads' shared ones (mot_headcore.hpp).
 #include "mot_headcore.hpp"
@@ -37,21 +39,26 @@ __device__ __forceinline__ float row_sumsq(const T *x, int K, int lane) {
     return wave_sum(ss);
 }
 
-// one wave per row: c, z, lse and the row's loss term; lane j holds classes lane + 64 i
-template <typename T>
+// one wave per row: c, z, lse and the row's loss term; lane j holds classes lane + 64 i.
+// EVAL is the evaluation variant (lse and cst optional): it also writes, for each of the row's tpr targets (lane k keeps those of
+// target k: tpr <= MOT_MAX_BPT = 64), lse - z[y], the class of the row's largest stored logit and the number of stored logits
+// above the target's into `ev` at byte position r * tpr + k.
+template <typename T, bool EVAL>
 __global__ __launch_bounds__(kThreads) void head_fwd_rows(const float *__restrict__ S, const T *__restrict__ x, int K, const int64_t *__restrict__ tgt,
                                                           int tpr, int64_t rows, int L, float eps, float *__restrict__ lse, float *__restrict__ cst,
-                                                          float *__restrict__ term, uint32_t *status) {
+                                                          float *__restrict__ term, uint32_t *status, HeadEvalRows ev) {
     const int lane = threadIdx.x & 63;
     const int64_t r = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
     if (r >= rows) return;
     float c, dc;
     row_scale(row_sumsq(x + r * K, K, lane) / (float)K, L, eps, c, dc);
     const float *s = S + r * kV;
-    float z[8], se = 0.f;
+    float z[8], sv[EVAL ? 8 : 1], se = 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-        z[i] = kCap * sigm(c * s[lane + 64 * i]);
+        const float si = s[lane + 64 * i];
+        if (EVAL) sv[i] = si;
+        z[i] = kCap * sigm(c * si);
         se += __expf(z[i] - kCap);
     }
     const float l = kCap + __logf(wave_sum(se));
@@ -66,10 +73,41 @@ __global__ __launch_bounds__(kThreads) void head_fwd_rows(const float *__restric
     }
     tz = wave_sum(tz);
     if (lane == 0) {
-        lse[r] = l;
-        cst[r] = c;
+        if (!EVAL || lse) lse[r] = l;
+        if (!EVAL || cst) cst[r] = c;
         term[r] = (float)nv * l - tz;
         if (nv < tpr && status) atomicOr(status, (uint32_t)MOT_STATUS_TARGET_OOR);
+    }
+    if (!EVAL) return;
+    float best = -INFINITY;
+    int best_cls = 0x7fffffff;
+#pragma unroll
+    for (int i = 0; i < 8; ++i)   // ascending classes: `>` keeps the lowest of equal logits
+        if (sv[i] > best) {
+            best = sv[i];
+            best_cls = lane + 64 * i;
+        }
+    wave_argmax(best, best_cls);
+    float my_loss = 0.f;
+    int my_rank = -1;
+    for (int k = 0; k < tpr; ++k) {
+        const int64_t y = tgt[r * tpr + k];
+        if (y < 0 || y >= kV) continue;   // wave-uniform
+        const float sy = s[y];
+        int above = 0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) above += sv[i] > sy ? 1 : 0;
+        const float n_above = wave_sum((float)above);   // at most 512: exact in fp32
+        if (lane == k) {
+            my_loss = l - kCap * sigm(c * sy);
+            my_rank = (int)n_above;
+        }
+    }
+    if (lane < tpr) {
+        const int64_t at = r * tpr + lane;
+        if (ev.row_loss) ev.row_loss[at] = my_loss;
+        if (ev.pred) ev.pred[at] = best_cls;
+        if (ev.rank) ev.rank[at] = my_rank;
     }
 }
 
@@ -132,24 +170,24 @@ HeadWs head_ws(const HeadGeom &g) {
 
 }  // namespace
 
-static int byte_head_geom(const MotByteHeadDesc *d, HeadGeom *geom_out) {
-    if (!d) return set_error(MOT_EINVAL, "byte_head: null descriptor");
+static int byte_head_geom(const MotByteHeadDesc *d, HeadGeom *geom_out, const char *fn = "byte_head") {
+    if (!d) return set_error(MOT_EINVAL, "%s: null descriptor", fn);
     if (d->struct_size != sizeof(MotByteHeadDesc))
-        return set_error(MOT_EINVAL, "byte_head: struct_size %u != %zu (ABI mismatch)", d->struct_size, sizeof(MotByteHeadDesc));
+        return set_error(MOT_EINVAL, "%s: struct_size %u != %zu (ABI mismatch)", fn, d->struct_size, sizeof(MotByteHeadDesc));
     if (d->method != MOT_HEAD_COPY && d->method != MOT_HEAD_SPLIT)
-        return set_error(MOT_EUNSUPPORTED, "byte_head: method %d is not built (copy and split are)", d->method);
-    if (d->dtype != MOT_F32 && d->dtype != MOT_BF16) return set_error(MOT_EUNSUPPORTED, "byte_head: dtype %d is not built", d->dtype);
+        return set_error(MOT_EUNSUPPORTED, "%s: method %d is not built (copy and split are)", fn, d->method);
+    if (d->dtype != MOT_F32 && d->dtype != MOT_BF16) return set_error(MOT_EUNSUPPORTED, "%s: dtype %d is not built", fn, d->dtype);
     if (d->n_tokens < 0 || d->model_dim <= 0 || d->n_layer_out < 0 || d->n_layer_out > 64)
-        return set_error(MOT_ESHAPE, "byte_head: n_tokens %lld, model_dim %d, n_layer_out %d", (long long)d->n_tokens, d->model_dim, d->n_layer_out);
-    if (d->bpt < 1 || d->bpt > MOT_MAX_BPT) return set_error(MOT_ESHAPE, "byte_head: bpt %d outside [1, %d]", d->bpt, MOT_MAX_BPT);
-    if (d->vocab != kV) return set_error(MOT_EUNSUPPORTED, "byte_head: vocab %d: only the %d-row head is built", d->vocab, kV);
+        return set_error(MOT_ESHAPE, "%s: n_tokens %lld, model_dim %d, n_layer_out %d", fn, (long long)d->n_tokens, d->model_dim, d->n_layer_out);
+    if (d->bpt < 1 || d->bpt > MOT_MAX_BPT) return set_error(MOT_ESHAPE, "%s: bpt %d outside [1, %d]", fn, d->bpt, MOT_MAX_BPT);
+    if (d->vocab != kV) return set_error(MOT_EUNSUPPORTED, "%s: vocab %d: only the %d-row head is built", fn, d->vocab, kV);
     const bool split = d->method == MOT_HEAD_SPLIT;
     if (split && d->model_dim % d->bpt)
-        return set_error(MOT_ESHAPE, "byte_head: split needs model_dim %% bpt == 0 (train_gpt.py:503), got %d %% %d", d->model_dim, d->bpt);
+        return set_error(MOT_ESHAPE, "%s: split needs model_dim %% bpt == 0 (train_gpt.py:503), got %d %% %d", fn, d->model_dim, d->bpt);
     const int K = split ? d->model_dim / d->bpt : d->model_dim;
-    if (K % 16 || K > kMaxK) return set_error(MOT_EUNSUPPORTED, "byte_head: row width %d must be a multiple of 16 and at most %d", K, kMaxK);
+    if (K % 16 || K > kMaxK) return set_error(MOT_EUNSUPPORTED, "%s: row width %d must be a multiple of 16 and at most %d", fn, K, kMaxK);
     const int64_t M = d->n_tokens * (int64_t)d->bpt;
-    if (M > 0x7fffffffLL) return set_error(MOT_EUNSUPPORTED, "byte_head: n_tokens * bpt exceeds 2^31");
+    if (M > 0x7fffffffLL) return set_error(MOT_EUNSUPPORTED, "%s: n_tokens * bpt exceeds 2^31", fn);
     HeadGeom &g = *geom_out;
     g.rows = split ? M : d->n_tokens;
     g.K = K;
@@ -172,29 +210,39 @@ size_t byte_head_workspace_bytes(const MotByteHeadDesc &d) {
     return head_ws(g).total;
 }
 
-static int head_check_ptrs(const MotByteHeadDesc &d, const HeadGeom &g, size_t need) {
-    if (!d.x || !d.weight || !d.targets || !d.row_stats) return set_error(MOT_EINVAL, "byte_head: null x / weight / targets / row_stats");
+static int head_check_ptrs(const MotByteHeadDesc &d, const HeadGeom &g, size_t need, const char *fn = "byte_head", bool need_stats = true) {
+    if (!d.x || !d.weight || !d.targets || (need_stats && !d.row_stats))
+        return set_error(MOT_EINVAL, "%s: null x / weight / targets%s", fn, need_stats ? " / row_stats" : "");
     if (!d.workspace || d.workspace_bytes < need)
-        return set_error(MOT_EWORKSPACE, "byte_head: workspace %zu bytes < %zu", d.workspace ? d.workspace_bytes : (size_t)0, need);
-    if (((uintptr_t)d.x & 15) || ((uintptr_t)d.weight & 15)) return set_error(MOT_EUNSUPPORTED, "byte_head: x and weight must be 16-byte aligned");
+        return set_error(MOT_EWORKSPACE, "%s: workspace %zu bytes < %zu", fn, d.workspace ? d.workspace_bytes : (size_t)0, need);
+    if (((uintptr_t)d.x & 15) || ((uintptr_t)d.weight & 15)) return set_error(MOT_EUNSUPPORTED, "%s: x and weight must be 16-byte aligned", fn);
     return MOT_OK;
 }
 
+// `ev` set: the evaluation call: the row pass also writes ev's rows per byte position, and the counts are closed behind the loss
 template <typename T>
-static int byte_head_fwd_run(const MotByteHeadDesc &d, const HeadGeom &g, const HeadWs &w, hipStream_t stream) {
+static int byte_head_fwd_run(const MotByteHeadDesc &d, const HeadGeom &g, const HeadWs &w, const MotHeadEvalOut *ev, hipStream_t stream) {
     unsigned char *ws = (unsigned char *)d.workspace;
     float *term = (float *)(ws + w.term), *S = (float *)(ws + w.S);
-    float *lse = d.row_stats, *cst = d.row_stats + g.rows;
+    float *lse = d.row_stats, *cst = d.row_stats ? d.row_stats + g.rows : nullptr;
+    const HeadEvalRows ev_rows = ev ? HeadEvalRows{ev->row_loss, ev->pred, ev->rank} : HeadEvalRows{};
     int rc;
     for (int64_t r0 = 0; r0 < g.rows; r0 += g.chunk) {
         const int64_t n = g.rows - r0 < g.chunk ? g.rows - r0 : g.chunk;
         const T *x = (const T *)d.x + r0 * g.K;
         if ((rc = launch_product_nt(head_dtype<T>, x, g.K, n, d.weight, g.K, g.K, kV, S, kV, false, nullptr, false, stream))) return rc;
-        hipLaunchKernelGGL(head_fwd_rows<T>, dim3((unsigned)((n + kWaves - 1) / kWaves)), dim3(kThreads), 0, stream, S, x, g.K, d.targets + r0 * g.tpr, g.tpr, n,
-                           d.n_layer_out, g.eps, lse + r0, cst + r0, term + r0, d.status);
+        const dim3 grid((unsigned)((n + kWaves - 1) / kWaves));
+        if (ev)
+            hipLaunchKernelGGL((head_fwd_rows<T, true>), grid, dim3(kThreads), 0, stream, S, x, g.K, d.targets + r0 * g.tpr, g.tpr, n, d.n_layer_out, g.eps,
+                               lse ? lse + r0 : nullptr, cst ? cst + r0 : nullptr, term + r0, d.status, ev_rows.at(r0 * g.tpr));
+        else
+            hipLaunchKernelGGL((head_fwd_rows<T, false>), grid, dim3(kThreads), 0, stream, S, x, g.K, d.targets + r0 * g.tpr, g.tpr, n, d.n_layer_out, g.eps,
+                               lse + r0, cst + r0, term + r0, d.status, HeadEvalRows{});
         if ((rc = check_launch("head_fwd_rows"))) return rc;
     }
-    return launch_head_loss(term, g.rows, (double *)(ws + w.part), 1.0 / (double)g.M, d.loss, stream);
+    if ((rc = launch_head_loss(term, g.rows, (double *)(ws + w.part), 1.0 / (double)g.M, d.loss, stream))) return rc;
+    if (ev && ev->counts) return launch_head_eval_counts(ev->pred, d.targets, g.M / d.bpt, d.bpt, kV, ws + w.part, ev->counts, 3, stream);
+    return MOT_OK;
 }
 
 int launch_byte_head_fwd(const MotByteHeadDesc &d, hipStream_t stream) {
@@ -205,7 +253,19 @@ int launch_byte_head_fwd(const MotByteHeadDesc &d, hipStream_t stream) {
     if (g.rows == 0) return set_error(MOT_ESHAPE, "byte_head: no targets (the mean over zero targets is undefined)");
     const HeadWs w = head_ws(g);
     if ((rc = head_check_ptrs(d, g, w.total))) return rc;
-    return g.bf16 ? byte_head_fwd_run<__bf16>(d, g, w, stream) : byte_head_fwd_run<float>(d, g, w, stream);
+    return g.bf16 ? byte_head_fwd_run<__bf16>(d, g, w, nullptr, stream) : byte_head_fwd_run<float>(d, g, w, nullptr, stream);
+}
+
+int launch_byte_head_eval(const MotByteHeadDesc *d, const MotHeadEvalOut *out, hipStream_t stream) {
+    static const char fn[] = "mot_byte_head_eval";
+    HeadGeom g;
+    int rc = byte_head_geom(d, &g, fn);
+    if (rc || (rc = head_eval_check(fn, out))) return rc;
+    if (!d->loss) return set_error(MOT_EINVAL, "%s: null loss", fn);
+    if (g.rows == 0) return set_error(MOT_ESHAPE, "%s: no targets (the mean over zero targets is undefined)", fn);
+    const HeadWs w = head_ws(g);
+    if ((rc = head_check_ptrs(*d, g, w.total, fn, false))) return rc;
+    return g.bf16 ? byte_head_fwd_run<__bf16>(*d, g, w, out, stream) : byte_head_fwd_run<float>(*d, g, w, out, stream);
 }
 
 // In fp32 G overwrites the chunk's logits S; in bf16 it is the bf16 copy G16, and u = G W reads the k-major copy WT of W.

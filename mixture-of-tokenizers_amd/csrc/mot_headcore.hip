@@ -1,5 +1,6 @@
 // mot_headcore.hip -- the kernels the output heads share (mot_headcore.hpp), each with its launcher: head_chain_rows, the
-// wave-per-row chain that closes dx behind u = G W, and head_loss_parts / head_loss_final, the loss as a sum of per-row terms.
+// wave-per-row chain that closes dx behind u = G W, head_loss_parts / head_loss_final, the loss as a sum of per-row terms, and
+// head_count_parts / head_count_final, the counts of the evaluation calls, with the check of their out struct.
 #include "mot_headcore.hpp"
 
 namespace mot {
@@ -47,7 +48,8 @@ static int loss_parts(int64_t rows) {
     return (int)(p < 1 ? 1 : p > kLossParts ? kLossParts : p);
 }
 
-static __device__ __forceinline__ double block_sum(double a, double *sh) {
+template <typename A>
+static __device__ __forceinline__ A block_sum(A a, A *sh) {
     sh[threadIdx.x] = a;
     __syncthreads();
     for (int o = kThreads / 2; o > 0; o >>= 1) {
@@ -88,6 +90,68 @@ int launch_head_loss(const float *term, int64_t rows, double *part, double inv_m
     if (int rc = check_launch("head_loss_parts")) return rc;
     hipLaunchKernelGGL(head_loss_final, dim3(1), dim3(kThreads), 0, stream, part, parts, inv_m, loss);
     return check_launch("head_loss_final");
+}
+
+// The counts of an evaluation call, closed from what its row passes wrote: a row counts when its target lies in [0, vocab), it is a
+// hit when pred equals that target, and a group (`per` consecutive rows: the byte positions of a token; 1 for the token-level head)
+// is all-correct when every row of it is a hit.  Integer sums, laid out as the loss's: workgroup p sums its fixed range of groups
+// into part[3 p ..], one workgroup then sums the parts in order.
+constexpr int kCountParts = kLossParts / 3;
+
+__global__ __launch_bounds__(kThreads) void head_count_parts(const int32_t *__restrict__ pred, const int64_t *__restrict__ tgt, int64_t groups, int per,
+                                                             int vocab, long long *__restrict__ part) {
+    __shared__ long long sh[kThreads];
+    const int64_t span = (groups + gridDim.x - 1) / gridDim.x, lo = (int64_t)blockIdx.x * span, hi = lo + span < groups ? lo + span : groups;
+    long long n_in = 0, n_hit = 0, n_all = 0;
+    for (int64_t g = lo + threadIdx.x; g < hi; g += kThreads) {
+        bool all = true;
+        for (int k = 0; k < per; ++k) {
+            const int64_t y = tgt[g * per + k];
+            const bool in = y >= 0 && y < vocab, hit = in && (int64_t)pred[g * per + k] == y;
+            n_in += in;
+            n_hit += hit;
+            all = all && hit;
+        }
+        n_all += all;
+    }
+    n_in = block_sum(n_in, sh);
+    __syncthreads();   // sh is read by every thread before the next sum overwrites it
+    n_hit = block_sum(n_hit, sh);
+    __syncthreads();
+    n_all = block_sum(n_all, sh);
+    if (threadIdx.x == 0) {
+        part[3 * blockIdx.x] = n_in;
+        part[3 * blockIdx.x + 1] = n_hit;
+        part[3 * blockIdx.x + 2] = n_all;
+    }
+}
+
+__global__ __launch_bounds__(64) void head_count_final(const long long *__restrict__ part, int parts, int64_t *__restrict__ counts, int n_counts) {
+    const int j = threadIdx.x;
+    if (j >= n_counts) return;
+    long long a = 0;
+    for (int p = 0; p < parts; ++p) a += part[3 * p + j];
+    counts[j] = a;
+}
+
+int launch_head_eval_counts(const int32_t *pred, const int64_t *tgt, int64_t groups, int per, int vocab, void *part, int64_t *counts, int n_counts,
+                            hipStream_t stream) {
+    const int parts = loss_parts(groups) < kCountParts ? loss_parts(groups) : kCountParts;
+    hipLaunchKernelGGL(head_count_parts, dim3(parts), dim3(kThreads), 0, stream, pred, tgt, groups, per, vocab, (long long *)part);
+    if (int rc = check_launch("head_count_parts")) return rc;
+    hipLaunchKernelGGL(head_count_final, dim3(1), dim3(64), 0, stream, (const long long *)part, parts, counts, n_counts);
+    return check_launch("head_count_final");
+}
+
+int head_eval_check(const char *fn, const MotHeadEvalOut *o) {
+    if (!o) return set_error(MOT_EINVAL, "%s: null out struct", fn);
+    if (o->struct_size != sizeof(MotHeadEvalOut))
+        return set_error(MOT_EINVAL, "%s: out struct_size %u != %zu (ABI mismatch)", fn, o->struct_size, sizeof(MotHeadEvalOut));
+    if (o->reserved) return set_error(MOT_EINVAL, "%s: reserved %u must be 0", fn, o->reserved);
+    if (((uintptr_t)o->row_loss & 3) || ((uintptr_t)o->pred & 3) || ((uintptr_t)o->rank & 3) || ((uintptr_t)o->counts & 7))
+        return set_error(MOT_EINVAL, "%s: row_loss, pred and rank must be 4-byte aligned, counts 8-byte aligned", fn);
+    if (o->counts && !o->pred) return set_error(MOT_EINVAL, "%s: counts are closed from pred and the targets: counts needs pred", fn);
+    return MOT_OK;
 }
 
 }  // namespace mot

@@ -29,6 +29,38 @@ __device__ __forceinline__ void row_scale(float m0, int L, float eps, float &c, 
     c *= r;
 }
 
+// The evaluation calls (mot_token_head_eval, mot_byte_head_eval): what a row pass writes per row, each pointer optional
+struct HeadEvalRows {
+    float *row_loss;
+    int32_t *pred, *rank;
+    HeadEvalRows at(int64_t first) const { return {row_loss ? row_loss + first : nullptr, pred ? pred + first : nullptr, rank ? rank + first : nullptr}; }
+};
+
+// the larger of two (logit, class) pairs, the lower class on equal logits: commutative and associative, so every order of a
+// reduction ends at the same pair
+__device__ __forceinline__ void argmax_take(float &v, int &i, float ov, int oi) {
+    const bool take = ov > v || (ov == v && oi < i);
+    v = take ? ov : v;
+    i = take ? oi : i;
+}
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ void argmax_dpp(float &v, int &i) {   // lanes outside ROW_MASK meet their own pair
+    const float ov = dpp_move<CTRL, ROW_MASK>(v, v);
+    const int oi = __builtin_amdgcn_update_dpp(i, i, CTRL, ROW_MASK, 0xf, false);
+    argmax_take(v, i, ov, oi);
+}
+// the wave's pair, wave-uniform, on the DPP steps of wave_max (mot_tile.hpp)
+__device__ __forceinline__ void wave_argmax(float &v, int &i) {
+    argmax_dpp<kDppQuadXor1, 0xf>(v, i);
+    argmax_dpp<kDppQuadXor2, 0xf>(v, i);
+    argmax_dpp<kDppRowRor4, 0xf>(v, i);
+    argmax_dpp<kDppRowRor8, 0xf>(v, i);
+    argmax_dpp<kDppRowBcast15, 0xa>(v, i);
+    argmax_dpp<kDppRowBcast31, 0xc>(v, i);
+    v = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+    i = __builtin_amdgcn_readlane(i, 63);
+}
+
 // rows per chunk: the largest multiple of 256 rows of per_row_bytes of scratch under the budget, at least 256, never more than the rows
 inline int64_t head_chunk_rows(int64_t budget_bytes, int64_t per_row_bytes, int64_t rows) {
     int64_t ch = budget_bytes / per_row_bytes / 256 * 256;
@@ -44,5 +76,11 @@ template <typename T>
 int launch_head_chain(const T *x, const float *u, int K, int64_t n, int L, int norm_in, float eps, T *dx, hipStream_t stream);
 // *loss = inv_m * (sum of term[0, rows)) in a fixed order in double; part: kLossParts doubles
 int launch_head_loss(const float *term, int64_t rows, double *part, double inv_m, float *loss, hipStream_t stream);
+// the out struct of an evaluation call, checked before any HIP call; `fn` starts the message
+int head_eval_check(const char *fn, const MotHeadEvalOut *o);
+// counts[0, n_counts) = {rows with a target in [0, vocab), those with pred == target, groups of `per` consecutive rows all of which
+// are such} as integer sums per workgroup, then over the workgroups in order; part: the kLossParts doubles of the loss, free by then
+int launch_head_eval_counts(const int32_t *pred, const int64_t *tgt, int64_t groups, int per, int vocab, void *part, int64_t *counts, int n_counts,
+                            hipStream_t stream);
 
 }  // namespace mot

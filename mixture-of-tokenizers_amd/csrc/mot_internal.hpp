@@ -133,10 +133,12 @@ int byte_head_check(const MotByteHeadDesc *d);
 size_t byte_head_workspace_bytes(const MotByteHeadDesc &d);
 int launch_byte_head_fwd(const MotByteHeadDesc &d, hipStream_t stream);
 int launch_byte_head_bwd(const MotByteHeadDesc &d, const float *grad_loss, void *dx, float *dW, hipStream_t stream);
+int launch_byte_head_eval(const MotByteHeadDesc *d, const MotHeadEvalOut *out, hipStream_t stream);   // its own validation, every refusal before any HIP call
 // the token-level output head (mot_tokhead.hip): validation before any HIP call, then the launches of loss, dx and dW
 int token_head_check(const MotTokenHeadDesc *d);
 size_t token_head_workspace_bytes(const MotTokenHeadDesc &d);
 int launch_token_head_fwd(const MotTokenHeadDesc &d, hipStream_t stream);
+int launch_token_head_eval(const MotTokenHeadDesc *d, const MotHeadEvalOut *out, hipStream_t stream);   // likewise
 // byte self-attention of the concat mixin (mot_bsa.hip); the descriptor is validated in mot_capi.hip
 size_t byte_self_attn_saved_bytes(const MotByteSelfAttnDesc &d);
 size_t byte_self_attn_workspace_bytes(const MotByteSelfAttnDesc &d);

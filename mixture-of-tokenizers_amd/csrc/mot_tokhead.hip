@@ -17,6 +17,8 @@
 // z[y] and the row's loss term, and, when gradients are asked for, writes G in place over the logits from the same registers.  Then
 // u = G W and dW += G^T x are two more products on the shared launchers, and the heads' wave-per-row chain closes dx.  So a chunk's
 // logits are formed once and a training step costs three products.  The gradients are those of grad_loss = 1; the caller scales them.
+// mot_token_head_eval is the loss call without gradients whose row pass (the EVAL instantiations of tokhead_rows) also writes every
+// row's loss term, the class of its largest stored logit and the number of stored logits above the target's (include/mot.h).
 // This unit holds tokhead_rows, the checks and the carve; row_scale, the products, the chunk rule, the chain and the loss's sum are
 // the heads' shared ones (mot_headcore.hpp).
 #include "mot_headcore.hpp"
@@ -112,15 +114,34 @@ __device__ __forceinline__ void vec_grad(LogitVec<T> &a, float c, float lse, flo
     a.put(g);
 }
 
+// the evaluation's share of one vector whose first class is cls0, on the logits as stored: the largest so far with its class (a
+// thread meets its classes in ascending order, so `>` keeps the lowest class of equal logits) and the count of those above sy
+template <typename T>
+__device__ __forceinline__ void vec_top(const LogitVec<T> &a, int cls0, float sy, float &best, int &best_cls, int &above) {
+#pragma unroll
+    for (int e = 0; e < LogitVec<T>::N; ++e) {
+        const float s = a.get(e);
+        if (s > best) {
+            best = s;
+            best_cls = cls0 + e;
+        }
+        above += s > sy ? 1 : 0;
+    }
+}
+
 // One workgroup per row of the chunk.  NV > 0: the row's vectors (nvec = V / N <= NV * blockDim.x) stay in registers between the
 // two uses, vector i of thread t is number t + i * blockDim.x, so a wave's 64 lanes touch 1 KiB at a time and the ragged last
 // round is a predicate.  NV == 0: rows too wide for the register file (V above kRegV) are read a second time.
-template <typename T, int CAP, int NV, bool GRAD>
+// EVAL (never with GRAD) is the evaluation variant: the same sweep also carries the row's largest stored logit with its class and
+// counts the stored logits above the target's, which every thread fetches for itself (one cached address); `ev` takes the results.
+template <typename T, int CAP, int NV, bool GRAD, bool EVAL>
 __global__ __launch_bounds__(kRowThreads) void tokhead_rows(T *S, int V, const T *__restrict__ x, int K, int norm_in, float eps,
                                                             const int64_t *__restrict__ tgt, int64_t rows, float inv_n, float *__restrict__ term,
-                                                            float *__restrict__ row_stats, int64_t stats_stride, uint32_t *status) {
+                                                            float *__restrict__ row_stats, int64_t stats_stride, uint32_t *status, HeadEvalRows ev) {
     typedef LogitVec<T> Vec;
     __shared__ float sh_ss[kRowWavesMax], sh_se[kRowWavesMax], sh_zy[kRowWavesMax];
+    __shared__ float sh_top[EVAL ? kRowWavesMax : 1], sh_above[EVAL ? kRowWavesMax : 1];
+    __shared__ int sh_cls[EVAL ? kRowWavesMax : 1];
     const int64_t r = blockIdx.x;
     if (r >= rows) return;
     const int tid = threadIdx.x, nt = blockDim.x, nvec = V / Vec::N;
@@ -147,16 +168,30 @@ __global__ __launch_bounds__(kRowThreads) void tokhead_rows(T *S, int V, const T
     const bool in_range = y >= 0 && y < V;
     const int yvec = in_range ? (int)(y / Vec::N) : -1, yel = in_range ? (int)(y % Vec::N) : -1;
     float se = 0.f, zy = 0.f;
+    float sy = 0.f, best = -INFINITY;   // EVAL: the target's stored logit, the largest of this thread's
+    int best_cls = 0x7fffffff, above = 0;
+    if (EVAL && in_range) sy = (float)S[r * (int64_t)V + y];
     if (NV > 0) {
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int idx = tid + i * nt;
-            if (idx < nvec) se += vec_stats<T, CAP>(a[i], c, idx == yvec ? yel : -1, zy);
+            if (idx < nvec) {
+                se += vec_stats<T, CAP>(a[i], c, idx == yvec ? yel : -1, zy);
+                if (EVAL) vec_top<T>(a[i], idx * Vec::N, sy, best, best_cls, above);
+            }
         }
     } else {
         for (int idx = tid; idx < nvec; idx += nt) {
             const Vec v = row[idx];
             se += vec_stats<T, CAP>(v, c, idx == yvec ? yel : -1, zy);
+            if (EVAL) vec_top<T>(v, idx * Vec::N, sy, best, best_cls, above);
+        }
+    }
+    if (EVAL) {   // the waves' pairs, met in wave order behind the next sum's barrier
+        wave_argmax(best, best_cls);
+        if ((tid & 63) == 0) {
+            sh_top[tid >> 6] = best;
+            sh_cls[tid >> 6] = best_cls;
         }
     }
     se = rows_block_sum(se, sh_se);
@@ -169,6 +204,15 @@ __global__ __launch_bounds__(kRowThreads) void tokhead_rows(T *S, int V, const T
             row_stats[stats_stride + r] = c;
         }
         if (!in_range && status) atomicOr(status, (uint32_t)MOT_STATUS_TARGET_OOR);
+    }
+    if (EVAL) {
+        const float n_above = rows_block_sum((float)above, sh_above);   // at most kMaxV = 2^18: exact in fp32
+        if (tid == 0) {
+            for (int w = 1; w < (nt >> 6); ++w) argmax_take(best, best_cls, sh_top[w], sh_cls[w]);   // thread 0 holds wave 0's pair
+            if (ev.row_loss) ev.row_loss[r] = in_range ? lse - zy : 0.f;
+            if (ev.pred) ev.pred[r] = best_cls;
+            if (ev.rank) ev.rank[r] = in_range ? (int)n_above : -1;
+        }
     }
     if (!GRAD) return;
     const float scale = in_range ? c * inv_n : 0.f;
@@ -214,15 +258,15 @@ TokWs tok_ws(const TokGeom &g) {
 }
 
 // the row pass of one chunk: the workgroup size and the registers per thread follow the row's number of 16-byte vectors
-template <typename T, int CAP, bool GRAD>
+template <typename T, int CAP, bool GRAD, bool EVAL = false>
 int launch_rows(T *S, const TokGeom &g, const T *x, const int64_t *tgt, int64_t n, float inv_n, float *term, float *row_stats, uint32_t *status,
-                hipStream_t stream) {
+                hipStream_t stream, HeadEvalRows ev = {}) {
     const int nvec = g.V / LogitVec<T>::N;
     const int nt = nvec <= 4 * kRowThreadsSmall ? kRowThreadsSmall : kRowThreads;
     const int nv = (nvec + nt - 1) / nt;
-#define MOT_TOKHEAD_ROWS(NV)                                                                                                                          \
-    hipLaunchKernelGGL((tokhead_rows<T, CAP, NV, GRAD>), dim3((unsigned)n), dim3(nt), 0, stream, S, g.V, x, g.K, g.norm_in, g.eps, tgt, n, inv_n, \
-                       term, row_stats, g.rows, status)
+#define MOT_TOKHEAD_ROWS(NV)                                                                                                                              \
+    hipLaunchKernelGGL((tokhead_rows<T, CAP, NV, GRAD, EVAL>), dim3((unsigned)n), dim3(nt), 0, stream, S, g.V, x, g.K, g.norm_in, g.eps, tgt, n, inv_n, \
+                       term, row_stats, g.rows, status, ev)
     // registers hold a row of up to kRegV classes (16 vectors a thread in fp32, 8 in bf16); a wider row is read twice
     if (nv <= 4) MOT_TOKHEAD_ROWS(4);
     else if (nv <= 8) MOT_TOKHEAD_ROWS(8);
@@ -234,23 +278,23 @@ int launch_rows(T *S, const TokGeom &g, const T *x, const int64_t *tgt, int64_t 
 
 }  // namespace
 
-static int token_head_geom(const MotTokenHeadDesc *d, TokGeom *out) {
-    if (!d) return set_error(MOT_EINVAL, "token_head: null descriptor");
+static int token_head_geom(const MotTokenHeadDesc *d, TokGeom *out, const char *fn = "token_head") {
+    if (!d) return set_error(MOT_EINVAL, "%s: null descriptor", fn);
     if (d->struct_size != sizeof(MotTokenHeadDesc))
-        return set_error(MOT_EINVAL, "token_head: struct_size %u != %zu (ABI mismatch)", d->struct_size, sizeof(MotTokenHeadDesc));
-    if (d->dtype != MOT_F32 && d->dtype != MOT_BF16) return set_error(MOT_EUNSUPPORTED, "token_head: dtype %d is not built", d->dtype);
+        return set_error(MOT_EINVAL, "%s: struct_size %u != %zu (ABI mismatch)", fn, d->struct_size, sizeof(MotTokenHeadDesc));
+    if (d->dtype != MOT_F32 && d->dtype != MOT_BF16) return set_error(MOT_EUNSUPPORTED, "%s: dtype %d is not built", fn, d->dtype);
     if (d->softcap != MOT_SOFTCAP_SIGMOID30 && d->softcap != MOT_SOFTCAP_RSQRT15)
-        return set_error(MOT_EUNSUPPORTED, "token_head: softcap %d is not built (sigmoid30 and rsqrt15 are)", d->softcap);
+        return set_error(MOT_EUNSUPPORTED, "%s: softcap %d is not built (sigmoid30 and rsqrt15 are)", fn, d->softcap);
     if (d->n_rows < 0 || d->n_rows > 0x7fffffffLL || d->model_dim <= 0 || d->vocab <= 0)
-        return set_error(MOT_ESHAPE, "token_head: n_rows %lld, model_dim %d, vocab %d", (long long)d->n_rows, d->model_dim, d->vocab);
+        return set_error(MOT_ESHAPE, "%s: n_rows %lld, model_dim %d, vocab %d", fn, (long long)d->n_rows, d->model_dim, d->vocab);
     if (d->vocab % kMinV || d->vocab > kMaxV)
-        return set_error(MOT_EUNSUPPORTED, "token_head: vocab %d must be a multiple of %d and at most %d", d->vocab, kMinV, kMaxV);
+        return set_error(MOT_EUNSUPPORTED, "%s: vocab %d must be a multiple of %d and at most %d", fn, d->vocab, kMinV, kMaxV);
     if (d->model_dim % 16 || d->model_dim > kMaxD)
-        return set_error(MOT_EUNSUPPORTED, "token_head: model_dim %d must be a multiple of 16 and at most %d", d->model_dim, kMaxD);
+        return set_error(MOT_EUNSUPPORTED, "%s: model_dim %d must be a multiple of 16 and at most %d", fn, d->model_dim, kMaxD);
     if (d->chunk_rows < 0 || d->chunk_rows % 32)
-        return set_error(MOT_ESHAPE, "token_head: chunk_rows %d must be 0 (the library's choice) or a multiple of 32", d->chunk_rows);
+        return set_error(MOT_ESHAPE, "%s: chunk_rows %d must be 0 (the library's choice) or a multiple of 32", fn, d->chunk_rows);
     if ((int64_t)d->chunk_rows * d->vocab > 0x7fffffffLL)
-        return set_error(MOT_EUNSUPPORTED, "token_head: chunk_rows %d x vocab %d exceeds 2^31 logits a chunk", d->chunk_rows, d->vocab);
+        return set_error(MOT_EUNSUPPORTED, "%s: chunk_rows %d x vocab %d exceeds 2^31 logits a chunk", fn, d->chunk_rows, d->vocab);
     TokGeom &g = *out;
     g.rows = d->n_rows;
     g.K = d->model_dim;
@@ -277,8 +321,9 @@ size_t token_head_workspace_bytes(const MotTokenHeadDesc &d) {
     return tok_ws(g).total;
 }
 
+// `ev` set: the evaluation call (no gradients): its row pass also writes ev's rows, and the counts are closed behind the loss
 template <typename T, int CAP>
-static int token_head_run(const MotTokenHeadDesc &d, const TokGeom &g, const TokWs &w, hipStream_t stream) {
+static int token_head_run(const MotTokenHeadDesc &d, const TokGeom &g, const TokWs &w, const MotHeadEvalOut *ev, hipStream_t stream) {
     constexpr bool BF = sizeof(T) == 2;
     unsigned char *ws = (unsigned char *)d.workspace;
     float *term = (float *)(ws + w.term), *u = (float *)(ws + w.u);
@@ -286,6 +331,7 @@ static int token_head_run(const MotTokenHeadDesc &d, const TokGeom &g, const Tok
     const T *X = (const T *)d.x, *W = (const T *)d.weight;
     const bool grad = d.dx || d.dW;
     const float inv_n = (float)(1.0 / (double)g.rows);
+    const HeadEvalRows ev_rows = ev ? HeadEvalRows{ev->row_loss, ev->pred, ev->rank} : HeadEvalRows{};
     int rc;
     if (d.dW && (rc = launch_zero_words(d.dW, (int64_t)g.V * g.K, stream))) return rc;
     if (BF && d.dx && (rc = launch_transpose_bf16(W, g.V, g.K, WT, stream))) return rc;   // WT[k][v]: the operand of u = G W on the bf16 launcher
@@ -294,7 +340,9 @@ static int token_head_run(const MotTokenHeadDesc &d, const TokGeom &g, const Tok
         const T *x = X + r0 * g.K;
         if ((rc = launch_product_nt(head_dtype<T>, x, g.K, n, W, g.K, g.K, g.V, S, g.V, BF, nullptr, false, stream))) return rc;   // s = x W^T for the chunk's rows, in T
         float *stats = d.row_stats ? d.row_stats + r0 : nullptr;
-        if (grad)
+        if (ev)
+            rc = launch_rows<T, CAP, false, true>(S, g, x, d.targets + r0, n, inv_n, term + r0, stats, d.status, stream, ev_rows.at(r0));
+        else if (grad)
             rc = launch_rows<T, CAP, true>(S, g, x, d.targets + r0, n, inv_n, term + r0, stats, d.status, stream);
         else
             rc = launch_rows<T, CAP, false>(S, g, x, d.targets + r0, n, inv_n, term + r0, stats, d.status, stream);
@@ -305,23 +353,40 @@ static int token_head_run(const MotTokenHeadDesc &d, const TokGeom &g, const Tok
         }
         if (d.dW && (rc = launch_product_tn(head_dtype<T>, S, g.V, g.V, x, g.K, g.K, n, d.dW, g.K, stream))) return rc;   // dW += G^T x
     }
-    return launch_head_loss(term, g.rows, (double *)(ws + w.part), 1.0 / (double)g.rows, d.loss, stream);
+    if ((rc = launch_head_loss(term, g.rows, (double *)(ws + w.part), 1.0 / (double)g.rows, d.loss, stream))) return rc;
+    if (ev && ev->counts) return launch_head_eval_counts(ev->pred, d.targets, g.rows, 1, g.V, ws + w.part, ev->counts, 2, stream);
+    return MOT_OK;
+}
+
+// the checks behind the descriptor's own, then the launches; `fn` starts the messages
+static int token_head_launch(const MotTokenHeadDesc &d, const TokGeom &g, const MotHeadEvalOut *ev, const char *fn, hipStream_t stream) {
+    if (!d.x || !d.weight || !d.targets || !d.loss) return set_error(MOT_EINVAL, "%s: null x / weight / targets / loss", fn);
+    if (g.rows == 0) return set_error(MOT_ESHAPE, "%s: no rows (the mean over zero targets is undefined)", fn);
+    const TokWs w = tok_ws(g);
+    if (!d.workspace || d.workspace_bytes < w.total)
+        return set_error(MOT_EWORKSPACE, "%s: workspace %zu bytes < %zu", fn, d.workspace ? d.workspace_bytes : (size_t)0, w.total);
+    if (((uintptr_t)d.x & 15) || ((uintptr_t)d.weight & 15) || ((uintptr_t)d.workspace & 15) || ((uintptr_t)d.dx & 15) || ((uintptr_t)d.dW & 15))
+        return set_error(MOT_EUNSUPPORTED, "%s: x, weight, workspace, dx and dW must be 16-byte aligned", fn);
+    const bool sig = d.softcap == MOT_SOFTCAP_SIGMOID30;
+    if (g.bf16)
+        return sig ? token_head_run<__bf16, MOT_SOFTCAP_SIGMOID30>(d, g, w, ev, stream) : token_head_run<__bf16, MOT_SOFTCAP_RSQRT15>(d, g, w, ev, stream);
+    return sig ? token_head_run<float, MOT_SOFTCAP_SIGMOID30>(d, g, w, ev, stream) : token_head_run<float, MOT_SOFTCAP_RSQRT15>(d, g, w, ev, stream);
 }
 
 int launch_token_head_fwd(const MotTokenHeadDesc &d, hipStream_t stream) {
     TokGeom g;
     int rc = token_head_geom(&d, &g);
     if (rc) return rc;
-    if (!d.x || !d.weight || !d.targets || !d.loss) return set_error(MOT_EINVAL, "token_head: null x / weight / targets / loss");
-    if (g.rows == 0) return set_error(MOT_ESHAPE, "token_head: no rows (the mean over zero targets is undefined)");
-    const TokWs w = tok_ws(g);
-    if (!d.workspace || d.workspace_bytes < w.total)
-        return set_error(MOT_EWORKSPACE, "token_head: workspace %zu bytes < %zu", d.workspace ? d.workspace_bytes : (size_t)0, w.total);
-    if (((uintptr_t)d.x & 15) || ((uintptr_t)d.weight & 15) || ((uintptr_t)d.workspace & 15) || ((uintptr_t)d.dx & 15) || ((uintptr_t)d.dW & 15))
-        return set_error(MOT_EUNSUPPORTED, "token_head: x, weight, workspace, dx and dW must be 16-byte aligned");
-    const bool sig = d.softcap == MOT_SOFTCAP_SIGMOID30;
-    if (g.bf16) return sig ? token_head_run<__bf16, MOT_SOFTCAP_SIGMOID30>(d, g, w, stream) : token_head_run<__bf16, MOT_SOFTCAP_RSQRT15>(d, g, w, stream);
-    return sig ? token_head_run<float, MOT_SOFTCAP_SIGMOID30>(d, g, w, stream) : token_head_run<float, MOT_SOFTCAP_RSQRT15>(d, g, w, stream);
+    return token_head_launch(d, g, nullptr, "token_head", stream);
+}
+
+int launch_token_head_eval(const MotTokenHeadDesc *d, const MotHeadEvalOut *out, hipStream_t stream) {
+    static const char fn[] = "mot_token_head_eval";
+    TokGeom g;
+    int rc = token_head_geom(d, &g, fn);
+    if (rc || (rc = head_eval_check(fn, out))) return rc;
+    if (d->dx || d->dW) return set_error(MOT_EINVAL, "%s: dx / dW set: the evaluation forms no gradients (mot_token_head_fwd does)", fn);
+    return token_head_launch(*d, g, out, fn, stream);
 }
 
 }  // namespace mot

@@ -11,6 +11,7 @@ import ctypes as C
 import math
 import os
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import torch
 
@@ -1195,6 +1196,72 @@ def token_head_loss(x: torch.Tensor, weight: torch.Tensor, targets: torch.Tensor
         x2, w, t = _token_head_operands(x, weight, targets, softcap)
         return _token_head_call(x2, w, t, softcap, norm_in, chunk_rows, None, None)
     return _TokenHeadFn.apply(x, weight, targets, softcap, bool(norm_in), chunk_rows)
+
+
+# ----------------------------------------------------------------------------------------------
+# evaluation form of the two heads: the no-grad loss pass that also writes per-row loss, top-1 prediction and target rank
+# ----------------------------------------------------------------------------------------------
+class HeadEval(NamedTuple):
+    """What token_head_eval / byte_head_eval return.  A row is a token (token-level head) or a byte position (byte head), in the
+    targets' shape.  loss: the fp32 scalar of the loss call, the same bits; row_loss fp32: lse(z) - z[target], 0 for a target out of
+    range; pred int32: the class of the largest logit, the lowest on ties; rank int32: the number of classes whose logit is strictly
+    above the target's, -1 for a target out of range; counts int64 on the device: [rows with a target in range, those with
+    pred == target], and for the byte head a third, the tokens all of whose byte predictions equal their targets."""
+    loss: torch.Tensor
+    row_loss: torch.Tensor
+    pred: torch.Tensor
+    rank: torch.Tensor
+    counts: torch.Tensor
+
+
+def _head_eval_call(dev, d, fn, ws_bytes, shape, n_counts):
+    """The tail of both evaluation calls: the outputs in the targets' shape, the out struct, the launch."""
+    n = math.prod(shape)
+    row_loss = torch.empty(n, dtype=torch.float32, device=dev)
+    pred = torch.empty(n, dtype=torch.int32, device=dev)
+    rank = torch.empty(n, dtype=torch.int32, device=dev)
+    counts = torch.empty(n_counts, dtype=torch.int64, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    d.loss = capi.ptr(loss)
+    o = capi.MotHeadEvalOut()
+    o.struct_size = C.sizeof(capi.MotHeadEvalOut)
+    o.row_loss, o.pred, o.rank, o.counts = capi.ptr(row_loss), capi.ptr(pred), capi.ptr(rank), capi.ptr(counts)
+    _launch(dev, d, fn, C.byref(o), ws_bytes=ws_bytes)
+    return HeadEval(loss, row_loss.reshape(shape), pred.reshape(shape), rank.reshape(shape), counts)
+
+
+@torch.compiler.disable
+@torch.no_grad()
+def token_head_eval(x: torch.Tensor, weight: torch.Tensor, targets: torch.Tensor, *, softcap: str = "sigmoid30", norm_in: bool = True,
+                    chunk_rows: int | None = None) -> HeadEval:
+    """The token-level head for evaluation: the pass of token_head_loss under no_grad over the same chunks, which also writes every
+    token's loss, top-1 prediction and target rank (HeadEval) without any tensor of rows x vocab.  Arguments as token_head_loss;
+    HeadEval.loss has the bits of that call.  pred and rank are taken on the stored products x W^T (bf16 with bfloat16 x), in front of
+    the norm's positive factor and the increasing softcap: rank < k is top-k accuracy.  Forms no gradients in any grad mode.
+    A target outside [0, vocab) raises the status bit that check_status() reports and is left out of loss and counts."""
+    x2, w, t = _token_head_operands(x, weight, targets, softcap)
+    dev = capi.require_device(x2, w, t)
+    d = capi.MotTokenHeadDesc()
+    d.struct_size = C.sizeof(capi.MotTokenHeadDesc)
+    d.dtype, d.softcap, d.norm_in, d.chunk_rows = capi.dtype_code(x2.dtype), _SOFTCAPS[softcap], int(bool(norm_in)), int(chunk_rows or 0)
+    d.n_rows, d.model_dim, d.vocab, d.eps = x2.shape[0], x2.shape[1], w.shape[0], 0.0
+    d.x, d.weight, d.targets = capi.ptr(x2), capi.ptr(w), capi.ptr(t)
+    return _head_eval_call(dev, d, capi.lib.mot_token_head_eval, capi.lib.mot_token_head_workspace_bytes, targets.shape, 2)
+
+
+@torch.compiler.disable
+@torch.no_grad()
+def byte_head_eval(x: torch.Tensor, weight: torch.Tensor, targets: torch.Tensor, *, method: str, bytes_per_token: int,
+                   n_layer_out: int = 0) -> HeadEval:
+    """The byte head for evaluation: the forward of byte_head_loss over the same chunks, which also writes every byte position's
+    loss, top-1 prediction and target rank (HeadEval, in the targets' shape) without any tensor of positions x 512.  Arguments as
+    byte_head_loss; HeadEval.loss has the bits of that call under no_grad.  In copy mode the head computes one row per token: pred
+    is that row's prediction at each of the token's positions, row_loss and rank are each position's own.  counts[2] is the number of
+    tokens with every byte right: the whole-token accuracy a token-level model reports as counts[1].  Forms no gradients."""
+    bpt = int(bytes_per_token)
+    x2, w, t = _byte_head_operands(x, weight, targets, bpt)
+    d, dev = _byte_head_desc(x2, w, t, method, bpt, n_layer_out, None, None)
+    return _head_eval_call(dev, d, capi.lib.mot_byte_head_eval, capi.lib.mot_byte_head_workspace_bytes, targets.shape, 3)
 
 
 # ----------------------------------------------------------------------------------------------

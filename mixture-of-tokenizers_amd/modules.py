@@ -454,6 +454,13 @@ class ByteMixout(nn.Module):  # train_gpt.py:530-542
             return F_mot.token_head_loss(x, lm_head.weight, target_seq, softcap="sigmoid30", norm_in=True)
         return F_mot.byte_head_loss(x, lm_head.weight, target_seq, method=self.method, bytes_per_token=self.bpt, n_layer_out=self.n_layer_out)
 
+    def evaluate(self, x: Tensor, lm_head: nn.Module, target_seq: Tensor) -> "F_mot.HeadEval":
+        """The head of loss() for evaluation: HeadEval(loss, row_loss, pred, rank, counts) per token (noop) or per byte position
+        (copy, split), from one fused pass that forms no gradients."""
+        if self.method == "noop":
+            return F_mot.token_head_eval(x, lm_head.weight, target_seq, softcap="sigmoid30", norm_in=True)
+        return F_mot.byte_head_eval(x, lm_head.weight, target_seq, method=self.method, bytes_per_token=self.bpt, n_layer_out=self.n_layer_out)
+
 
 class FusedFrontEnd(nn.Module):
     """Loader + embed + mixin in one library call: tokens (B,T) -> x (B,T,model_dim), with the
