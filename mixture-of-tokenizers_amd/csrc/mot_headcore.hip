@@ -27,9 +27,9 @@ __global__ __launch_bounds__(kThreads) void head_chain_rows(const T *__restrict_
     }
     ss = wave_sum(ss);
     xu = wave_sum(xu);
-    float c, dc;
-    row_scale(ss / (float)K, L, eps, c, dc);
-    const float coef = dc * (2.f / (float)K) * xu / c;
+    // a row that is zero to fp32's sum of squares has dx_r = u_r: its x term is 0 x_r, whatever the factor (which no format holds at L > 44)
+    const float m0 = ss / (float)K;
+    const float coef = m0 > 0.f ? (float)(row_scale_dlog((double)m0, L, (double)eps) * (2.0 / (double)K) * (double)xu) : 0.f;
     for (int k = lane; k < K; k += 64) dx[r * K + k] = (T)(ur[k] + coef * (float)xr[k]);
 }
 

@@ -29,6 +29,20 @@ __device__ __forceinline__ void row_scale(float m0, int L, float eps, float &c, 
     c *= r;
 }
 
+// (dc/dm0) / c of row_scale, for the row chain: the same recurrence on the logarithm of c, in double.  A row whose mean square lies
+// far below eps (a zero row, a row of 2^-60) has r = eps^-1/2 in every layer, so dm grows by (1 + r)^2 = 8.4e6 a layer and dc/dm0
+// (1e45 at L = 3) leaves fp32, while its product with x . u in the chain fits.  m0 > 0 keeps every term finite up to L = 64.
+__device__ __forceinline__ double row_scale_dlog(double m0, int L, double eps) {
+    double m = m0, dm = 1.0, q = 0.0;
+    for (int i = 0; i < L; ++i) {
+        const double r = 1.0 / sqrt(m + eps), dr = -0.5 * r * r * r * dm, a = 1.0 + r;
+        q += dr / a;
+        dm = dm * a * a + 2.0 * m * a * dr;
+        m *= a * a;
+    }
+    return q - 0.5 * dm / (m + eps);
+}
+
 // The evaluation calls (mot_token_head_eval, mot_byte_head_eval): what a row pass writes per row, each pointer optional
 struct HeadEvalRows {
     float *row_loss;

@@ -12,26 +12,29 @@ VOCAB = 512            # next_multiple_of_n(458, n=128)
 N_TOKENS, BPT = 16, 8  # the fixture's cases
 DIMS = {"copy": 16, "split": 128}
 LAYERS = (0, 1, 2)
+HEAD_EPS = 2.0 ** -23  # the head's epsilon in every dtype (kHeadEps): what F.rms_norm(eps=None) takes in fp32, not in float64
 
 
-def byte_states(x: torch.Tensor, method: str, bpt: int, n_layer_out: int) -> torch.Tensor:
-    """ByteMixoutCopy / ByteMixoutSplit.forward with identity layers: x (..., T, D) -> (..., T*bpt, D or D/bpt)."""
+def byte_states(x: torch.Tensor, method: str, bpt: int, n_layer_out: int, eps=None) -> torch.Tensor:
+    """ByteMixoutCopy / ByteMixoutSplit.forward with identity layers: x (..., T, D) -> (..., T*bpt, D or D/bpt).  `eps` goes to every
+    F.rms_norm: None is the dtype's own (2.2e-16 in float64), HEAD_EPS the head's, which rows near zero need."""
     if method == "copy":
         h = x.repeat_interleave(bpt, dim=-2)
     else:
         h = x.reshape(*x.shape[:-2], x.shape[-2] * bpt, x.shape[-1] // bpt)
     for _ in range(n_layer_out):
-        h = h + F.rms_norm(h, (h.size(-1),))
+        h = h + F.rms_norm(h, (h.size(-1),), eps=eps)
     return h
 
 
-def head(x, w, targets, method, bpt, n_layer_out, dtype=torch.float64, drop=None):
+def head(x, w, targets, method, bpt, n_layer_out, dtype=torch.float64, drop=None, eps=None):
     """Eager forward + backward in `dtype` (the weight cast to it, as CastedLinear does; logits softcapped in fp32 or float64).
-    Returns dict(states, loss, dx, dW) in float64.  `drop`: flat indices of targets whose terms leave the sum (denominator M)."""
+    Returns dict(states, loss, dx, dW) in float64.  `drop`: flat indices of targets whose terms leave the sum (denominator M);
+    `eps` as in byte_states."""
     xd = x.detach().to(dtype).clone().requires_grad_(True)
     wd = w.detach().to(torch.float64 if dtype == torch.float64 else torch.float32).clone().requires_grad_(True)
-    h = byte_states(xd, method, bpt, n_layer_out)
-    logits = F.linear(F.rms_norm(h, (h.size(-1),)), wd.type_as(h))
+    h = byte_states(xd, method, bpt, n_layer_out, eps)
+    logits = F.linear(F.rms_norm(h, (h.size(-1),), eps=eps), wd.type_as(h))
     z = 30 * torch.sigmoid((logits.double() if dtype == torch.float64 else logits.float()) / 7.5)
     z = z.reshape(-1, z.size(-1))
     t = targets.reshape(-1).long()

@@ -74,22 +74,28 @@ def test_order_of_the_backward_pointer_checks():
     assert bwd(256, 256, 256) == capi.MOT_ESHAPE and "no targets" in _err()
 
 
-@pytest.mark.parametrize("method, dtype, n_tokens, rows, chunk", [
-    (capi.HEAD_COPY, capi.F32, 20000, 20000, 16384),
-    (capi.HEAD_COPY, capi.BF16, 20000, 20000, 12288),
-    (capi.HEAD_SPLIT, capi.F32, 1536, 24576, 23808),
-    (capi.HEAD_SPLIT, capi.BF16, 1536, 24576, 15872),
-    (capi.HEAD_SPLIT, capi.BF16, 40, 640, 640),   # a chunk never exceeds the rows there are
-])
-def test_workspace_query(method, dtype, n_tokens, rows, chunk):
+@pytest.mark.parametrize("method, dtype, D, bpt, n_tokens, rows, chunk", [pytest.param(*c, id="-".join(map(str, c[:2] + c[4:]))) for c in [
+    (capi.HEAD_COPY, capi.F32, 256, 16, 20000, 20000, 16384),
+    (capi.HEAD_COPY, capi.BF16, 256, 16, 20000, 20000, 12288),
+    (capi.HEAD_SPLIT, capi.F32, 256, 16, 1536, 24576, 23808),
+    (capi.HEAD_SPLIT, capi.BF16, 256, 16, 1536, 24576, 15872),
+    (capi.HEAD_SPLIT, capi.BF16, 256, 16, 40, 640, 640),   # a chunk never exceeds the rows there are
+    # the widest row, K 2048, has the shortest chunk: the seams of tests/test_gpu_byte_head_edges.py, a full chunk and 37 or 38 rows
+    (capi.HEAD_COPY, capi.F32, 2048, 2, 4901, 4901, 4864),
+    (capi.HEAD_COPY, capi.BF16, 2048, 2, 4389, 4389, 4352),
+    (capi.HEAD_SPLIT, capi.F32, 4096, 2, 2451, 4902, 4864),
+    (capi.HEAD_SPLIT, capi.BF16, 4096, 2, 2195, 4390, 4352),
+]])   # the ids name method, dtype and the rows, as they did before D and bpt became parameters
+def test_workspace_query(method, dtype, D, bpt, n_tokens, rows, chunk):
     """The carve of mot_head.hip written out: per-row terms, the loss partials, a chunk's fp32 logits, its bf16 gradient (bf16), u,
     and the k-major bf16 weight (bf16), each rounded up to 256 bytes.  A chunk is the largest multiple of 256 rows whose pieces
     stay below 48 MiB, at least 256 and at most the rows."""
-    D, bpt, bf = 256, 16, dtype == capi.BF16
+    bf = dtype == capi.BF16
     K = D if method == capi.HEAD_COPY else D // bpt
     assert rows == (n_tokens if method == capi.HEAD_COPY else n_tokens * bpt)
     per_row = 512 * 4 + (512 * 2 if bf else 0) + K * 4
     assert chunk == min(rows, max(256, (48 << 20) // per_row // 256 * 256))
+    assert K < 2048 or chunk < rows < 2 * chunk   # the seam cases: two chunks, the second a short one
     up = lambda b: (b + 255) // 256 * 256
     want = up(4 * rows) + up(512 * 8) + up(chunk * 512 * 4) + up(chunk * K * 4)
     if bf:
