@@ -530,6 +530,30 @@ int mot_byte_head_fwd(const MotByteHeadDesc *desc /* host */, mot_stream_t strea
 int mot_byte_head_bwd(const MotByteHeadDesc *desc /* host */, const float *grad_loss, void *dx, float *dW, mot_stream_t stream);
 
 /*
+ * The split-mode training step in ONE call: mot_byte_head_fwd followed by mot_byte_head_bwd with grad_loss = 1 (the caller scales dx
+ * and dW by the incoming gradient on the device, as with mot_token_head_fwd), on one fused kernel: each workgroup of a persistent
+ * grid holds W in LDS and walks tiles of 256 byte rows; a tile's logits are formed on the MFMA with the rows on the lanes, and the
+ * cap, the loss term, G, u = G W and the row chain stay in registers, so nothing 512 wide per row goes to memory on the way to loss
+ * and dx.  dW = G^T x: the kernel stores a chunk's G in dtype (bf16: 1 KB a row; 131 072 rows a chunk) and the shared product adds
+ * the chunk into dW with fp32 atomics, as mot_byte_head_bwd does.
+ *   loss   as mot_byte_head_fwd: fixed-order sum, the same bits every run; out-of-range targets as there (term dropped, G row zero,
+ *          so that row of dx is exactly zero, M stays, MOT_STATUS_TARGET_OOR raised).
+ *   dx     [n_tokens, model_dim] in dtype, written once per element, the same bits every run; the row chain is mot_byte_head_bwd's.
+ *   dW     [512, K] fp32, OVERWRITTEN (the caller zeroes nothing).
+ *   dx = dW = NULL: the loss alone, nothing written per logit, the same loss bits.  One of the two NULL: MOT_EINVAL.
+ * desc->row_stats is ignored (may be NULL); eps <= 0 as above.  Asynchronous on `stream`, no allocation, no host read, no memset or
+ * memcpy node: hipGraph-capturable.  bf16 rounding points are those of the pair: G rounded once to bf16, u in fp32, dx rounded once.
+ * Built: method MOT_HEAD_SPLIT, vocab 512, K = model_dim / bpt a multiple of 16 and at most 128 in MOT_BF16, 64 in MOT_F32 (W and
+ * its staging must fit in LDS).  Everything else is refused before any HIP call, mot_last_error() starting with "byte_head_step":
+ * MOT_EUNSUPPORTED for copy mode (use mot_byte_head_fwd / _bwd), another vocab, an unknown dtype, K not a multiple of 16 or above
+ * its bound, n_tokens * bpt > 2^31, a misaligned x, weight or dx; MOT_ESHAPE for the shapes mot_byte_head_fwd refuses and for no
+ * targets; MOT_EINVAL for a null x, weight, targets or loss; MOT_EWORKSPACE (with the size) for a missing or short workspace.
+ * The workspace query returns 0 for a refused descriptor.
+ */
+size_t mot_byte_head_step_workspace_bytes(const MotByteHeadDesc *desc /* host */);
+int mot_byte_head_step(const MotByteHeadDesc *desc /* host */, void *dx, float *dW, mot_stream_t stream);
+
+/*
  * Token-level output head, forward and backward in one call: replaces the last five lines of every training script
  *   scaled-pre-train/train_gpt.py:619-623 with byte_mixout_method "noop"   (norm; lm_head; 30 sigmoid(l.float() / 7.5); cross_entropy)
  *   modded-nanogpt/runs/71_*.py:331-334, and the other 49 runs alike       (norm; F.linear; 15 l rsqrt(l^2 + 225); cross_entropy)

@@ -4,7 +4,7 @@ Hand-written HIP kernels behind a C ABI (include/mot.h, csrc/), called through c
 Python layer mirrors the reference's interfaces for this path and nothing else:
 
   data_creation   make_embedding / tokens_to_bytes / pull_from_left / pull_from_right / create_batch
-  functional      tensor-level wrappers (embed_mix = the fused gather + mix forward; byte_head_loss = the mixout byte head; token_head_loss = the token-level head;
+  functional      tensor-level wrappers (embed_mix = the fused gather + mix forward; byte_head_loss = the mixout byte head (one_call=True: split mode's step on one fused kernel); token_head_loss = the token-level head;
                   token_head_eval / byte_head_eval = the heads' evaluation form: per-row loss, top-1 prediction, target rank, counts;
                   byte_self_attn = the sliding-window byte self-attention layer of the concat mixin;
                   byte_fc_mix = the linear-on-bytes mixin of run 71051; byte_cat = the bytes-only front-end and byte value embeddings

@@ -57,6 +57,7 @@ EXPORTS = (
     "mot_cross_attn_bwd_workspace_bytes", "mot_cross_attn_bwd",
     "mot_char_swa_desc_size", "mot_char_swa_workspace_bytes", "mot_char_swa_fwd",
     "mot_byte_head_desc_size", "mot_byte_head_workspace_bytes", "mot_byte_head_fwd", "mot_byte_head_bwd",
+    "mot_byte_head_step_workspace_bytes", "mot_byte_head_step",
     "mot_token_head_desc_size", "mot_token_head_workspace_bytes", "mot_token_head_fwd",
     "mot_head_eval_out_size", "mot_token_head_eval", "mot_byte_head_eval",
     "mot_byte_self_attn_desc_size", "mot_byte_self_attn_saved_bytes", "mot_byte_self_attn_workspace_bytes",
@@ -364,6 +365,10 @@ def _load() -> C.CDLL:
     lib.mot_byte_head_fwd.restype = C.c_int
     lib.mot_byte_head_bwd.argtypes = [C.POINTER(MotByteHeadDesc), vp, vp, vp, vp]
     lib.mot_byte_head_bwd.restype = C.c_int
+    lib.mot_byte_head_step_workspace_bytes.restype = C.c_size_t
+    lib.mot_byte_head_step_workspace_bytes.argtypes = [C.POINTER(MotByteHeadDesc)]
+    lib.mot_byte_head_step.argtypes = [C.POINTER(MotByteHeadDesc), vp, vp, vp]
+    lib.mot_byte_head_step.restype = C.c_int
     lib.mot_token_head_desc_size.restype = C.c_size_t
     lib.mot_token_head_workspace_bytes.restype = C.c_size_t
     lib.mot_token_head_workspace_bytes.argtypes = [C.POINTER(MotTokenHeadDesc)]

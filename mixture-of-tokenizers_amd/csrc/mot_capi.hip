@@ -373,6 +373,12 @@ int mot_byte_head_eval(const MotByteHeadDesc *desc, const MotHeadEvalOut *out, m
     return launch_byte_head_eval(desc, out, (hipStream_t)stream);
 }
 
+size_t mot_byte_head_step_workspace_bytes(const MotByteHeadDesc *desc) { return byte_head_step_workspace_bytes(desc); }
+
+int mot_byte_head_step(const MotByteHeadDesc *desc, void *dx, float *dW, mot_stream_t stream) {
+    return launch_byte_head_step(desc, dx, dW, (hipStream_t)stream);
+}
+
 size_t mot_token_head_desc_size(void) { return sizeof(MotTokenHeadDesc); }
 
 size_t mot_token_head_workspace_bytes(const MotTokenHeadDesc *desc) {

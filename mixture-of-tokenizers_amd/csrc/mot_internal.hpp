@@ -134,6 +134,9 @@ size_t byte_head_workspace_bytes(const MotByteHeadDesc &d);
 int launch_byte_head_fwd(const MotByteHeadDesc &d, hipStream_t stream);
 int launch_byte_head_bwd(const MotByteHeadDesc &d, const float *grad_loss, void *dx, float *dW, hipStream_t stream);
 int launch_byte_head_eval(const MotByteHeadDesc *d, const MotHeadEvalOut *out, hipStream_t stream);   // its own validation, every refusal before any HIP call
+// the split-mode training step in one call (mot_headstep.hip): its own validation, every refusal before any HIP call
+size_t byte_head_step_workspace_bytes(const MotByteHeadDesc *d);   // 0 for a descriptor the call would refuse
+int launch_byte_head_step(const MotByteHeadDesc *d, void *dx, float *dW, hipStream_t stream);
 // the token-level output head (mot_tokhead.hip): validation before any HIP call, then the launches of loss, dx and dW
 int token_head_check(const MotTokenHeadDesc *d);
 size_t token_head_workspace_bytes(const MotTokenHeadDesc &d);

@@ -1107,15 +1107,82 @@ class _ByteHeadFn(torch.autograd.Function):
         return dx.reshape(xshape), dw.to(wdtype), None, None, None, None
 
 
+def _byte_head_step_call(x2, w, t, bpt, n_layer_out, dx, dw):
+    """One mot_byte_head_step: the loss, and the gradients for grad_loss = 1 into dx / dw where given."""
+    loss = torch.empty((), dtype=torch.float32, device=x2.device)
+    d, dev = _byte_head_desc(x2, w, t, "split", bpt, n_layer_out, None, loss)
+    _launch(dev, d, capi.lib.mot_byte_head_step, capi.ptr(dx), capi.ptr(dw), ws_bytes=capi.lib.mot_byte_head_step_workspace_bytes)
+    return loss
+
+
+def _byte_head_step_operands(x, weight, targets, method, bpt, n_layer_out):
+    """The operands of the one-call form.  What the call does not build (copy mode, a row width or dtype outside its limits) is
+    refused by the library itself, from the shapes alone and before the device check: NotImplementedError with its message."""
+    if method not in _HEAD_METHODS:
+        raise ValueError(f"byte_head_loss: method must be 'copy' or 'split', got {method!r}")
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"byte_head_loss: x must be float32 or bfloat16, got {x.dtype}")
+    if weight.ndim != 2:
+        raise ValueError("byte_head_loss: weight must be (vocab, in_features)")
+    d = capi.MotByteHeadDesc()
+    d.struct_size = C.sizeof(capi.MotByteHeadDesc)
+    d.method, d.dtype, d.bpt = _HEAD_METHODS[method], capi.dtype_code(x.dtype), int(bpt)
+    d.n_tokens, d.model_dim, d.n_layer_out, d.vocab = x.numel() // max(x.shape[-1], 1), x.shape[-1], int(n_layer_out), weight.shape[0]
+    rc = capi.lib.mot_byte_head_step(C.byref(d), None, None, None)   # no pointers: the shape checks come first, nothing is launched
+    if rc in (capi.MOT_EUNSUPPORTED, capi.MOT_ESHAPE):
+        capi.check(rc)
+    capi.require_device(x, weight, targets)
+    return _byte_head_operands(x, weight, targets, bpt)
+
+
+class _ByteHeadStepFn(torch.autograd.Function):
+    """forward = one mot_byte_head_step that also forms dx and the fp32 dW for grad_loss = 1; backward multiplies them by the incoming
+    grad_loss on the device, out of place (a retained graph runs backward again on the same saved gradients)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, targets, method, bpt, n_layer_out):
+        x2, w, t = _byte_head_step_operands(x, weight, targets, method, bpt, n_layer_out)
+        dx = torch.empty_like(x2)
+        dw = torch.empty(w.shape, dtype=torch.float32, device=x2.device)
+        loss = _byte_head_step_call(x2, w, t, bpt, n_layer_out, dx, dw)
+        ctx.save_for_backward(dx, dw)
+        ctx.cfg = (x.shape, weight.dtype, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss):
+        dx, dw = ctx.saved_tensors
+        xshape, wdtype, need_x, need_w = ctx.cfg
+        go = grad_loss.detach().reshape(1, 1).float()
+        gx = gw = None
+        if need_x:   # one elementwise pass: fp32 factor, fp32 product, one rounding on store
+            gx = torch.mul(dx, go, out=torch.empty_like(dx)).reshape(xshape)
+        if need_w:
+            gw = torch.mul(dw, go, out=torch.empty(dw.shape, dtype=wdtype, device=dw.device))
+        return gx, gw, None, None, None, None
+
+
 @torch.compiler.disable
 def byte_head_loss(x: torch.Tensor, weight: torch.Tensor, targets: torch.Tensor, *, method: str, bytes_per_token: int,
-                   n_layer_out: int = 0) -> torch.Tensor:
+                   n_layer_out: int = 0, one_call: bool = False) -> torch.Tensor:
     """The byte output head of a mixout run with identity layers (use_byte_self_attn off), train_gpt.py:618-623:
     h = repeat (copy) or rearrange (split) of x into byte rows; h = h + norm(h) n_layer_out times; logits = norm(h) @ weight.T;
     z = 30 sigmoid(logits.float() / 7.5); returns cross_entropy(z, targets) (mean over all n_tokens * bytes_per_token targets) as an
     fp32 scalar.  x (..., model_dim) float32 or bfloat16; weight (512, model_dim or model_dim / bpt), cast to x's dtype as CastedLinear
     does; targets int64 (..., T * bpt).  Differentiable in x and weight (the weight's gradient in the weight's dtype).
-    A target outside [0, 512) raises the status bit that check_status() reports; its term is left out of the sum."""
+    A target outside [0, 512) raises the status bit that check_status() reports; its term is left out of the sum.
+    one_call=True takes the split-mode step on one fused kernel (mot_byte_head_step): with grad mode on, the one call forms the loss,
+    dx and the fp32 dW, and backward only scales them by the incoming gradient; under no_grad, or with neither input requiring a
+    gradient, it is the loss alone, with the same bits.  It is built for method="split" with a row width model_dim / bytes_per_token
+    that is a multiple of 16 and at most 128 in bfloat16, 64 in float32; anything else raises NotImplementedError here, with the
+    library's message (there is no fallback to the two-call path)."""
+    if one_call:
+        bpt, L = int(bytes_per_token), int(n_layer_out)
+        if not torch.is_grad_enabled() or not (x.requires_grad or weight.requires_grad):
+            x2, w, t = _byte_head_step_operands(x, weight, targets, method, bpt, L)
+            return _byte_head_step_call(x2, w, t, bpt, L, None, None)
+        return _ByteHeadStepFn.apply(x, weight, targets, method, bpt, L)
     return _ByteHeadFn.apply(x, weight, targets, method, int(bytes_per_token), int(n_layer_out))
 
 

@@ -430,7 +430,7 @@ class ByteMixout(nn.Module):  # train_gpt.py:530-542
     """The reference's ByteMixout with identity ByteSelfAttn layers (the only kind its runs build at the output).
     forward(x) returns the byte-level states in plain torch ops, so an unmodified GPT.forward still works;
     loss(x, lm_head, target_seq) is the fused head in place of train_gpt.py:618-623: one mot_byte_head_fwd / _bwd pair for copy and
-    split, one mot_token_head_fwd for noop (the token-level head over lm_head's 50 304 rows)."""
+    split (or, with one_call=True, one mot_byte_head_step for split), one mot_token_head_fwd for noop (the token-level head over lm_head's 50 304 rows)."""
 
     def __init__(self, dims: ModelDims, max_seq_len: int, byte_params: ByteHyperparameters):
         super().__init__()
@@ -448,11 +448,14 @@ class ByteMixout(nn.Module):  # train_gpt.py:530-542
     def forward(self, x: Tensor) -> Tensor:
         return self.mixout(x)
 
-    def loss(self, x: Tensor, lm_head: nn.Module, target_seq: Tensor) -> Tensor:
-        """cross_entropy(30 sigmoid(lm_head(norm(self(x))).float() / 7.5), target_seq), fused; x (..., T, model_dim)."""
+    def loss(self, x: Tensor, lm_head: nn.Module, target_seq: Tensor, one_call: bool = False) -> Tensor:
+        """cross_entropy(30 sigmoid(lm_head(norm(self(x))).float() / 7.5), target_seq), fused; x (..., T, model_dim).
+        one_call=True takes byte_head_loss(one_call=True), the split-mode step on one fused kernel (row width at most 128 in bfloat16, 64 in
+        float32; what it does not build raises NotImplementedError); noop is one call either way."""
         if self.method == "noop":   # the token-level head: targets are tokens, one per row of x
             return F_mot.token_head_loss(x, lm_head.weight, target_seq, softcap="sigmoid30", norm_in=True)
-        return F_mot.byte_head_loss(x, lm_head.weight, target_seq, method=self.method, bytes_per_token=self.bpt, n_layer_out=self.n_layer_out)
+        return F_mot.byte_head_loss(x, lm_head.weight, target_seq, method=self.method, bytes_per_token=self.bpt, n_layer_out=self.n_layer_out,
+                                    one_call=one_call)
 
     def evaluate(self, x: Tensor, lm_head: nn.Module, target_seq: Tensor) -> "F_mot.HeadEval":
         """The head of loss() for evaluation: HeadEval(loss, row_loss, pred, rank, counts) per token (noop) or per byte position
