@@ -49,7 +49,7 @@ typedef enum MotStatus {
  * never fault -- the host shim turns a non-zero word into the reference's IndexError. */
 #define MOT_STATUS_TOKEN_OOR 1u /* token id outside [0, tok_rows) / [0, ttb_rows) */
 #define MOT_STATUS_BYTE_OOR 2u  /* byte id outside [0, byte_rows)                 */
-#define MOT_STATUS_TARGET_OOR 4u /* target outside [0, vocab) (mot_byte_head_*, mot_token_head_*) */
+#define MOT_STATUS_TARGET_OOR 4u /* target outside [0, vocab) (mot_byte_head_*, mot_token_head_*, mot_plain_head_*) */
 
 typedef enum MotPullDir {
     MOT_PULL_NONE = 0,
@@ -647,6 +647,75 @@ typedef struct MotHeadEvalOut {
 size_t mot_head_eval_out_size(void);
 int mot_token_head_eval(const MotTokenHeadDesc *desc /* host */, const MotHeadEvalOut *out /* host */, mot_stream_t stream);
 int mot_byte_head_eval(const MotByteHeadDesc *desc /* host */, const MotHeadEvalOut *out /* host */, mot_stream_t stream);
+
+/*
+ * Plain cross-entropy head, forward and backward in one call: lm_head and F.cross_entropy on the logits as they are, with NO softcap,
+ * with ignore_index, and with the mean taken over the kept targets.  Replaces the loss of the reference's two remaining loops:
+ *   mathblations/model.py:337-338 with main.py:294-303, evaluation main.py:164-187
+ *       (F.rms_norm(x); lm_head(x).float(); slice_logits_and_targets; F.cross_entropy; argmax accuracies; 50 304 classes in fp32)
+ *   inference/inference.py:349-359
+ *       (lm_head(hidden_states); shift; CrossEntropyLoss(), i.e. ignore_index -100 and the mean over the kept targets; 128 256
+ *        classes at model_dim 2048, hidden states already normed: norm_in = 0, the shift stays with the caller)
+ * mot_token_head_* cannot serve them: its row pass takes lse from the softcap's constant bound, it has no ignore_index and it
+ * divides by n_rows.  Per row r of x [n_rows, model_dim], weight [vocab, model_dim], targets [n_rows]:
+ *   c_r = (mean(x_r^2) + eps)^-1/2 with norm_in, else 1;   l = c_r (x_r W^T);   m_r = max_v l;   lse_r = m_r + log sum_v exp(l - m_r).
+ * The product is stored per chunk in fp32, or in bf16 in MOT_BF16 (where lm_head returns bf16); everything behind it is fp32:
+ * cross_entropy(lm_head(x).float(), y), the expression of model.py:338.
+ * A row is KEPT when 0 <= y_r < vocab and y_r != ignore_index; `kept` is the number of kept rows.  A target equal to ignore_index
+ * drops its row silently (set the field to -100 for torch's default, or to any value no target takes); any other target outside
+ * [0, vocab) drops its row too and ORs MOT_STATUS_TARGET_OOR into `status` (torch would assert there).
+ *   loss = (sum over kept rows of (lse_r - l_r[y_r])) / kept: one fp32 scalar from the heads' fixed-order double sum, the same bits
+ *          on every run.  kept == 0 gives NaN (0 / 0, as F.cross_entropy returns) and gradients that are exactly zero.
+ * Scoring the window [start, end) of each sequence (slice_logits_and_targets) is this loss with every other position's target set
+ * to ignore_index.  `kept` is counted on the device in front of the first chunk and never read on the host: no allocation, no host
+ * read, no memset or memcpy node, so loss, dx and dW capture into a hipGraph, and a replay follows targets changed in place.
+ * With dx and dW NULL the call is the loss alone.  With either set the same pass over a chunk forms the gradients FOR grad_loss = 1:
+ *   G_r = (c_r / kept) (softmax(l_r) - onehot(y_r)) for a kept row, a row of zeros otherwise;   u = G W;
+ *   dx [n_rows, model_dim] in dtype = u_r - c_r^2 (x_r . u_r / model_dim) x_r with norm_in, else u_r; written once per row;
+ *   dW [vocab, model_dim] fp32 = G^T x, zeroed by the call, then summed over the rows with fp32 atomics.
+ * Chunks, workspace and shapes are the token-level head's: chunk_rows = 0 is the largest multiple of 256 rows whose logits and u
+ * stay below 512 MiB (2560 rows of fp32 logits at 50 304 x 768; 1024 of fp32 and 1792 of bf16 logits at 128 256 x 2048), at least
+ * 256, never more than n_rows.  Checked before any HIP call, with a message that starts with the function's name: vocab not a
+ * multiple of 128 or above 262 144, model_dim not a multiple of 16 or above 2048, an unknown dtype -> MOT_EUNSUPPORTED; chunk_rows
+ * neither 0 nor a multiple of 32, group_rows negative or not dividing n_rows, no rows -> MOT_ESHAPE; chunk_rows x vocab above 2^31
+ * -> MOT_EUNSUPPORTED; a null descriptor, x, weight, targets or loss, a wrong struct_size -> MOT_EINVAL; a missing or short workspace
+ * -> MOT_EWORKSPACE; a misaligned pointer -> MOT_EUNSUPPORTED.  The workspace query returns 0 for what the call refuses; it reads
+ * dx (set or NULL) and no other pointer.
+ * mot_plain_head_eval is the evaluation form (MotHeadEvalOut above, dx = dW = NULL): row_loss, pred and rank as defined there on the
+ * stored product (c_r > 0 changes no order), the lowest class on ties; for a dropped row row_loss = 0, rank = -1, pred still
+ * written.  desc->loss has the bits of mot_plain_head_fwd without gradients.  counts = int64 [kept, kept rows with pred == target],
+ * and with group_rows > 0 a third entry: the groups of group_rows consecutive rows (a sequence) that have at least one kept row and
+ * whose kept rows are ALL right, full_correct of main.py:183-187.  Dropped rows count neither for nor against their group (the byte
+ * head's third count differs there).  group_rows is read by the evaluation alone.
+ * Not built: label smoothing; the 14-class digit head of digit_mixout_method != "noop"; compaction of the kept rows in front of
+ * the products (every row's logits are formed, kept or not).
+ */
+typedef struct MotPlainHeadDesc {
+    uint32_t struct_size; /* sizeof(MotPlainHeadDesc) */
+    int32_t dtype;        /* MotDType of x, weight and dx */
+    int32_t norm_in;      /* 1: x is rms-normed first (model.py:337), 0: x is taken as it is (inference.py:349) */
+    int32_t chunk_rows;   /* rows per chunk: 0 = the library's choice, else a multiple of 32 */
+    int64_t n_rows;       /* B * T */
+    int32_t model_dim;    /* columns of x and of weight */
+    int32_t vocab;        /* rows of weight: 50 304, 128 256 */
+    float eps;            /* of the norm; <= 0 -> FLT_EPSILON, as F.rms_norm(eps=None) takes it, on bf16 inputs too */
+    int32_t group_rows;   /* evaluation: rows per group (a sequence) of the third count; 0 = two counts */
+    int64_t ignore_index; /* targets equal to it drop their rows silently; torch's default is -100 */
+    const void *x;        /* [n_rows, model_dim], 16-byte aligned */
+    const void *weight;   /* [vocab, model_dim] in dtype, 16-byte aligned */
+    const int64_t *targets; /* [n_rows] */
+    float *loss;          /* fp32 scalar */
+    uint32_t *status;     /* optional, as in MotEmbedMixDesc */
+    void *workspace;      /* >= mot_plain_head_workspace_bytes(desc), 16-byte aligned */
+    size_t workspace_bytes;
+    void *dx;             /* optional [n_rows, model_dim] in dtype, 16-byte aligned, OVERWRITTEN */
+    float *dW;            /* optional [vocab, model_dim] fp32, 16-byte aligned, OVERWRITTEN */
+} MotPlainHeadDesc;
+
+size_t mot_plain_head_desc_size(void);
+size_t mot_plain_head_workspace_bytes(const MotPlainHeadDesc *desc /* host */);
+int mot_plain_head_fwd(const MotPlainHeadDesc *desc /* host */, mot_stream_t stream);
+int mot_plain_head_eval(const MotPlainHeadDesc *desc /* host */, const MotHeadEvalOut *out /* host */, mot_stream_t stream);
 
 /*
  * Byte self-attention in front of the concat mixin, forward: replaces ByteSelfAttn.forward with use_byte_self_attn on

@@ -60,6 +60,7 @@ EXPORTS = (
     "mot_byte_head_step_workspace_bytes", "mot_byte_head_step",
     "mot_token_head_desc_size", "mot_token_head_workspace_bytes", "mot_token_head_fwd",
     "mot_head_eval_out_size", "mot_token_head_eval", "mot_byte_head_eval",
+    "mot_plain_head_desc_size", "mot_plain_head_workspace_bytes", "mot_plain_head_fwd", "mot_plain_head_eval",
     "mot_byte_self_attn_desc_size", "mot_byte_self_attn_saved_bytes", "mot_byte_self_attn_workspace_bytes",
     "mot_byte_self_attn_fwd", "mot_byte_self_attn_bwd",
     "mot_byte_fc_mix_desc_size", "mot_byte_fc_mix_workspace_bytes", "mot_byte_fc_mix_bwd_workspace_bytes",
@@ -167,6 +168,16 @@ class MotTokenHeadDesc(C.Structure):
         ("struct_size", C.c_uint32), ("dtype", C.c_int32), ("softcap", C.c_int32), ("norm_in", C.c_int32), ("n_rows", C.c_int64),
         ("model_dim", C.c_int32), ("vocab", C.c_int32), ("eps", C.c_float), ("chunk_rows", C.c_int32),
         ("x", C.c_void_p), ("weight", C.c_void_p), ("targets", C.c_void_p), ("loss", C.c_void_p), ("row_stats", C.c_void_p),
+        ("status", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("dx", C.c_void_p), ("dW", C.c_void_p),
+    ]
+
+
+class MotPlainHeadDesc(C.Structure):
+    """Mirror of struct MotPlainHeadDesc (include/mot.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("dtype", C.c_int32), ("norm_in", C.c_int32), ("chunk_rows", C.c_int32), ("n_rows", C.c_int64),
+        ("model_dim", C.c_int32), ("vocab", C.c_int32), ("eps", C.c_float), ("group_rows", C.c_int32), ("ignore_index", C.c_int64),
+        ("x", C.c_void_p), ("weight", C.c_void_p), ("targets", C.c_void_p), ("loss", C.c_void_p),
         ("status", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("dx", C.c_void_p), ("dW", C.c_void_p),
     ]
 
@@ -379,6 +390,13 @@ def _load() -> C.CDLL:
     lib.mot_token_head_eval.restype = C.c_int
     lib.mot_byte_head_eval.argtypes = [C.POINTER(MotByteHeadDesc), C.POINTER(MotHeadEvalOut), vp]
     lib.mot_byte_head_eval.restype = C.c_int
+    lib.mot_plain_head_desc_size.restype = C.c_size_t
+    lib.mot_plain_head_workspace_bytes.restype = C.c_size_t
+    lib.mot_plain_head_workspace_bytes.argtypes = [C.POINTER(MotPlainHeadDesc)]
+    lib.mot_plain_head_fwd.argtypes = [C.POINTER(MotPlainHeadDesc), vp]
+    lib.mot_plain_head_fwd.restype = C.c_int
+    lib.mot_plain_head_eval.argtypes = [C.POINTER(MotPlainHeadDesc), C.POINTER(MotHeadEvalOut), vp]
+    lib.mot_plain_head_eval.restype = C.c_int
     lib.mot_byte_self_attn_desc_size.restype = C.c_size_t
     for name in ("mot_byte_self_attn_saved_bytes", "mot_byte_self_attn_workspace_bytes"):
         getattr(lib, name).restype = C.c_size_t
@@ -444,6 +462,8 @@ def _load() -> C.CDLL:
         raise ImportError("MotByteHeadDesc layout mismatch between include/mot.h and _capi.py")
     if lib.mot_token_head_desc_size() != C.sizeof(MotTokenHeadDesc):
         raise ImportError("MotTokenHeadDesc layout mismatch between include/mot.h and _capi.py")
+    if lib.mot_plain_head_desc_size() != C.sizeof(MotPlainHeadDesc):
+        raise ImportError("MotPlainHeadDesc layout mismatch between include/mot.h and _capi.py")
     if lib.mot_head_eval_out_size() != C.sizeof(MotHeadEvalOut):
         raise ImportError("MotHeadEvalOut layout mismatch between include/mot.h and _capi.py")
     if lib.mot_byte_self_attn_desc_size() != C.sizeof(MotByteSelfAttnDesc):

@@ -398,6 +398,16 @@ int mot_token_head_eval(const MotTokenHeadDesc *desc, const MotHeadEvalOut *out,
     return launch_token_head_eval(desc, out, (hipStream_t)stream);
 }
 
+size_t mot_plain_head_desc_size(void) { return sizeof(MotPlainHeadDesc); }
+
+size_t mot_plain_head_workspace_bytes(const MotPlainHeadDesc *desc) { return plain_head_workspace_bytes(desc); }
+
+int mot_plain_head_fwd(const MotPlainHeadDesc *desc, mot_stream_t stream) { return launch_plain_head_fwd(desc, (hipStream_t)stream); }
+
+int mot_plain_head_eval(const MotPlainHeadDesc *desc, const MotHeadEvalOut *out, mot_stream_t stream) {
+    return launch_plain_head_eval(desc, out, (hipStream_t)stream);
+}
+
 size_t mot_byte_self_attn_desc_size(void) { return sizeof(MotByteSelfAttnDesc); }
 
 // everything that does not need the pointers: also what the two size queries run

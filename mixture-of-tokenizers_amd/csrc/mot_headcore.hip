@@ -1,6 +1,7 @@
 // mot_headcore.hip -- the kernels the output heads share (mot_headcore.hpp), each with its launcher: head_chain_rows, the
 // wave-per-row chain that closes dx behind u = G W, head_loss_parts / head_loss_final, the loss as a sum of per-row terms, and
-// head_count_parts / head_count_final, the counts of the evaluation calls, with the check of their out struct.
+// head_count_parts / head_count_final, the counts of the evaluation calls, with the check of their out struct, and
+// head_kept_parts / head_kept_final / head_loss_final_kept, the plain head's device count of kept rows and the loss divided by it.
 #include "mot_headcore.hpp"
 
 namespace mot {
@@ -92,27 +93,78 @@ int launch_head_loss(const float *term, int64_t rows, double *part, double inv_m
     return check_launch("head_loss_final");
 }
 
+// The plain head's divisor: the number of kept rows (target in [0, vocab) and not `ignore`), counted on the device in front of the
+// first chunk as integer sums laid out as the loss's, and its loss close, which divides by that count (0 / 0 = NaN at no kept row,
+// as F.cross_entropy returns).
+__global__ __launch_bounds__(kThreads) void head_kept_parts(const int64_t *__restrict__ tgt, int64_t rows, int vocab, int64_t ignore,
+                                                            long long *__restrict__ part) {
+    __shared__ long long sh[kThreads];
+    const int64_t per = (rows + gridDim.x - 1) / gridDim.x, lo = (int64_t)blockIdx.x * per, hi = lo + per < rows ? lo + per : rows;
+    long long n = 0;
+    for (int64_t i = lo + threadIdx.x; i < hi; i += kThreads) {
+        const int64_t y = tgt[i];
+        n += y >= 0 && y < vocab && y != ignore;
+    }
+    n = block_sum(n, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = n;
+}
+
+__global__ __launch_bounds__(64) void head_kept_final(const long long *__restrict__ part, int parts, long long *__restrict__ kept) {
+    if (threadIdx.x) return;
+    long long a = 0;
+    for (int p = 0; p < parts; ++p) a += part[p];
+    *kept = a;
+}
+
+int launch_head_kept(const int64_t *tgt, int64_t rows, int vocab, int64_t ignore, void *part, long long *kept, hipStream_t stream) {
+    const int parts = loss_parts(rows);
+    hipLaunchKernelGGL(head_kept_parts, dim3(parts), dim3(kThreads), 0, stream, tgt, rows, vocab, ignore, (long long *)part);
+    if (int rc = check_launch("head_kept_parts")) return rc;
+    hipLaunchKernelGGL(head_kept_final, dim3(1), dim3(64), 0, stream, (const long long *)part, parts, kept);
+    return check_launch("head_kept_final");
+}
+
+__global__ __launch_bounds__(kThreads) void head_loss_final_kept(const double *__restrict__ part, int parts, const long long *__restrict__ kept,
+                                                                 float *__restrict__ loss) {
+    __shared__ double sh[kThreads];
+    double a = 0.0;
+    for (int i = threadIdx.x; i < parts; i += kThreads) a += part[i];
+    const double s = block_sum(a, sh);
+    if (threadIdx.x == 0) *loss = (float)(s / (double)*kept);
+}
+
+int launch_head_loss_kept(const float *term, int64_t rows, double *part, const long long *kept, float *loss, hipStream_t stream) {
+    const int parts = loss_parts(rows);
+    hipLaunchKernelGGL(head_loss_parts, dim3(parts), dim3(kThreads), 0, stream, term, rows, part);
+    if (int rc = check_launch("head_loss_parts")) return rc;
+    hipLaunchKernelGGL(head_loss_final_kept, dim3(1), dim3(kThreads), 0, stream, part, parts, kept, loss);
+    return check_launch("head_loss_final_kept");
+}
+
 // The counts of an evaluation call, closed from what its row passes wrote: a row counts when its target lies in [0, vocab), it is a
 // hit when pred equals that target, and a group (`per` consecutive rows: the byte positions of a token; 1 for the token-level head)
 // is all-correct when every row of it is a hit.  Integer sums, laid out as the loss's: workgroup p sums its fixed range of groups
 // into part[3 p ..], one workgroup then sums the parts in order.
+// The plain head's form (skip_dropped, with its `ignore`; the other heads pass 0 and a value outside [0, vocab), which changes
+// nothing for them): a row that does not count neither makes nor breaks its group, and a group with no counted row is not all-correct.
 constexpr int kCountParts = kLossParts / 3;
 
 __global__ __launch_bounds__(kThreads) void head_count_parts(const int32_t *__restrict__ pred, const int64_t *__restrict__ tgt, int64_t groups, int per,
-                                                             int vocab, long long *__restrict__ part) {
+                                                             int vocab, int skip_dropped, int64_t ignore, long long *__restrict__ part) {
     __shared__ long long sh[kThreads];
     const int64_t span = (groups + gridDim.x - 1) / gridDim.x, lo = (int64_t)blockIdx.x * span, hi = lo + span < groups ? lo + span : groups;
     long long n_in = 0, n_hit = 0, n_all = 0;
     for (int64_t g = lo + threadIdx.x; g < hi; g += kThreads) {
-        bool all = true;
+        bool all = true, any = false;
         for (int k = 0; k < per; ++k) {
-            const int64_t y = tgt[g * per + k];
-            const bool in = y >= 0 && y < vocab, hit = in && (int64_t)pred[g * per + k] == y;
+            const int64_t y = tgt[g * (int64_t)per + k];
+            const bool in = y >= 0 && y < vocab && y != ignore, hit = in && (int64_t)pred[g * (int64_t)per + k] == y;
             n_in += in;
             n_hit += hit;
-            all = all && hit;
+            any = any || in;
+            all = all && (hit || (skip_dropped && !in));
         }
-        n_all += all;
+        n_all += all && (any || !skip_dropped);
     }
     n_in = block_sum(n_in, sh);
     __syncthreads();   // sh is read by every thread before the next sum overwrites it
@@ -135,9 +187,9 @@ __global__ __launch_bounds__(64) void head_count_final(const long long *__restri
 }
 
 int launch_head_eval_counts(const int32_t *pred, const int64_t *tgt, int64_t groups, int per, int vocab, void *part, int64_t *counts, int n_counts,
-                            hipStream_t stream) {
+                            hipStream_t stream, int skip_dropped, int64_t ignore) {
     const int parts = loss_parts(groups) < kCountParts ? loss_parts(groups) : kCountParts;
-    hipLaunchKernelGGL(head_count_parts, dim3(parts), dim3(kThreads), 0, stream, pred, tgt, groups, per, vocab, (long long *)part);
+    hipLaunchKernelGGL(head_count_parts, dim3(parts), dim3(kThreads), 0, stream, pred, tgt, groups, per, vocab, skip_dropped, ignore, (long long *)part);
     if (int rc = check_launch("head_count_parts")) return rc;
     hipLaunchKernelGGL(head_count_final, dim3(1), dim3(64), 0, stream, (const long long *)part, parts, counts, n_counts);
     return check_launch("head_count_final");

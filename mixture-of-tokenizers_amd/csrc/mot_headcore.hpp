@@ -1,6 +1,7 @@
-// mot_headcore.hpp -- what the output heads (mot_head.hip: the 512-row byte head, mot_tokhead.hip: the token-level head) share:
-// the factor of the row's closing rms-norm with its derivative (device inline), the chunk rule, and the launchers of
-// mot_headcore.hip: the row chain for dx and the loss's fixed-order double sum.
+// mot_headcore.hpp -- what the output heads (mot_head.hip: the 512-row byte head, mot_tokhead.hip: the token-level head,
+// mot_plainhead.hip: the plain cross-entropy head) share: the factor of the row's closing rms-norm with its derivative (device
+// inline), the chunk rule, and the launchers of mot_headcore.hip: the row chain for dx, the loss's fixed-order double sum (divided
+// by a constant or by the plain head's device count of kept rows) and the evaluation's counts.
 // Their products are launch_product_nt / _nn / _tn (mot_internal.hpp).
 #pragma once
 #include "mot_desc.hpp"   // up256, Arena: the heads' workspace carves
@@ -95,6 +96,12 @@ int head_eval_check(const char *fn, const MotHeadEvalOut *o);
 // counts[0, n_counts) = {rows with a target in [0, vocab), those with pred == target, groups of `per` consecutive rows all of which
 // are such} as integer sums per workgroup, then over the workgroups in order; part: the kLossParts doubles of the loss, free by then
 int launch_head_eval_counts(const int32_t *pred, const int64_t *tgt, int64_t groups, int per, int vocab, void *part, int64_t *counts, int n_counts,
-                            hipStream_t stream);
+                            hipStream_t stream, int skip_dropped = 0, int64_t ignore = -1);
+// the plain head's: skip_dropped = 1 takes a row with a target outside [0, vocab) or equal to `ignore` out of its group instead of
+// failing the group, and a group without a counted row is not all-correct
+// *kept = the number of targets in [0, vocab) other than `ignore`, an integer sum on the device; part: the kLossParts doubles
+int launch_head_kept(const int64_t *tgt, int64_t rows, int vocab, int64_t ignore, void *part, long long *kept, hipStream_t stream);
+// launch_head_loss with the divisor read on the device: *loss = (sum of term[0, rows)) / *kept, NaN at *kept == 0
+int launch_head_loss_kept(const float *term, int64_t rows, double *part, const long long *kept, float *loss, hipStream_t stream);
 
 }  // namespace mot

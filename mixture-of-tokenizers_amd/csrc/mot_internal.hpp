@@ -142,6 +142,10 @@ int token_head_check(const MotTokenHeadDesc *d);
 size_t token_head_workspace_bytes(const MotTokenHeadDesc &d);
 int launch_token_head_fwd(const MotTokenHeadDesc &d, hipStream_t stream);
 int launch_token_head_eval(const MotTokenHeadDesc *d, const MotHeadEvalOut *out, hipStream_t stream);   // likewise
+// the plain cross-entropy head (mot_plainhead.hip): its own validation, every refusal before any HIP call
+size_t plain_head_workspace_bytes(const MotPlainHeadDesc *d);   // 0 for a descriptor the call would refuse
+int launch_plain_head_fwd(const MotPlainHeadDesc *d, hipStream_t stream);
+int launch_plain_head_eval(const MotPlainHeadDesc *d, const MotHeadEvalOut *out, hipStream_t stream);
 // byte self-attention of the concat mixin (mot_bsa.hip); the descriptor is validated in mot_capi.hip
 size_t byte_self_attn_saved_bytes(const MotByteSelfAttnDesc &d);
 size_t byte_self_attn_workspace_bytes(const MotByteSelfAttnDesc &d);

@@ -20,18 +20,12 @@
 // mot_token_head_eval is the loss call without gradients whose row pass (the EVAL instantiations of tokhead_rows) also writes every
 // row's loss term, the class of its largest stored logit and the number of stored logits above the target's (include/mot.h).
 // This unit holds tokhead_rows, the checks and the carve; row_scale, the products, the chunk rule, the chain and the loss's sum are
-// the heads' shared ones (mot_headcore.hpp).
-#include "mot_headcore.hpp"
+// the heads' shared ones (mot_headcore.hpp); the vector of logits, the workgroup's sums and the evaluation's share of a vector are
+// shared with the plain head's row pass (mot_headrows.hpp).
+#include "mot_headrows.hpp"
 
 namespace mot {
 namespace {
-
-constexpr int kMinV = 128, kMaxV = 262144, kMaxD = 2048;
-constexpr int64_t kChunkBytes = 512ll << 20;   // the library's chunk: logits and u of a chunk stay below this
-constexpr int kRowThreads = 1024;              // workgroup of the row pass at wide rows; kRowThreadsSmall when a row has <= 1024 vectors
-constexpr int kRowThreadsSmall = 256;
-constexpr int kRowWavesMax = kRowThreads / 64;
-constexpr int kRegV = 65536;                  // widest row the row pass keeps in registers between its two uses
 
 // z = cap(l) and dz/dl
 template <int CAP>
@@ -48,43 +42,6 @@ __device__ __forceinline__ float softcap(float l, float &dz) {
 }
 template <int CAP>
 __device__ __forceinline__ float softcap_max() { return CAP == MOT_SOFTCAP_SIGMOID30 ? 30.f : 15.f; }
-
-// 16 bytes of a row of logits: 4 fp32 or 8 bf16
-template <typename T>
-struct LogitVec;
-template <>
-struct LogitVec<float> {
-    static constexpr int N = 4;
-    float4 q;
-    __device__ __forceinline__ float get(int e) const { return e == 0 ? q.x : e == 1 ? q.y : e == 2 ? q.z : q.w; }
-    __device__ __forceinline__ void put(const float *v) { q = make_float4(v[0], v[1], v[2], v[3]); }
-};
-template <>
-struct LogitVec<__bf16> {
-    static constexpr int N = 8;
-    uint4 q;
-    __device__ __forceinline__ float get(int e) const {
-        const uint32_t w = e < 2 ? q.x : e < 4 ? q.y : e < 6 ? q.z : q.w;
-        return __uint_as_float((e & 1) ? (w & 0xffff0000u) : (w << 16));
-    }
-    static __device__ __forceinline__ uint32_t pack(float lo, float hi) {   // two roundings to nearest even
-        const __bf16 a = (__bf16)lo, b = (__bf16)hi;
-        return (uint32_t)__builtin_bit_cast(unsigned short, a) | ((uint32_t)__builtin_bit_cast(unsigned short, b) << 16);
-    }
-    __device__ __forceinline__ void put(const float *v) { q = make_uint4(pack(v[0], v[1]), pack(v[2], v[3]), pack(v[4], v[5]), pack(v[6], v[7])); }
-};
-
-// sum over the workgroup in a fixed order: the waves' DPP sums, then the waves in index order.  `sh` holds one float per wave and is
-// used by one sum only, so a single barrier suffices.
-__device__ __forceinline__ float rows_block_sum(float v, float *sh) {
-    const int nw = blockDim.x >> 6;
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float s = 0.f;
-    for (int w = 0; w < nw; ++w) s += sh[w];
-    return s;
-}
 
 // sum exp(z - zmax) over one vector, and z[y] when the vector holds class y (ey: its element there, else -1)
 template <typename T, int CAP>
@@ -112,21 +69,6 @@ __device__ __forceinline__ void vec_grad(LogitVec<T> &a, float c, float lse, flo
         g[e] = scale * dz * (p - (e == ey ? 1.f : 0.f));
     }
     a.put(g);
-}
-
-// the evaluation's share of one vector whose first class is cls0, on the logits as stored: the largest so far with its class (a
-// thread meets its classes in ascending order, so `>` keeps the lowest class of equal logits) and the count of those above sy
-template <typename T>
-__device__ __forceinline__ void vec_top(const LogitVec<T> &a, int cls0, float sy, float &best, int &best_cls, int &above) {
-#pragma unroll
-    for (int e = 0; e < LogitVec<T>::N; ++e) {
-        const float s = a.get(e);
-        if (s > best) {
-            best = s;
-            best_cls = cls0 + e;
-        }
-        above += s > sy ? 1 : 0;
-    }
 }
 
 // One workgroup per row of the chunk.  NV > 0: the row's vectors (nvec = V / N <= NV * blockDim.x) stay in registers between the
@@ -261,9 +203,8 @@ TokWs tok_ws(const TokGeom &g) {
 template <typename T, int CAP, bool GRAD, bool EVAL = false>
 int launch_rows(T *S, const TokGeom &g, const T *x, const int64_t *tgt, int64_t n, float inv_n, float *term, float *row_stats, uint32_t *status,
                 hipStream_t stream, HeadEvalRows ev = {}) {
-    const int nvec = g.V / LogitVec<T>::N;
-    const int nt = nvec <= 4 * kRowThreadsSmall ? kRowThreadsSmall : kRowThreads;
-    const int nv = (nvec + nt - 1) / nt;
+    int nt, nv;
+    rows_geometry<T>(g.V, nt, nv);
 #define MOT_TOKHEAD_ROWS(NV)                                                                                                                              \
     hipLaunchKernelGGL((tokhead_rows<T, CAP, NV, GRAD, EVAL>), dim3((unsigned)n), dim3(nt), 0, stream, S, g.V, x, g.K, g.norm_in, g.eps, tgt, n, inv_n, \
                        term, row_stats, g.rows, status, ev)

@@ -1332,6 +1332,116 @@ def byte_head_eval(x: torch.Tensor, weight: torch.Tensor, targets: torch.Tensor,
 
 
 # ----------------------------------------------------------------------------------------------
+# plain cross-entropy head: lm_head + cross_entropy without a softcap, with ignore_index and the mean over the kept targets,
+# mathblations/model.py:337-338 + main.py:294-303 (evaluation :164-187), inference/inference.py:349-359
+# ----------------------------------------------------------------------------------------------
+def _plain_head_operands(x, weight, targets):
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"plain_head_loss: x must be float32 or bfloat16, got {x.dtype}")
+    if weight.ndim != 2 or weight.shape[1] != x.shape[-1]:
+        raise ValueError(f"plain_head_loss: weight must be (vocab, {x.shape[-1]}), got {tuple(weight.shape)}")
+    if targets.dtype not in (torch.int64, torch.int32):
+        raise TypeError(f"plain_head_loss: targets must be int64 or int32, got {targets.dtype}")
+    capi.require_device(x, weight, targets)
+    return _head_operands("plain_head_loss", x, weight, targets.to(torch.int64), 1, "rows")
+
+
+def _plain_head_desc(x2, w, t, norm_in, ignore_index, chunk_rows, group_rows=0):
+    dev = capi.require_device(x2, w, t)
+    d = capi.MotPlainHeadDesc()
+    d.struct_size = C.sizeof(capi.MotPlainHeadDesc)
+    d.dtype, d.norm_in, d.chunk_rows, d.group_rows = capi.dtype_code(x2.dtype), int(bool(norm_in)), int(chunk_rows or 0), int(group_rows or 0)
+    d.n_rows, d.model_dim, d.vocab, d.eps, d.ignore_index = x2.shape[0], x2.shape[1], w.shape[0], 0.0, int(ignore_index)
+    d.x, d.weight, d.targets = capi.ptr(x2), capi.ptr(w), capi.ptr(t)
+    return d, dev
+
+
+def _plain_head_call(x2, w, t, norm_in, ignore_index, chunk_rows, dx, dw):
+    """One mot_plain_head_fwd: the loss, and the gradients for grad_loss = 1 into dx / dw where given."""
+    d, dev = _plain_head_desc(x2, w, t, norm_in, ignore_index, chunk_rows)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    d.loss, d.dx, d.dW = capi.ptr(loss), capi.ptr(dx), capi.ptr(dw)
+    _launch(dev, d, capi.lib.mot_plain_head_fwd, ws_bytes=capi.lib.mot_plain_head_workspace_bytes)
+    return loss
+
+
+class _PlainHeadFn(torch.autograd.Function):
+    """forward = one mot_plain_head_fwd that also forms dx and the fp32 dW for grad_loss = 1; backward multiplies them by the incoming
+    grad_loss on the device, out of place (a retained graph runs backward again on the same saved gradients)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, targets, norm_in, ignore_index, chunk_rows):
+        x2, w, t = _plain_head_operands(x, weight, targets)
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        dx = torch.empty_like(x2) if need_x else None
+        dw = torch.empty(w.shape, dtype=torch.float32, device=x2.device) if need_w else None
+        loss = _plain_head_call(x2, w, t, norm_in, ignore_index, chunk_rows, dx, dw)
+        ctx.save_for_backward(dx, dw)
+        ctx.cfg = (x.shape, weight.dtype)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss):
+        dx, dw = ctx.saved_tensors
+        xshape, wdtype = ctx.cfg
+        go = grad_loss.detach().reshape(1, 1).float()
+        gx = gw = None
+        if dx is not None:   # one elementwise pass: fp32 factor, fp32 product, one rounding on store, no fp32 copy of dx
+            gx = torch.mul(dx, go, out=torch.empty_like(dx)).reshape(xshape)
+        if dw is not None:
+            gw = torch.mul(dw, go, out=torch.empty(dw.shape, dtype=wdtype, device=dw.device))
+        return gx, gw, None, None, None, None
+
+
+@torch.compiler.disable
+def plain_head_loss(x: torch.Tensor, weight: torch.Tensor, targets: torch.Tensor, *, norm_in: bool = True, ignore_index: int = -100,
+                    chunk_rows: int | None = None) -> torch.Tensor:
+    """The plain cross-entropy head, fused: F.cross_entropy(F.linear(norm(x), weight).float(), targets, ignore_index=ignore_index)
+    as an fp32 scalar, with no softcap and the mean over the kept targets: mathblations/model.py:337-338 with main.py:294-303
+    (norm_in=True, the scored window marked with window_targets) and inference/inference.py:349-359 (norm_in=False, the shift done by
+    the caller).  x (..., model_dim) float32 or bfloat16; weight (vocab, model_dim), cast once to x's dtype; targets int64 or int32
+    (...).  No logits tensor of rows x vocab exists: the rows run in chunks (chunk_rows rows, a multiple of 32; None: the library's
+    choice).  Differentiable in x and weight (the weight's gradient in the weight's dtype, summed in fp32): with grad mode on, the
+    one call forms both gradients beside the loss; under no_grad it is the loss alone, with the same bits.
+    A target equal to ignore_index drops its row; any other target outside [0, vocab) drops it too and raises the status bit that
+    check_status() reports.  The number of kept targets is counted on the device (the call captures into a hipGraph); with none kept
+    the loss is NaN, as torch's, and the gradients are exactly zero."""
+    if not torch.is_grad_enabled() or not (x.requires_grad or weight.requires_grad):
+        x2, w, t = _plain_head_operands(x, weight, targets)
+        return _plain_head_call(x2, w, t, norm_in, ignore_index, chunk_rows, None, None)
+    return _PlainHeadFn.apply(x, weight, targets, bool(norm_in), int(ignore_index), chunk_rows)
+
+
+@torch.compiler.disable
+@torch.no_grad()
+def plain_head_eval(x: torch.Tensor, weight: torch.Tensor, targets: torch.Tensor, *, norm_in: bool = True, ignore_index: int = -100,
+                    chunk_rows: int | None = None, group_rows: int = 0) -> HeadEval:
+    """The plain head for evaluation (mathblations/main.py:164-187): the pass of plain_head_loss under no_grad over the same chunks,
+    which also writes every row's loss, top-1 prediction and target rank (HeadEval) without any tensor of rows x vocab.
+    HeadEval.loss has the bits of plain_head_loss.  A dropped row (target ignore_index or out of range) has row_loss 0 and rank -1;
+    its pred is still written.  counts = [kept rows, kept rows with pred == target]; with group_rows > 0 (the sequence length; it
+    must divide the rows) a third entry counts the groups of group_rows consecutive rows that have a kept row and whose kept rows are
+    all right, full_correct of main.py:183-187.  Forms no gradients in any grad mode."""
+    x2, w, t = _plain_head_operands(x, weight, targets)
+    d, dev = _plain_head_desc(x2, w, t, norm_in, ignore_index, chunk_rows, group_rows)
+    return _head_eval_call(dev, d, capi.lib.mot_plain_head_eval, capi.lib.mot_plain_head_workspace_bytes, targets.shape, 3 if group_rows else 2)
+
+
+def window_targets(targets: torch.Tensor, ranges, ignore_index: int = -100) -> torch.Tensor:
+    """targets (B, T) with everything outside each row's [start, end) set to ignore_index: the positions slice_logits_and_targets
+    (mathblations/data.py:262-278) keeps for y_indices = ranges, (B, 2) as a tensor or a sequence of (start, end).  The mean over the
+    kept targets of plain_head_loss on the result is the reference's cross_entropy over the sliced rows.  Plain torch on the targets'
+    device, no loop over rows."""
+    if targets.ndim != 2:
+        raise ValueError(f"window_targets: targets must be (B, T), got {tuple(targets.shape)}")
+    r = torch.as_tensor(ranges, device=targets.device).reshape(targets.shape[0], 2)
+    pos = torch.arange(targets.shape[1], device=targets.device)
+    inside = (pos >= r[:, :1]) & (pos < r[:, 1:])
+    return torch.where(inside, targets, torch.full_like(targets, ignore_index))
+
+
+# ----------------------------------------------------------------------------------------------
 # byte self-attention in front of the concat mixin: ByteSelfAttn with use_byte_self_attn, train_gpt.py:382-418
 # ----------------------------------------------------------------------------------------------
 def _byte_self_attn_desc(x3, qkv_w, proj_w, lam, cos, sin, bpt, window, block_causal, out, saved):

@@ -465,6 +465,32 @@ class ByteMixout(nn.Module):  # train_gpt.py:530-542
         return F_mot.byte_head_eval(x, lm_head.weight, target_seq, method=self.method, bytes_per_token=self.bpt, n_layer_out=self.n_layer_out)
 
 
+class PlainLMHead(nn.Module):
+    """The output end of the mathblations model (model.py:337-338) and of the inference wrapper (inference.py:349-359) on the fused
+    plain head: holds the model's own `lm_head` (a bias-free nn.Linear or CastedLinear, no new parameter), so a weight tied to the
+    embedding (wte.weight = lm_head.weight, model.py:317) stays tied and receives both gradients.
+    loss(x, targets) = F.cross_entropy(lm_head(norm(x)).float(), targets, ignore_index=ignore_index) without a logits tensor;
+    evaluate(x, targets, group_rows) is main.py:164-187: HeadEval with the counts of kept rows, of right ones and, with group_rows
+    (the sequence length), of sequences whose kept rows are all right.  norm_in=False takes x as already normed (inference)."""
+
+    def __init__(self, lm_head: nn.Module, norm_in: bool = True, ignore_index: int = -100):
+        super().__init__()
+        if getattr(lm_head, "bias", None) is not None:
+            raise ValueError("PlainLMHead: lm_head must have no bias (model.py:316 builds it with bias=False)")
+        self.lm_head = lm_head
+        self.norm_in = bool(norm_in)
+        self.ignore_index = int(ignore_index)
+
+    def forward(self, x: Tensor) -> Tensor:   # the logits in plain torch ops, for generation
+        return F.linear(norm(x) if self.norm_in else x, self.lm_head.weight.type_as(x))
+
+    def loss(self, x: Tensor, targets: Tensor) -> Tensor:
+        return F_mot.plain_head_loss(x, self.lm_head.weight, targets, norm_in=self.norm_in, ignore_index=self.ignore_index)
+
+    def evaluate(self, x: Tensor, targets: Tensor, group_rows: int = 0) -> "F_mot.HeadEval":
+        return F_mot.plain_head_eval(x, self.lm_head.weight, targets, norm_in=self.norm_in, ignore_index=self.ignore_index, group_rows=group_rows)
+
+
 class FusedFrontEnd(nn.Module):
     """Loader + embed + mixin in one library call: tokens (B,T) -> x (B,T,model_dim), with the
     token->byte gather and the pull done on the device inside that call (index kernels into scratch,
