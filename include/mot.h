@@ -50,6 +50,7 @@ typedef enum MotStatus {
 #define MOT_STATUS_TOKEN_OOR 1u /* token id outside [0, tok_rows) / [0, ttb_rows) */
 #define MOT_STATUS_BYTE_OOR 2u  /* byte id outside [0, byte_rows)                 */
 #define MOT_STATUS_TARGET_OOR 4u /* target outside [0, vocab) (mot_byte_head_*, mot_token_head_*, mot_plain_head_*) */
+#define MOT_STATUS_KEPT_OVERFLOW 8u /* more kept rows than max_kept (mot_plain_head_compact_*): nothing was scored */
 
 typedef enum MotPullDir {
     MOT_PULL_NONE = 0,
@@ -687,8 +688,8 @@ int mot_byte_head_eval(const MotByteHeadDesc *desc /* host */, const MotHeadEval
  * and with group_rows > 0 a third entry: the groups of group_rows consecutive rows (a sequence) that have at least one kept row and
  * whose kept rows are ALL right, full_correct of main.py:183-187.  Dropped rows count neither for nor against their group (the byte
  * head's third count differs there).  group_rows is read by the evaluation alone.
- * Not built: label smoothing; the 14-class digit head of digit_mixout_method != "noop"; compaction of the kept rows in front of
- * the products (every row's logits are formed, kept or not).
+ * These two calls form the logits of every row, kept or not; mot_plain_head_compact_* below form them for the kept rows alone.
+ * Not built: label smoothing; the 14-class digit head of digit_mixout_method != "noop".
  */
 typedef struct MotPlainHeadDesc {
     uint32_t struct_size; /* sizeof(MotPlainHeadDesc) */
@@ -716,6 +717,52 @@ size_t mot_plain_head_desc_size(void);
 size_t mot_plain_head_workspace_bytes(const MotPlainHeadDesc *desc /* host */);
 int mot_plain_head_fwd(const MotPlainHeadDesc *desc /* host */, mot_stream_t stream);
 int mot_plain_head_eval(const MotPlainHeadDesc *desc /* host */, const MotHeadEvalOut *out /* host */, mot_stream_t stream);
+
+/*
+ * The plain head with the kept rows compacted in front of the products: the time follows the number of scored positions, not
+ * n_rows.  `desc` and everything stated above hold (kept rows, `kept`, loss, G, dx, dW, MOT_STATUS_TARGET_OOR, NaN at kept == 0,
+ * dtypes, shape limits); the count of kept rows still lives on the device alone, so the caller passes a bound it knows on the host
+ * (the window lengths, the label mask's shape): max_kept.
+ *   cap = min(max_kept, n_rows).  The kept rows are taken in ascending row order into slots 0 .. kept-1 by an index pass over the
+ *   targets (per-workgroup counts, a scan of the counts, per-workgroup writes: three launches, no workgroup waits on another).
+ *   Slots kept .. cap-1 are padding: zero rows with an ignored target, which add nothing to the loss, have G = 0 and add exactly
+ *   nothing to dW.  Per chunk the slots' rows of x and their targets are gathered, the products and the row pass run per slot,
+ *   and the row chain writes each valid slot's gradient straight into its row of dx.
+ *   With norm_in the norm is applied in the gather: the slot's row is h = c_r x_r, rounded to dtype as F.rms_norm's output is in
+ *   front of lm_head, and l = h W^T is stored per chunk as above.  The same l, G, dx and dW mathematically; in MOT_BF16 the
+ *   logits carry the reference's own two roundings (norm(x), then the product), where mot_plain_head_fwd scales the stored
+ *   product of the un-normed row in fp32.  pred and rank of the evaluation are taken on the stored h W^T.
+ *   The chunk rule runs over cap: chunk_rows = 0 is the rule above with cap in place of n_rows, a given chunk_rows is clipped to
+ *   cap.  The number of chunks, every grid and the workspace depend on host values only, so whole padding chunks still run their
+ *   products on zero rows: a tight bound is the caller's job.
+ *   loss: the fixed-order double sum over the slots' terms divided by the device count; the same bits on every run, NOT necessarily
+ *   those of mot_plain_head_fwd (the sum is grouped differently and a chunk of another height may take another product route).
+ *   dx [n_rows, model_dim]: every element is written by the call, a kept row's gradient once, +0 in every element of a dropped row
+ *   (by a kernel, no memset node).  dW = G^T x over the gathered rows, zeroed by the call, summed with fp32 atomics as above.
+ *   kept > cap is a caller error: MOT_STATUS_KEPT_OVERFLOW is ORed into `status` and the call behaves as if nothing were kept
+ *   (loss NaN, dx and dW exactly zero); it never scores only the first cap rows.
+ * mot_plain_head_compact_eval: row_loss, pred and rank stay per original row.  A kept row gets what mot_plain_head_eval writes; a
+ * dropped row gets row_loss = 0, rank = -1 and pred = -1 (its logits are never formed: the one difference from mot_plain_head_eval,
+ * which still writes a dropped row's pred).  counts as above, group_rows included.  desc->loss has the bits of
+ * mot_plain_head_compact_fwd without gradients.
+ * No allocation, no host read, no memset or memcpy node: the calls capture into a hipGraph, and a replay follows targets changed in
+ * place, a change of kept in either direction and into and out of overflow included.
+ * Checked before any HIP call, with a message that starts with the function's name: everything the calls above refuse, with the same
+ * codes; a null or wrongly sized MotPlainHeadCompact or reserved != 0 -> MOT_EINVAL; max_kept <= 0 -> MOT_ESHAPE.  max_kept > n_rows
+ * is clipped.  The workspace query returns 0 for what the calls refuse; it is at least mot_plain_head_workspace_bytes(desc) at
+ * max_kept >= n_rows and shrinks with max_kept.
+ */
+typedef struct MotPlainHeadCompact {
+    uint32_t struct_size; /* sizeof(MotPlainHeadCompact) */
+    uint32_t reserved;    /* 0 */
+    int64_t max_kept;     /* host bound on the number of kept rows; > 0; clipped to n_rows */
+} MotPlainHeadCompact;
+
+size_t mot_plain_head_compact_size(void);
+size_t mot_plain_head_compact_workspace_bytes(const MotPlainHeadDesc *desc /* host */, const MotPlainHeadCompact *compact /* host */);
+int mot_plain_head_compact_fwd(const MotPlainHeadDesc *desc /* host */, const MotPlainHeadCompact *compact /* host */, mot_stream_t stream);
+int mot_plain_head_compact_eval(const MotPlainHeadDesc *desc /* host */, const MotPlainHeadCompact *compact /* host */,
+                                const MotHeadEvalOut *out /* host */, mot_stream_t stream);
 
 /*
  * Byte self-attention in front of the concat mixin, forward: replaces ByteSelfAttn.forward with use_byte_self_attn on

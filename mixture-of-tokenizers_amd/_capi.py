@@ -25,7 +25,7 @@ IS_DEV_LIB = _dev_lib is not None
 
 # ---- enums of include/mot.h
 MOT_OK, MOT_EINVAL, MOT_ESHAPE, MOT_EUNSUPPORTED, MOT_EHIP, MOT_EWORKSPACE = 0, -1, -2, -3, -4, -5
-STATUS_TOKEN_OOR, STATUS_BYTE_OOR, STATUS_TARGET_OOR = 1, 2, 4
+STATUS_TOKEN_OOR, STATUS_BYTE_OOR, STATUS_TARGET_OOR, STATUS_KEPT_OVERFLOW = 1, 2, 4, 8
 PULL_NONE, PULL_LEFT, PULL_RIGHT = 0, 1, 2
 MIX_NOOP, MIX_SUM, MIX_MEAN, MIX_CONCAT_LINEAR, MIX_CONCAT = 0, 1, 2, 3, 4
 IDS_NONE, IDS_FROM_TTB, IDS_GIVEN = 0, 1, 2
@@ -61,6 +61,7 @@ EXPORTS = (
     "mot_token_head_desc_size", "mot_token_head_workspace_bytes", "mot_token_head_fwd",
     "mot_head_eval_out_size", "mot_token_head_eval", "mot_byte_head_eval",
     "mot_plain_head_desc_size", "mot_plain_head_workspace_bytes", "mot_plain_head_fwd", "mot_plain_head_eval",
+    "mot_plain_head_compact_size", "mot_plain_head_compact_workspace_bytes", "mot_plain_head_compact_fwd", "mot_plain_head_compact_eval",
     "mot_byte_self_attn_desc_size", "mot_byte_self_attn_saved_bytes", "mot_byte_self_attn_workspace_bytes",
     "mot_byte_self_attn_fwd", "mot_byte_self_attn_bwd",
     "mot_byte_fc_mix_desc_size", "mot_byte_fc_mix_workspace_bytes", "mot_byte_fc_mix_bwd_workspace_bytes",
@@ -180,6 +181,11 @@ class MotPlainHeadDesc(C.Structure):
         ("x", C.c_void_p), ("weight", C.c_void_p), ("targets", C.c_void_p), ("loss", C.c_void_p),
         ("status", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("dx", C.c_void_p), ("dW", C.c_void_p),
     ]
+
+
+class MotPlainHeadCompact(C.Structure):
+    """Mirror of struct MotPlainHeadCompact (include/mot.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("max_kept", C.c_int64)]
 
 
 class MotHeadEvalOut(C.Structure):
@@ -397,6 +403,13 @@ def _load() -> C.CDLL:
     lib.mot_plain_head_fwd.restype = C.c_int
     lib.mot_plain_head_eval.argtypes = [C.POINTER(MotPlainHeadDesc), C.POINTER(MotHeadEvalOut), vp]
     lib.mot_plain_head_eval.restype = C.c_int
+    lib.mot_plain_head_compact_size.restype = C.c_size_t
+    lib.mot_plain_head_compact_workspace_bytes.restype = C.c_size_t
+    lib.mot_plain_head_compact_workspace_bytes.argtypes = [C.POINTER(MotPlainHeadDesc), C.POINTER(MotPlainHeadCompact)]
+    lib.mot_plain_head_compact_fwd.argtypes = [C.POINTER(MotPlainHeadDesc), C.POINTER(MotPlainHeadCompact), vp]
+    lib.mot_plain_head_compact_fwd.restype = C.c_int
+    lib.mot_plain_head_compact_eval.argtypes = [C.POINTER(MotPlainHeadDesc), C.POINTER(MotPlainHeadCompact), C.POINTER(MotHeadEvalOut), vp]
+    lib.mot_plain_head_compact_eval.restype = C.c_int
     lib.mot_byte_self_attn_desc_size.restype = C.c_size_t
     for name in ("mot_byte_self_attn_saved_bytes", "mot_byte_self_attn_workspace_bytes"):
         getattr(lib, name).restype = C.c_size_t
@@ -464,6 +477,8 @@ def _load() -> C.CDLL:
         raise ImportError("MotTokenHeadDesc layout mismatch between include/mot.h and _capi.py")
     if lib.mot_plain_head_desc_size() != C.sizeof(MotPlainHeadDesc):
         raise ImportError("MotPlainHeadDesc layout mismatch between include/mot.h and _capi.py")
+    if lib.mot_plain_head_compact_size() != C.sizeof(MotPlainHeadCompact):
+        raise ImportError("MotPlainHeadCompact layout mismatch between include/mot.h and _capi.py")
     if lib.mot_head_eval_out_size() != C.sizeof(MotHeadEvalOut):
         raise ImportError("MotHeadEvalOut layout mismatch between include/mot.h and _capi.py")
     if lib.mot_byte_self_attn_desc_size() != C.sizeof(MotByteSelfAttnDesc):
@@ -532,7 +547,10 @@ def check_status(device=None) -> None:
             w.zero_()
             what = [n for bit, n in ((STATUS_TOKEN_OOR, "token id"), (STATUS_BYTE_OOR, "byte id"), (STATUS_TARGET_OOR, "byte target"))
                     if v & bit]
-            raise IndexError(f"index out of range in self ({' and '.join(what)} out of range)")
+            said = [f"{' and '.join(what)} out of range"] if what else []
+            if v & STATUS_KEPT_OVERFLOW:   # the compacted plain head: a caller error, nothing was scored
+                said.append("kept overflow: more kept rows than max_kept")
+            raise IndexError(f"index out of range in self ({'; '.join(said)})")
 
 
 def after_call(device: torch.device) -> None:

@@ -408,6 +408,20 @@ int mot_plain_head_eval(const MotPlainHeadDesc *desc, const MotHeadEvalOut *out,
     return launch_plain_head_eval(desc, out, (hipStream_t)stream);
 }
 
+size_t mot_plain_head_compact_size(void) { return sizeof(MotPlainHeadCompact); }
+
+size_t mot_plain_head_compact_workspace_bytes(const MotPlainHeadDesc *desc, const MotPlainHeadCompact *compact) {
+    return plain_head_compact_workspace_bytes(desc, compact);
+}
+
+int mot_plain_head_compact_fwd(const MotPlainHeadDesc *desc, const MotPlainHeadCompact *compact, mot_stream_t stream) {
+    return launch_plain_head_compact_fwd(desc, compact, (hipStream_t)stream);
+}
+
+int mot_plain_head_compact_eval(const MotPlainHeadDesc *desc, const MotPlainHeadCompact *compact, const MotHeadEvalOut *out, mot_stream_t stream) {
+    return launch_plain_head_compact_eval(desc, compact, out, (hipStream_t)stream);
+}
+
 size_t mot_byte_self_attn_desc_size(void) { return sizeof(MotByteSelfAttnDesc); }
 
 // everything that does not need the pointers: also what the two size queries run

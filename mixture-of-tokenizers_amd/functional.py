@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import numbers
 import os
 from dataclasses import dataclass
 from typing import NamedTuple
@@ -1271,7 +1272,8 @@ def token_head_loss(x: torch.Tensor, weight: torch.Tensor, targets: torch.Tensor
 class HeadEval(NamedTuple):
     """What token_head_eval / byte_head_eval return.  A row is a token (token-level head) or a byte position (byte head), in the
     targets' shape.  loss: the fp32 scalar of the loss call, the same bits; row_loss fp32: lse(z) - z[target], 0 for a target out of
-    range; pred int32: the class of the largest logit, the lowest on ties; rank int32: the number of classes whose logit is strictly
+    range; pred int32: the class of the largest logit, the lowest on ties (-1 for a dropped row of plain_head_eval with max_kept: its
+    logits are never formed); rank int32: the number of classes whose logit is strictly
     above the target's, -1 for a target out of range; counts int64 on the device: [rows with a target in range, those with
     pred == target], and for the byte head a third, the tokens all of whose byte predictions equal their targets."""
     loss: torch.Tensor
@@ -1281,8 +1283,9 @@ class HeadEval(NamedTuple):
     counts: torch.Tensor
 
 
-def _head_eval_call(dev, d, fn, ws_bytes, shape, n_counts):
-    """The tail of both evaluation calls: the outputs in the targets' shape, the out struct, the launch."""
+def _head_eval_call(dev, d, fn, ws_bytes, shape, n_counts, *pre):
+    """The tail of the evaluation calls: the outputs in the targets' shape, the out struct, the launch (`pre`: what the call takes
+    between the descriptor and the out struct)."""
     n = math.prod(shape)
     row_loss = torch.empty(n, dtype=torch.float32, device=dev)
     pred = torch.empty(n, dtype=torch.int32, device=dev)
@@ -1293,7 +1296,7 @@ def _head_eval_call(dev, d, fn, ws_bytes, shape, n_counts):
     o = capi.MotHeadEvalOut()
     o.struct_size = C.sizeof(capi.MotHeadEvalOut)
     o.row_loss, o.pred, o.rank, o.counts = capi.ptr(row_loss), capi.ptr(pred), capi.ptr(rank), capi.ptr(counts)
-    _launch(dev, d, fn, C.byref(o), ws_bytes=ws_bytes)
+    _launch(dev, d, fn, *pre, C.byref(o), ws_bytes=ws_bytes)
     return HeadEval(loss, row_loss.reshape(shape), pred.reshape(shape), rank.reshape(shape), counts)
 
 
@@ -1356,26 +1359,48 @@ def _plain_head_desc(x2, w, t, norm_in, ignore_index, chunk_rows, group_rows=0):
     return d, dev
 
 
-def _plain_head_call(x2, w, t, norm_in, ignore_index, chunk_rows, dx, dw):
-    """One mot_plain_head_fwd: the loss, and the gradients for grad_loss = 1 into dx / dw where given."""
+def _max_kept_arg(fn, max_kept):
+    """max_kept of the plain head's calls: None (every row's logits are formed) or a positive int, checked before anything else."""
+    if max_kept is None:
+        return None
+    if isinstance(max_kept, bool) or not isinstance(max_kept, numbers.Integral) or max_kept <= 0:
+        raise ValueError(f"{fn}: max_kept must be None or a positive int (a host bound on the kept rows), got {max_kept!r}")
+    return int(max_kept)
+
+
+def _plain_head_compact(max_kept):
+    """The MotPlainHeadCompact of a call with max_kept, and the workspace query bound to it."""
+    c = capi.MotPlainHeadCompact()
+    c.struct_size, c.reserved, c.max_kept = C.sizeof(capi.MotPlainHeadCompact), 0, max_kept
+    return c, lambda p: capi.lib.mot_plain_head_compact_workspace_bytes(p, C.byref(c))
+
+
+def _plain_head_call(x2, w, t, norm_in, ignore_index, chunk_rows, dx, dw, max_kept=None):
+    """One mot_plain_head_fwd (max_kept None) or mot_plain_head_compact_fwd: the loss, and the gradients for grad_loss = 1 into
+    dx / dw where given."""
     d, dev = _plain_head_desc(x2, w, t, norm_in, ignore_index, chunk_rows)
     loss = torch.empty((), dtype=torch.float32, device=dev)
     d.loss, d.dx, d.dW = capi.ptr(loss), capi.ptr(dx), capi.ptr(dw)
-    _launch(dev, d, capi.lib.mot_plain_head_fwd, ws_bytes=capi.lib.mot_plain_head_workspace_bytes)
+    if max_kept is None:
+        _launch(dev, d, capi.lib.mot_plain_head_fwd, ws_bytes=capi.lib.mot_plain_head_workspace_bytes)
+    else:
+        c, ws_bytes = _plain_head_compact(max_kept)
+        _launch(dev, d, capi.lib.mot_plain_head_compact_fwd, C.byref(c), ws_bytes=ws_bytes)
     return loss
 
 
 class _PlainHeadFn(torch.autograd.Function):
-    """forward = one mot_plain_head_fwd that also forms dx and the fp32 dW for grad_loss = 1; backward multiplies them by the incoming
-    grad_loss on the device, out of place (a retained graph runs backward again on the same saved gradients)."""
+    """forward = one mot_plain_head_fwd (mot_plain_head_compact_fwd with max_kept) that also forms dx and the fp32 dW for
+    grad_loss = 1; backward multiplies them by the incoming grad_loss on the device, out of place (a retained graph runs backward
+    again on the same saved gradients)."""
 
     @staticmethod
-    def forward(ctx, x, weight, targets, norm_in, ignore_index, chunk_rows):
+    def forward(ctx, x, weight, targets, norm_in, ignore_index, chunk_rows, max_kept=None):
         x2, w, t = _plain_head_operands(x, weight, targets)
         need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         dx = torch.empty_like(x2) if need_x else None
         dw = torch.empty(w.shape, dtype=torch.float32, device=x2.device) if need_w else None
-        loss = _plain_head_call(x2, w, t, norm_in, ignore_index, chunk_rows, dx, dw)
+        loss = _plain_head_call(x2, w, t, norm_in, ignore_index, chunk_rows, dx, dw, max_kept)
         ctx.save_for_backward(dx, dw)
         ctx.cfg = (x.shape, weight.dtype)
         return loss
@@ -1391,12 +1416,12 @@ class _PlainHeadFn(torch.autograd.Function):
             gx = torch.mul(dx, go, out=torch.empty_like(dx)).reshape(xshape)
         if dw is not None:
             gw = torch.mul(dw, go, out=torch.empty(dw.shape, dtype=wdtype, device=dw.device))
-        return gx, gw, None, None, None, None
+        return gx, gw, None, None, None, None, None
 
 
 @torch.compiler.disable
 def plain_head_loss(x: torch.Tensor, weight: torch.Tensor, targets: torch.Tensor, *, norm_in: bool = True, ignore_index: int = -100,
-                    chunk_rows: int | None = None) -> torch.Tensor:
+                    chunk_rows: int | None = None, max_kept: int | None = None) -> torch.Tensor:
     """The plain cross-entropy head, fused: F.cross_entropy(F.linear(norm(x), weight).float(), targets, ignore_index=ignore_index)
     as an fp32 scalar, with no softcap and the mean over the kept targets: mathblations/model.py:337-338 with main.py:294-303
     (norm_in=True, the scored window marked with window_targets) and inference/inference.py:349-359 (norm_in=False, the shift done by
@@ -1406,26 +1431,42 @@ def plain_head_loss(x: torch.Tensor, weight: torch.Tensor, targets: torch.Tensor
     one call forms both gradients beside the loss; under no_grad it is the loss alone, with the same bits.
     A target equal to ignore_index drops its row; any other target outside [0, vocab) drops it too and raises the status bit that
     check_status() reports.  The number of kept targets is counted on the device (the call captures into a hipGraph); with none kept
-    the loss is NaN, as torch's, and the gradients are exactly zero."""
+    the loss is NaN, as torch's, and the gradients are exactly zero.
+    max_kept (None: every row's logits are formed, kept or not): a host bound on the number of kept targets, e.g.
+    window_kept_bound(ranges, T) or the label mask's count.  The kept rows are then compacted on the device behind
+    cap = min(max_kept, rows) and the products, the row pass and the chunks (chunk_rows clipped to cap) run over cap slots, so the
+    time and the workspace follow the scored positions; whole padding chunks of a loose bound still run, on zero rows.  The loss is
+    the same fixed-order sum over the slots (the same bits on every run, not necessarily those of max_kept=None); dropped rows of
+    the gradient are +0.  More kept targets than max_kept is a caller error: the loss is NaN, the gradients are exactly zero and
+    check_status() reports the kept overflow; the first max_kept rows are never scored alone."""
+    max_kept = _max_kept_arg("plain_head_loss", max_kept)
     if not torch.is_grad_enabled() or not (x.requires_grad or weight.requires_grad):
         x2, w, t = _plain_head_operands(x, weight, targets)
-        return _plain_head_call(x2, w, t, norm_in, ignore_index, chunk_rows, None, None)
-    return _PlainHeadFn.apply(x, weight, targets, bool(norm_in), int(ignore_index), chunk_rows)
+        return _plain_head_call(x2, w, t, norm_in, ignore_index, chunk_rows, None, None, max_kept)
+    return _PlainHeadFn.apply(x, weight, targets, bool(norm_in), int(ignore_index), chunk_rows, max_kept)
 
 
 @torch.compiler.disable
 @torch.no_grad()
 def plain_head_eval(x: torch.Tensor, weight: torch.Tensor, targets: torch.Tensor, *, norm_in: bool = True, ignore_index: int = -100,
-                    chunk_rows: int | None = None, group_rows: int = 0) -> HeadEval:
+                    chunk_rows: int | None = None, group_rows: int = 0, max_kept: int | None = None) -> HeadEval:
     """The plain head for evaluation (mathblations/main.py:164-187): the pass of plain_head_loss under no_grad over the same chunks,
     which also writes every row's loss, top-1 prediction and target rank (HeadEval) without any tensor of rows x vocab.
     HeadEval.loss has the bits of plain_head_loss.  A dropped row (target ignore_index or out of range) has row_loss 0 and rank -1;
     its pred is still written.  counts = [kept rows, kept rows with pred == target]; with group_rows > 0 (the sequence length; it
     must divide the rows) a third entry counts the groups of group_rows consecutive rows that have a kept row and whose kept rows are
-    all right, full_correct of main.py:183-187.  Forms no gradients in any grad mode."""
+    all right, full_correct of main.py:183-187.  Forms no gradients in any grad mode.
+    max_kept as in plain_head_loss: the kept rows alone are scored.  Kept rows get what max_kept=None writes; a dropped row's logits
+    are never formed, so its pred is -1 (row_loss 0 and rank -1 as before).  The counts keep their definition, HeadEval.loss has the
+    bits of plain_head_loss(..., max_kept=max_kept) under no_grad."""
+    max_kept = _max_kept_arg("plain_head_eval", max_kept)
     x2, w, t = _plain_head_operands(x, weight, targets)
     d, dev = _plain_head_desc(x2, w, t, norm_in, ignore_index, chunk_rows, group_rows)
-    return _head_eval_call(dev, d, capi.lib.mot_plain_head_eval, capi.lib.mot_plain_head_workspace_bytes, targets.shape, 3 if group_rows else 2)
+    n_counts = 3 if group_rows else 2
+    if max_kept is None:
+        return _head_eval_call(dev, d, capi.lib.mot_plain_head_eval, capi.lib.mot_plain_head_workspace_bytes, targets.shape, n_counts)
+    c, ws_bytes = _plain_head_compact(max_kept)
+    return _head_eval_call(dev, d, capi.lib.mot_plain_head_compact_eval, ws_bytes, targets.shape, n_counts, C.byref(c))
 
 
 def window_targets(targets: torch.Tensor, ranges, ignore_index: int = -100) -> torch.Tensor:
@@ -1439,6 +1480,18 @@ def window_targets(targets: torch.Tensor, ranges, ignore_index: int = -100) -> t
     pos = torch.arange(targets.shape[1], device=targets.device)
     inside = (pos >= r[:, :1]) & (pos < r[:, 1:])
     return torch.where(inside, targets, torch.full_like(targets, ignore_index))
+
+
+def window_kept_bound(ranges, seq_len: int) -> int:
+    """The number of positions window_targets keeps for `ranges` on sequences of seq_len positions: the sum over the rows of
+    clip(end, 0, seq_len) - clip(start, 0, seq_len), a negative length counting 0.  The max_kept of plain_head_loss /
+    plain_head_eval for targets marked with window_targets (when every target inside the windows is a class; fewer kept rows only
+    leave padding).  ranges: a sequence of (start, end) pairs or a CPU tensor (B, 2): host data, read on the host.  A tensor on
+    another device raises TypeError: there is no hidden device read here; take the bound from the loader's host copy."""
+    if isinstance(ranges, torch.Tensor) and ranges.device.type != "cpu":
+        raise TypeError(f"window_kept_bound: ranges must be host data (a sequence or a CPU tensor), got a tensor on {ranges.device}")
+    r = torch.as_tensor(ranges, dtype=torch.int64).reshape(-1, 2).clamp(0, int(seq_len))
+    return int((r[:, 1] - r[:, 0]).clamp_min(0).sum())
 
 
 # ----------------------------------------------------------------------------------------------

@@ -471,7 +471,8 @@ class PlainLMHead(nn.Module):
     embedding (wte.weight = lm_head.weight, model.py:317) stays tied and receives both gradients.
     loss(x, targets) = F.cross_entropy(lm_head(norm(x)).float(), targets, ignore_index=ignore_index) without a logits tensor;
     evaluate(x, targets, group_rows) is main.py:164-187: HeadEval with the counts of kept rows, of right ones and, with group_rows
-    (the sequence length), of sequences whose kept rows are all right.  norm_in=False takes x as already normed (inference)."""
+    (the sequence length), of sequences whose kept rows are all right.  norm_in=False takes x as already normed (inference).  max_kept (both calls): a host bound on the kept targets,
+    e.g. functional.window_kept_bound(ranges, T); the kept rows alone are then scored (see functional.plain_head_loss)."""
 
     def __init__(self, lm_head: nn.Module, norm_in: bool = True, ignore_index: int = -100):
         super().__init__()
@@ -484,11 +485,12 @@ class PlainLMHead(nn.Module):
     def forward(self, x: Tensor) -> Tensor:   # the logits in plain torch ops, for generation
         return F.linear(norm(x) if self.norm_in else x, self.lm_head.weight.type_as(x))
 
-    def loss(self, x: Tensor, targets: Tensor) -> Tensor:
-        return F_mot.plain_head_loss(x, self.lm_head.weight, targets, norm_in=self.norm_in, ignore_index=self.ignore_index)
+    def loss(self, x: Tensor, targets: Tensor, max_kept: int | None = None) -> Tensor:
+        return F_mot.plain_head_loss(x, self.lm_head.weight, targets, norm_in=self.norm_in, ignore_index=self.ignore_index, max_kept=max_kept)
 
-    def evaluate(self, x: Tensor, targets: Tensor, group_rows: int = 0) -> "F_mot.HeadEval":
-        return F_mot.plain_head_eval(x, self.lm_head.weight, targets, norm_in=self.norm_in, ignore_index=self.ignore_index, group_rows=group_rows)
+    def evaluate(self, x: Tensor, targets: Tensor, group_rows: int = 0, max_kept: int | None = None) -> "F_mot.HeadEval":
+        return F_mot.plain_head_eval(x, self.lm_head.weight, targets, norm_in=self.norm_in, ignore_index=self.ignore_index, group_rows=group_rows,
+                                     max_kept=max_kept)
 
 
 class FusedFrontEnd(nn.Module):
