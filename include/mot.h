@@ -51,6 +51,7 @@ typedef enum MotStatus {
 #define MOT_STATUS_BYTE_OOR 2u  /* byte id outside [0, byte_rows)                 */
 #define MOT_STATUS_TARGET_OOR 4u /* target outside [0, vocab) (mot_byte_head_*, mot_token_head_*, mot_plain_head_*) */
 #define MOT_STATUS_KEPT_OVERFLOW 8u /* more kept rows than max_kept (mot_plain_head_compact_*): nothing was scored */
+#define MOT_STATUS_LOGIT_NONFINITE 16u /* a row of mot_next_token held a NaN or +inf logit: its token is -1 */
 
 typedef enum MotPullDir {
     MOT_PULL_NONE = 0,
@@ -763,6 +764,80 @@ size_t mot_plain_head_compact_workspace_bytes(const MotPlainHeadDesc *desc /* ho
 int mot_plain_head_compact_fwd(const MotPlainHeadDesc *desc /* host */, const MotPlainHeadCompact *compact /* host */, mot_stream_t stream);
 int mot_plain_head_compact_eval(const MotPlainHeadDesc *desc /* host */, const MotPlainHeadCompact *compact /* host */,
                                 const MotHeadEvalOut *out /* host */, mot_stream_t stream);
+
+/*
+ * The generation step behind the plain head: the last position's logits, the top-k and top-p cuts and the draw in ONE call.
+ * Replaces the loop body of inference/inference.py:420-444 (lm_head on the last position / temperature; torch.topk; a full
+ * torch.sort of 128 256 logits with cumsum, scatter and softmax; argmax or multinomial; .item()) and the print of :448-453.
+ * Shapes and conventions are the plain head's: vocab a multiple of 128 up to 262 144, model_dim a multiple of 16 up to 2048,
+ * norm_in, bf16 logits as stored.  Per row r of x [n_rows, model_dim], rows x_stride ELEMENTS apart (hidden[:, -1, :] passes
+ * without a copy; x_stride * sizeof(dtype) must be a multiple of 16):
+ *  1. h = c x_r with c = (mean(x_r^2) + eps)^-1/2 (norm_in), else h = x_r; with norm_in h is rounded to dtype, as F.rms_norm's
+ *     output is in front of lm_head.  l = h W^T is STORED in fp32, or in bf16 in MOT_BF16; everything behind it is fp32 or integer.
+ *     `logits` (optional, fp32 [n_rows, vocab]) receives the stored values, widened, in front of the temperature.
+ *  2. All order decisions are taken on the stored logits (-0 counts as +0); temperature > 0 keeps their order.  The mass of a class is
+ *     exp((l - m) / temperature) with m the row's maximum, held as an integer number of 2^-44 rounded UP (at least one unit for a
+ *     finite logit, none for -inf): every sum of masses is an integer sum, the same bits on every run and in every order.  The
+ *     rounding adds at most vocab * 2^-44 (1.5e-8) to a total of at least 1.
+ *  3. top-k (line 423-425) applies when 0 < top_k < vocab: a class stays when l >= the k-th largest value.  Ties with that value all
+ *     stay, as the reference's `<` leaves them.
+ *  4. top-p (line 428-437) applies when top_p < 1, over the survivors of 3 with their masses renormalised: a class stays when the mass
+ *     of the STRICTLY LARGER logits is <= top_p.  For distinct logits that is the reference (its shift by one keeps the first class
+ *     that crosses).  Among equal logits torch.sort promises no order, so the reference leaves open which members of a tie group on
+ *     the boundary stay; this call keeps a tie group whole.  That is the one place where it pins what the reference leaves open.
+ *  5. greedy: the largest logit, the lowest class on ties (the evaluation's rule).  Otherwise the inverse CDF over the kept classes
+ *     in ascending class order with the caller's u[r]: the first kept class whose running mass exceeds u Z (Z: the kept mass).  u is
+ *     clamped into [0, 1 - 2^-24], a NaN counts as 0; if rounding lets no class exceed u Z, the last kept class is returned: never
+ *     an unkept class, never vocab.  The random number itself (torch.rand, capture-aware) stays with the caller, which makes the call
+ *     reproducible.
+ *  6. token int64 [n_rows]; prob (optional) the filtered probability of the returned token; kept (optional, int32) the number of
+ *     surviving classes; top_cls / top_prob (optional, [n_rows, n_top], n_top <= 8) the largest filtered probabilities in descending
+ *     order, the lowest class first on ties, -1 / 0 past the kept count.
+ *  7. A row with a NaN or +inf logit (or with no finite logit at all) returns token = -1, prob = NaN, kept = 0, top_cls = -1,
+ *     top_prob = 0 and ORs MOT_STATUS_LOGIT_NONFINITE into `status`; the other rows are unaffected.
+ *  8. No allocation, no host read, no memset or memcpy node: the call captures into a hipGraph and a replay follows x, weight and u
+ *     changed in place (temperature, top_k, top_p, greedy and n_top are host values of the captured call).
+ *  9. n_rows = 0 is a no-op.  Up to 16 rows take a product kernel that reads W once; more rows take the heads' product in chunks whose
+ *     logits stay below 512 MiB.
+ * Checked before any HIP call, with a message that starts with the function's name: a null descriptor or a wrong struct_size ->
+ * MOT_EINVAL; dtype, vocab, model_dim, a misaligned x_stride or pointer -> MOT_EUNSUPPORTED; n_rows < 0 or x_stride < model_dim ->
+ * MOT_ESHAPE; temperature <= 0 or not finite, top_k < 0, top_p <= 0 or NaN, n_top outside 0..8, reserved != 0, a null u without
+ * greedy, a null x, weight or token -> MOT_EINVAL; a missing or short workspace -> MOT_EWORKSPACE.  The workspace query returns 0 for
+ * a descriptor the call would refuse (it ignores workspace and workspace_bytes) and for n_rows = 0.
+ * Not built: the trunk and its KV cache, a random generator inside the kernel, repetition penalties, beam search, gradients.
+ */
+typedef struct MotNextTokenDesc {
+    uint32_t struct_size; /* sizeof(MotNextTokenDesc) */
+    int32_t dtype;        /* MotDType of x and weight */
+    int32_t norm_in;      /* 1: x is rms-normed first, 0: x is taken as it is (inference.py: hidden states already normed) */
+    int32_t greedy;       /* 1: the largest logit; 0: the draw with u */
+    int64_t n_rows;       /* sequences in the batch */
+    int64_t x_stride;     /* elements between rows of x, >= model_dim */
+    int32_t model_dim;    /* columns of x and of weight */
+    int32_t vocab;        /* rows of weight */
+    float eps;            /* of the norm; <= 0 -> FLT_EPSILON */
+    float temperature;    /* > 0 */
+    int32_t top_k;        /* 0 or >= vocab: no cut */
+    float top_p;          /* > 0; >= 1: no cut */
+    int32_t n_top;        /* 0..8 columns of top_cls / top_prob */
+    int32_t reserved;     /* 0 */
+    const void *x;        /* [n_rows] rows of model_dim, 16-byte aligned */
+    const void *weight;   /* [vocab, model_dim] in dtype, 16-byte aligned */
+    const float *u;       /* [n_rows] uniform numbers of the caller; may be NULL with greedy */
+    int64_t *token;       /* [n_rows] */
+    float *prob;          /* optional [n_rows] */
+    int32_t *kept;        /* optional [n_rows] */
+    int32_t *top_cls;     /* optional [n_rows, n_top] */
+    float *top_prob;      /* optional [n_rows, n_top] */
+    float *logits;        /* optional [n_rows, vocab] fp32, 16-byte aligned */
+    uint32_t *status;     /* optional, as in MotEmbedMixDesc */
+    void *workspace;      /* >= mot_next_token_workspace_bytes(desc), 16-byte aligned */
+    size_t workspace_bytes;
+} MotNextTokenDesc;
+
+size_t mot_next_token_desc_size(void);
+size_t mot_next_token_workspace_bytes(const MotNextTokenDesc *desc /* host */);
+int mot_next_token(const MotNextTokenDesc *desc /* host */, mot_stream_t stream);
 
 /*
  * Byte self-attention in front of the concat mixin, forward: replaces ByteSelfAttn.forward with use_byte_self_attn on

@@ -25,7 +25,7 @@ IS_DEV_LIB = _dev_lib is not None
 
 # ---- enums of include/mot.h
 MOT_OK, MOT_EINVAL, MOT_ESHAPE, MOT_EUNSUPPORTED, MOT_EHIP, MOT_EWORKSPACE = 0, -1, -2, -3, -4, -5
-STATUS_TOKEN_OOR, STATUS_BYTE_OOR, STATUS_TARGET_OOR, STATUS_KEPT_OVERFLOW = 1, 2, 4, 8
+STATUS_TOKEN_OOR, STATUS_BYTE_OOR, STATUS_TARGET_OOR, STATUS_KEPT_OVERFLOW, STATUS_LOGIT_NONFINITE = 1, 2, 4, 8, 16
 PULL_NONE, PULL_LEFT, PULL_RIGHT = 0, 1, 2
 MIX_NOOP, MIX_SUM, MIX_MEAN, MIX_CONCAT_LINEAR, MIX_CONCAT = 0, 1, 2, 3, 4
 IDS_NONE, IDS_FROM_TTB, IDS_GIVEN = 0, 1, 2
@@ -62,6 +62,7 @@ EXPORTS = (
     "mot_head_eval_out_size", "mot_token_head_eval", "mot_byte_head_eval",
     "mot_plain_head_desc_size", "mot_plain_head_workspace_bytes", "mot_plain_head_fwd", "mot_plain_head_eval",
     "mot_plain_head_compact_size", "mot_plain_head_compact_workspace_bytes", "mot_plain_head_compact_fwd", "mot_plain_head_compact_eval",
+    "mot_next_token_desc_size", "mot_next_token_workspace_bytes", "mot_next_token",
     "mot_byte_self_attn_desc_size", "mot_byte_self_attn_saved_bytes", "mot_byte_self_attn_workspace_bytes",
     "mot_byte_self_attn_fwd", "mot_byte_self_attn_bwd",
     "mot_byte_fc_mix_desc_size", "mot_byte_fc_mix_workspace_bytes", "mot_byte_fc_mix_bwd_workspace_bytes",
@@ -186,6 +187,18 @@ class MotPlainHeadDesc(C.Structure):
 class MotPlainHeadCompact(C.Structure):
     """Mirror of struct MotPlainHeadCompact (include/mot.h)."""
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("max_kept", C.c_int64)]
+
+
+class MotNextTokenDesc(C.Structure):
+    """Mirror of struct MotNextTokenDesc (include/mot.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("dtype", C.c_int32), ("norm_in", C.c_int32), ("greedy", C.c_int32), ("n_rows", C.c_int64),
+        ("x_stride", C.c_int64), ("model_dim", C.c_int32), ("vocab", C.c_int32), ("eps", C.c_float), ("temperature", C.c_float),
+        ("top_k", C.c_int32), ("top_p", C.c_float), ("n_top", C.c_int32), ("reserved", C.c_int32),
+        ("x", C.c_void_p), ("weight", C.c_void_p), ("u", C.c_void_p), ("token", C.c_void_p), ("prob", C.c_void_p), ("kept", C.c_void_p),
+        ("top_cls", C.c_void_p), ("top_prob", C.c_void_p), ("logits", C.c_void_p),
+        ("status", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
 
 
 class MotHeadEvalOut(C.Structure):
@@ -410,6 +423,11 @@ def _load() -> C.CDLL:
     lib.mot_plain_head_compact_fwd.restype = C.c_int
     lib.mot_plain_head_compact_eval.argtypes = [C.POINTER(MotPlainHeadDesc), C.POINTER(MotPlainHeadCompact), C.POINTER(MotHeadEvalOut), vp]
     lib.mot_plain_head_compact_eval.restype = C.c_int
+    lib.mot_next_token_desc_size.restype = C.c_size_t
+    lib.mot_next_token_workspace_bytes.restype = C.c_size_t
+    lib.mot_next_token_workspace_bytes.argtypes = [C.POINTER(MotNextTokenDesc)]
+    lib.mot_next_token.argtypes = [C.POINTER(MotNextTokenDesc), vp]
+    lib.mot_next_token.restype = C.c_int
     lib.mot_byte_self_attn_desc_size.restype = C.c_size_t
     for name in ("mot_byte_self_attn_saved_bytes", "mot_byte_self_attn_workspace_bytes"):
         getattr(lib, name).restype = C.c_size_t
@@ -479,6 +497,8 @@ def _load() -> C.CDLL:
         raise ImportError("MotPlainHeadDesc layout mismatch between include/mot.h and _capi.py")
     if lib.mot_plain_head_compact_size() != C.sizeof(MotPlainHeadCompact):
         raise ImportError("MotPlainHeadCompact layout mismatch between include/mot.h and _capi.py")
+    if lib.mot_next_token_desc_size() != C.sizeof(MotNextTokenDesc):
+        raise ImportError("MotNextTokenDesc layout mismatch between include/mot.h and _capi.py")
     if lib.mot_head_eval_out_size() != C.sizeof(MotHeadEvalOut):
         raise ImportError("MotHeadEvalOut layout mismatch between include/mot.h and _capi.py")
     if lib.mot_byte_self_attn_desc_size() != C.sizeof(MotByteSelfAttnDesc):
@@ -550,6 +570,8 @@ def check_status(device=None) -> None:
             said = [f"{' and '.join(what)} out of range"] if what else []
             if v & STATUS_KEPT_OVERFLOW:   # the compacted plain head: a caller error, nothing was scored
                 said.append("kept overflow: more kept rows than max_kept")
+            if v & STATUS_LOGIT_NONFINITE:   # next_token: a row held a NaN or +inf logit, its token is -1
+                said.append("next_token: a NaN or +inf logit")
             raise IndexError(f"index out of range in self ({'; '.join(said)})")
 
 

@@ -422,6 +422,12 @@ int mot_plain_head_compact_eval(const MotPlainHeadDesc *desc, const MotPlainHead
     return launch_plain_head_compact_eval(desc, compact, out, (hipStream_t)stream);
 }
 
+size_t mot_next_token_desc_size(void) { return sizeof(MotNextTokenDesc); }
+
+size_t mot_next_token_workspace_bytes(const MotNextTokenDesc *desc) { return next_token_workspace_bytes(desc); }
+
+int mot_next_token(const MotNextTokenDesc *desc, mot_stream_t stream) { return launch_next_token(desc, (hipStream_t)stream); }
+
 size_t mot_byte_self_attn_desc_size(void) { return sizeof(MotByteSelfAttnDesc); }
 
 // everything that does not need the pointers: also what the two size queries run

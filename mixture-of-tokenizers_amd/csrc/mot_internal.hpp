@@ -149,6 +149,9 @@ int launch_plain_head_eval(const MotPlainHeadDesc *d, const MotHeadEvalOut *out,
 size_t plain_head_compact_workspace_bytes(const MotPlainHeadDesc *d, const MotPlainHeadCompact *c);   // 0 for what the calls would refuse
 int launch_plain_head_compact_fwd(const MotPlainHeadDesc *d, const MotPlainHeadCompact *c, hipStream_t stream);
 int launch_plain_head_compact_eval(const MotPlainHeadDesc *d, const MotPlainHeadCompact *c, const MotHeadEvalOut *out, hipStream_t stream);
+// the generation step (mot_nexttoken.hip): its own validation, every refusal before any HIP call
+size_t next_token_workspace_bytes(const MotNextTokenDesc *d);   // 0 for a descriptor the call would refuse
+int launch_next_token(const MotNextTokenDesc *d, hipStream_t stream);
 // byte self-attention of the concat mixin (mot_bsa.hip); the descriptor is validated in mot_capi.hip
 size_t byte_self_attn_saved_bytes(const MotByteSelfAttnDesc &d);
 size_t byte_self_attn_workspace_bytes(const MotByteSelfAttnDesc &d);

@@ -1469,6 +1469,84 @@ def plain_head_eval(x: torch.Tensor, weight: torch.Tensor, targets: torch.Tensor
     return _head_eval_call(dev, d, capi.lib.mot_plain_head_compact_eval, ws_bytes, targets.shape, n_counts, C.byref(c))
 
 
+# ----------------------------------------------------------------------------------------------
+# the generation step behind the plain head: logits of the last position, top-k / top-p and the draw, inference/inference.py:420-444
+# ----------------------------------------------------------------------------------------------
+class NextToken(NamedTuple):
+    """What next_token returns, in the shape of x without its last dimension.  token int64: the chosen class, -1 for a row with a NaN or
+    +inf logit; prob fp32: its probability after the cuts; kept int32: the classes that survive the cuts; top_cls int32 / top_prob fp32
+    (..., n_top): the largest filtered probabilities in descending order, -1 / 0 past the kept count (None at n_top = 0); logits fp32
+    (..., vocab): the stored logits in front of the temperature (None unless return_logits)."""
+    token: torch.Tensor
+    prob: torch.Tensor
+    kept: torch.Tensor
+    top_cls: torch.Tensor | None
+    top_prob: torch.Tensor | None
+    logits: torch.Tensor | None
+
+
+def _next_token_rows(x):
+    """x (..., model_dim) as rows the library reads in place: a 2-d view whose rows are contiguous, 16-byte aligned and a fixed number
+    of elements apart (hidden[:, -1, :] is one), else a contiguous copy.  Returns (rows, stride in elements)."""
+    x2 = x.detach()
+    if x2.ndim == 1:
+        x2 = x2[None]
+    elif x2.ndim != 2:
+        x2 = x2.reshape(-1, x2.shape[-1])
+    n, dim = x2.shape
+    e = x2.element_size()
+    ok = n == 0 or ((dim == 1 or x2.stride(1) == 1) and x2.data_ptr() % 16 == 0 and (n == 1 or (x2.stride(0) >= dim and x2.stride(0) * e % 16 == 0)))
+    if not ok:
+        x2 = x2.contiguous()
+    return x2, (x2.stride(0) if n > 1 else dim)
+
+
+@torch.compiler.disable
+@torch.no_grad()
+def next_token(x: torch.Tensor, weight: torch.Tensor, *, norm_in: bool = False, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+               greedy: bool = False, u: torch.Tensor | None = None, n_top: int = 0, return_logits: bool = False) -> NextToken:
+    """One generation step, fused (inference/inference.py:420-444): lm_head on the rows of x (the last position's hidden states),
+    / temperature, the top-k cut (0 < top_k < vocab), the top-p cut over its survivors (top_p < 1), then argmax (greedy) or the
+    inverse-CDF draw with u, one uniform number in [0, 1) per row (None: torch.rand on the device, so the call stays capturable).
+    x (..., model_dim) float32 or bfloat16, read in place when its rows are a fixed stride apart; weight (vocab, model_dim), cast to
+    x's dtype.  Decisions are taken on the stored logits (bf16 with bfloat16 x).  top-k keeps every class tied with the k-th value;
+    top-p keeps a class when the mass of the strictly larger logits is <= top_p and keeps a tie group whole; the draw takes the first
+    kept class, in ascending class order, whose running mass exceeds u * (kept mass).  Nothing is read on the host, no sort, no tensor
+    beyond the logits.  Forms no gradients in any grad mode."""
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"next_token: x must be float32 or bfloat16, got {x.dtype}")
+    if weight.ndim != 2 or weight.shape[1] != x.shape[-1]:
+        raise ValueError(f"next_token: weight must be (vocab, {x.shape[-1]}), got {tuple(weight.shape)}")
+    dev = capi.require_device(x, weight, u)
+    x2, stride = _next_token_rows(x)
+    n, shape, vocab, n_top = x2.shape[0], tuple(x.shape[:-1]), weight.shape[0], int(n_top)
+    w = _contig(weight.detach().to(x2.dtype), x2.dtype, "weight")
+    if u is not None:
+        u = _contig(u.detach().reshape(-1), torch.float32, "u")
+        if u.numel() != n:
+            raise ValueError(f"next_token: {u.numel()} uniform numbers for {n} rows")
+    elif not greedy:
+        u = torch.rand(n, dtype=torch.float32, device=dev)
+    token = torch.empty(n, dtype=torch.int64, device=dev)
+    prob = torch.empty(n, dtype=torch.float32, device=dev)
+    kept = torch.empty(n, dtype=torch.int32, device=dev)
+    top_cls = torch.empty((n, n_top), dtype=torch.int32, device=dev) if n_top > 0 else None
+    top_prob = torch.empty((n, n_top), dtype=torch.float32, device=dev) if n_top > 0 else None
+    logits = torch.empty((n, vocab), dtype=torch.float32, device=dev) if return_logits else None
+    d = capi.MotNextTokenDesc()
+    d.struct_size = C.sizeof(capi.MotNextTokenDesc)
+    d.dtype, d.norm_in, d.greedy, d.n_rows, d.x_stride = capi.dtype_code(x2.dtype), int(bool(norm_in)), int(bool(greedy)), n, stride
+    d.model_dim, d.vocab, d.eps, d.temperature = x2.shape[1], vocab, 0.0, float(temperature)
+    d.top_k, d.top_p, d.n_top, d.reserved = int(top_k), float(top_p), n_top, 0
+    d.x, d.weight, d.u, d.token, d.prob, d.kept = capi.ptr(x2), capi.ptr(w), capi.ptr(u), capi.ptr(token), capi.ptr(prob), capi.ptr(kept)
+    d.top_cls, d.top_prob, d.logits = capi.ptr(top_cls), capi.ptr(top_prob), capi.ptr(logits)
+    if n > 0:   # no rows: nothing to launch (and an empty tensor has no address to pass)
+        _launch(dev, d, capi.lib.mot_next_token, ws_bytes=capi.lib.mot_next_token_workspace_bytes)
+    return NextToken(token.reshape(shape), prob.reshape(shape), kept.reshape(shape),
+                     None if top_cls is None else top_cls.reshape(shape + (n_top,)), None if top_prob is None else top_prob.reshape(shape + (n_top,)),
+                     None if logits is None else logits.reshape(shape + (vocab,)))
+
+
 def window_targets(targets: torch.Tensor, ranges, ignore_index: int = -100) -> torch.Tensor:
     """targets (B, T) with everything outside each row's [start, end) set to ignore_index: the positions slice_logits_and_targets
     (mathblations/data.py:262-278) keeps for y_indices = ranges, (B, 2) as a tensor or a sequence of (start, end).  The mean over the

@@ -492,6 +492,14 @@ class PlainLMHead(nn.Module):
         return F_mot.plain_head_eval(x, self.lm_head.weight, targets, norm_in=self.norm_in, ignore_index=self.ignore_index, group_rows=group_rows,
                                      max_kept=max_kept)
 
+    def next_token(self, hidden: Tensor, **kw) -> "F_mot.NextToken":
+        """One generation step on the fused call (inference.py:420-444): hidden (B, T, D), whose last position is read in place as a
+        strided view, or (B, D); kw as functional.next_token (temperature, top_k, top_p, greedy, u, n_top, return_logits)."""
+        if hidden.ndim not in (2, 3):
+            raise ValueError(f"PlainLMHead.next_token: hidden must be (B, T, D) or (B, D), got {tuple(hidden.shape)}")
+        rows = hidden[:, -1, :] if hidden.ndim == 3 else hidden
+        return F_mot.next_token(rows, self.lm_head.weight, norm_in=self.norm_in, **kw)
+
 
 class FusedFrontEnd(nn.Module):
     """Loader + embed + mixin in one library call: tokens (B,T) -> x (B,T,model_dim), with the
