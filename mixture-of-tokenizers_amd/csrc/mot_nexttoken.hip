@@ -7,7 +7,7 @@
 //                      call's dtype as F.rms_norm's output is in front of lm_head, sit in LDS; a wave owns four class rows at a time,
 //                      every lane a 16-byte slice of the reduction, the waves' DPP sums close each product.  Stores fp32 or bf16.
 //                      Above 16 rows the same rows of x are written by nexttoken_rows_in and the product is launch_product_nt.
-//   nexttoken_row      one workgroup per row, plainhead_rows' geometry (the row in registers up to eight 16-byte vectors a thread:
+//   nexttoken_row      one workgroup per row, wide_rows' geometry (the row in registers up to eight 16-byte vectors a thread:
 //                      32 768 classes in fp32, 65 536 in bf16; read again from L2 above that).
 //                      All order decisions are taken on the stored logit's order-preserving integer image (-0 counts as +0):
 //                      the k-th largest value and the top-p boundary come from a three-level radix selection (11 + 11 + 10 bits),
@@ -20,7 +20,7 @@
 // The draw walks the kept classes in ascending class order: step i of the sweep gives wave w the 64 consecutive vectors
 // [(i * waves + w) * 64, +64), so the sums of these spans, in (i, w) order, are the prefix masses of contiguous class spans; one
 // wave scans them, the owning wave scans its lanes, the owning lane its vector.
-#include "mot_headrows.hpp"
+#include "mot_widehead.hpp"
 
 namespace mot {
 namespace {
@@ -35,28 +35,13 @@ constexpr float kNtMassScale = 0x1p44f;
 constexpr double kNtMassUnit = 0x1p-44;
 
 // ---------------------------------------------------------------------------------------------- the rows of x as the product takes them
-// row r of the chunk, normed (norm_in) and rounded to T, into dst[0, K); one wave
-template <typename T>
-__device__ __forceinline__ void nt_stage_row(const T *__restrict__ xr, int K, int norm_in, float eps, T *dst) {
-    const int lane = threadIdx.x & 63;
-    float c = 1.f;
-    if (norm_in) {
-        float ss = 0.f, dc;
-        for (int k = lane; k < K; k += 64) {
-            const float v = (float)xr[k];
-            ss += v * v;
-        }
-        row_scale(wave_sum(ss) / (float)K, 0, eps, c, dc);
-    }
-    for (int k = lane; k < K; k += 64) dst[k] = norm_in ? (T)(c * (float)xr[k]) : xr[k];
-}
-
+// norm_round_row (mot_headrows.hpp): a row, normed (norm_in) and rounded to T; one wave
 template <typename T>
 __global__ __launch_bounds__(kThreads) void nexttoken_rows_in(const T *__restrict__ x, int64_t x_stride, int64_t n, int K, int norm_in, float eps,
                                                               T *__restrict__ hg) {
     const int64_t j = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
     if (j >= n) return;
-    nt_stage_row<T>(x + j * x_stride, K, norm_in, eps, hg + j * K);
+    norm_round_row<T>(x + j * x_stride, K, norm_in, eps, hg + j * K);
 }
 
 // S[r][v] = T(sum_k xs[r][k] W[v][k]) for r < n_rows <= R, fp32 sums (fused multiply-adds over the lane's slices, then the wave's DPP sum)
@@ -68,7 +53,7 @@ __global__ __launch_bounds__(kSkinnyThreads) void nexttoken_skinny(const T *__re
     T *xs = (T *)nt_smem;   // [R][K]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int r = wave; r < R; r += kSkinnyWaves) {
-        if (r < n_rows) nt_stage_row<T>(x + r * x_stride, K, norm_in, eps, xs + r * K);
+        if (r < n_rows) norm_round_row<T>(x + r * x_stride, K, norm_in, eps, xs + r * K);
         else
             for (int k = lane; k < K; k += 64) xs[r * K + k] = (T)0.f;
     }
@@ -471,13 +456,7 @@ int nt_check(const MotNextTokenDesc *d, NtGeom *out, const char *fn) {
     if (!d) return set_error(MOT_EINVAL, "%s: null descriptor", fn);
     if (d->struct_size != sizeof(MotNextTokenDesc))
         return set_error(MOT_EINVAL, "%s: struct_size %u != %zu (ABI mismatch)", fn, d->struct_size, sizeof(MotNextTokenDesc));
-    if (d->dtype != MOT_F32 && d->dtype != MOT_BF16) return set_error(MOT_EUNSUPPORTED, "%s: dtype %d is not built", fn, d->dtype);
-    if (d->n_rows < 0 || d->n_rows > 0x7fffffffLL || d->model_dim <= 0 || d->vocab <= 0)
-        return set_error(MOT_ESHAPE, "%s: n_rows %lld, model_dim %d, vocab %d", fn, (long long)d->n_rows, d->model_dim, d->vocab);
-    if (d->vocab % kMinV || d->vocab > kMaxV)
-        return set_error(MOT_EUNSUPPORTED, "%s: vocab %d must be a multiple of %d and at most %d", fn, d->vocab, kMinV, kMaxV);
-    if (d->model_dim % 16 || d->model_dim > kMaxD)
-        return set_error(MOT_EUNSUPPORTED, "%s: model_dim %d must be a multiple of 16 and at most %d", fn, d->model_dim, kMaxD);
+    if (int rc = wide_shape_check(fn, d->dtype, d->n_rows, d->model_dim, d->vocab)) return rc;
     const int e = d->dtype == MOT_BF16 ? 2 : 4;
     if (d->x_stride < d->model_dim) return set_error(MOT_ESHAPE, "%s: x_stride %lld below model_dim %d", fn, (long long)d->x_stride, d->model_dim);
     if ((d->x_stride * e) & 15)

@@ -1136,6 +1136,20 @@ def _byte_head_step_operands(x, weight, targets, method, bpt, n_layer_out):
     return _byte_head_operands(x, weight, targets, bpt)
 
 
+def _scale_head_grads(ctx, grad_loss, need_x=True, need_w=True):
+    """The backward of the head Functions whose forward formed dx and the fp32 dW for grad_loss = 1 and saved them (either may be
+    None) with cfg = (x.shape, weight.dtype, ...): both times the incoming grad_loss, on the device and out of place."""
+    dx, dw = ctx.saved_tensors
+    xshape, wdtype = ctx.cfg[:2]
+    go = grad_loss.detach().reshape(1, 1).float()
+    gx = gw = None
+    if need_x and dx is not None:   # one elementwise pass: fp32 factor, fp32 product, one rounding on store, no fp32 copy of dx
+        gx = torch.mul(dx, go, out=torch.empty_like(dx)).reshape(xshape)
+    if need_w and dw is not None:
+        gw = torch.mul(dw, go, out=torch.empty(dw.shape, dtype=wdtype, device=dw.device))
+    return gx, gw
+
+
 class _ByteHeadStepFn(torch.autograd.Function):
     """forward = one mot_byte_head_step that also forms dx and the fp32 dW for grad_loss = 1; backward multiplies them by the incoming
     grad_loss on the device, out of place (a retained graph runs backward again on the same saved gradients)."""
@@ -1153,15 +1167,7 @@ class _ByteHeadStepFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_loss):
-        dx, dw = ctx.saved_tensors
-        xshape, wdtype, need_x, need_w = ctx.cfg
-        go = grad_loss.detach().reshape(1, 1).float()
-        gx = gw = None
-        if need_x:   # one elementwise pass: fp32 factor, fp32 product, one rounding on store
-            gx = torch.mul(dx, go, out=torch.empty_like(dx)).reshape(xshape)
-        if need_w:
-            gw = torch.mul(dw, go, out=torch.empty(dw.shape, dtype=wdtype, device=dw.device))
-        return gx, gw, None, None, None, None
+        return _scale_head_grads(ctx, grad_loss, *ctx.cfg[2:]) + (None,) * 4
 
 
 @torch.compiler.disable
@@ -1193,31 +1199,42 @@ def byte_head_loss(x: torch.Tensor, weight: torch.Tensor, targets: torch.Tensor,
 _SOFTCAPS = {"sigmoid30": capi.SOFTCAP_SIGMOID30, "rsqrt15": capi.SOFTCAP_RSQRT15}
 
 
-def _token_head_call(x2, w, t, softcap, norm_in, chunk_rows, dx, dw):
-    """One mot_token_head_fwd: the loss, and the gradients for grad_loss = 1 into dx / dw where given."""
+def _token_head_desc(x2, w, t, softcap, norm_in, chunk_rows):
     dev = capi.require_device(x2, w, t)
-    loss = torch.empty((), dtype=torch.float32, device=dev)
     d = capi.MotTokenHeadDesc()
     d.struct_size = C.sizeof(capi.MotTokenHeadDesc)
     d.dtype, d.softcap, d.norm_in, d.chunk_rows = capi.dtype_code(x2.dtype), _SOFTCAPS[softcap], int(bool(norm_in)), int(chunk_rows or 0)
     d.n_rows, d.model_dim, d.vocab, d.eps = x2.shape[0], x2.shape[1], w.shape[0], 0.0
-    d.x, d.weight, d.targets, d.loss = capi.ptr(x2), capi.ptr(w), capi.ptr(t), capi.ptr(loss)
-    d.dx, d.dW = capi.ptr(dx), capi.ptr(dw)
+    d.x, d.weight, d.targets = capi.ptr(x2), capi.ptr(w), capi.ptr(t)
+    return d, dev
+
+
+def _token_head_call(x2, w, t, softcap, norm_in, chunk_rows, dx, dw):
+    """One mot_token_head_fwd: the loss, and the gradients for grad_loss = 1 into dx / dw where given."""
+    d, dev = _token_head_desc(x2, w, t, softcap, norm_in, chunk_rows)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    d.loss, d.dx, d.dW = capi.ptr(loss), capi.ptr(dx), capi.ptr(dw)
     _launch(dev, d, capi.lib.mot_token_head_fwd, ws_bytes=capi.lib.mot_token_head_workspace_bytes)
     return loss
+
+
+def _wide_head_operands(fn, x, weight, targets):
+    """The operand checks of the token-level and the plain head, then x as rows, the weight in x's dtype and int64 targets; `fn`,
+    the public function's name, starts the messages."""
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"{fn}: x must be float32 or bfloat16, got {x.dtype}")
+    if weight.ndim != 2 or weight.shape[1] != x.shape[-1]:
+        raise ValueError(f"{fn}: weight must be (vocab, {x.shape[-1]}), got {tuple(weight.shape)}")
+    if targets.dtype not in (torch.int64, torch.int32):
+        raise TypeError(f"{fn}: targets must be int64 or int32, got {targets.dtype}")
+    capi.require_device(x, weight, targets)
+    return _head_operands(fn, x, weight, targets.to(torch.int64), 1, "rows")
 
 
 def _token_head_operands(x, weight, targets, softcap):
     if softcap not in _SOFTCAPS:
         raise ValueError(f"token_head_loss: softcap must be 'sigmoid30' or 'rsqrt15', got {softcap!r}")
-    if x.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError(f"token_head_loss: x must be float32 or bfloat16, got {x.dtype}")
-    if weight.ndim != 2 or weight.shape[1] != x.shape[-1]:
-        raise ValueError(f"token_head_loss: weight must be (vocab, {x.shape[-1]}), got {tuple(weight.shape)}")
-    if targets.dtype not in (torch.int64, torch.int32):
-        raise TypeError(f"token_head_loss: targets must be int64 or int32, got {targets.dtype}")
-    capi.require_device(x, weight, targets)
-    return _head_operands("token_head_loss", x, weight, targets.to(torch.int64), 1, "rows")
+    return _wide_head_operands("token_head_loss", x, weight, targets)
 
 
 class _TokenHeadFn(torch.autograd.Function):
@@ -1238,15 +1255,7 @@ class _TokenHeadFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_loss):
-        dx, dw = ctx.saved_tensors
-        xshape, wdtype = ctx.cfg
-        go = grad_loss.detach().reshape(1, 1).float()
-        gx = gw = None
-        if dx is not None:   # one elementwise pass: fp32 factor, fp32 product, one rounding on store, no fp32 copy of dx
-            gx = torch.mul(dx, go, out=torch.empty_like(dx)).reshape(xshape)
-        if dw is not None:
-            gw = torch.mul(dw, go, out=torch.empty(dw.shape, dtype=wdtype, device=dw.device))
-        return gx, gw, None, None, None, None
+        return _scale_head_grads(ctx, grad_loss) + (None,) * 4
 
 
 @torch.compiler.disable
@@ -1309,13 +1318,8 @@ def token_head_eval(x: torch.Tensor, weight: torch.Tensor, targets: torch.Tensor
     HeadEval.loss has the bits of that call.  pred and rank are taken on the stored products x W^T (bf16 with bfloat16 x), in front of
     the norm's positive factor and the increasing softcap: rank < k is top-k accuracy.  Forms no gradients in any grad mode.
     A target outside [0, vocab) raises the status bit that check_status() reports and is left out of loss and counts."""
-    x2, w, t = _token_head_operands(x, weight, targets, softcap)
-    dev = capi.require_device(x2, w, t)
-    d = capi.MotTokenHeadDesc()
-    d.struct_size = C.sizeof(capi.MotTokenHeadDesc)
-    d.dtype, d.softcap, d.norm_in, d.chunk_rows = capi.dtype_code(x2.dtype), _SOFTCAPS[softcap], int(bool(norm_in)), int(chunk_rows or 0)
-    d.n_rows, d.model_dim, d.vocab, d.eps = x2.shape[0], x2.shape[1], w.shape[0], 0.0
-    d.x, d.weight, d.targets = capi.ptr(x2), capi.ptr(w), capi.ptr(t)
+    x2, w, t = _token_head_operands(x, weight, targets, softcap)   # held until the launch: the descriptor has only their addresses
+    d, dev = _token_head_desc(x2, w, t, softcap, norm_in, chunk_rows)
     return _head_eval_call(dev, d, capi.lib.mot_token_head_eval, capi.lib.mot_token_head_workspace_bytes, targets.shape, 2)
 
 
@@ -1338,17 +1342,6 @@ def byte_head_eval(x: torch.Tensor, weight: torch.Tensor, targets: torch.Tensor,
 # plain cross-entropy head: lm_head + cross_entropy without a softcap, with ignore_index and the mean over the kept targets,
 # mathblations/model.py:337-338 + main.py:294-303 (evaluation :164-187), inference/inference.py:349-359
 # ----------------------------------------------------------------------------------------------
-def _plain_head_operands(x, weight, targets):
-    if x.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError(f"plain_head_loss: x must be float32 or bfloat16, got {x.dtype}")
-    if weight.ndim != 2 or weight.shape[1] != x.shape[-1]:
-        raise ValueError(f"plain_head_loss: weight must be (vocab, {x.shape[-1]}), got {tuple(weight.shape)}")
-    if targets.dtype not in (torch.int64, torch.int32):
-        raise TypeError(f"plain_head_loss: targets must be int64 or int32, got {targets.dtype}")
-    capi.require_device(x, weight, targets)
-    return _head_operands("plain_head_loss", x, weight, targets.to(torch.int64), 1, "rows")
-
-
 def _plain_head_desc(x2, w, t, norm_in, ignore_index, chunk_rows, group_rows=0):
     dev = capi.require_device(x2, w, t)
     d = capi.MotPlainHeadDesc()
@@ -1396,7 +1389,7 @@ class _PlainHeadFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, targets, norm_in, ignore_index, chunk_rows, max_kept=None):
-        x2, w, t = _plain_head_operands(x, weight, targets)
+        x2, w, t = _wide_head_operands("plain_head_loss", x, weight, targets)
         need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         dx = torch.empty_like(x2) if need_x else None
         dw = torch.empty(w.shape, dtype=torch.float32, device=x2.device) if need_w else None
@@ -1408,15 +1401,7 @@ class _PlainHeadFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_loss):
-        dx, dw = ctx.saved_tensors
-        xshape, wdtype = ctx.cfg
-        go = grad_loss.detach().reshape(1, 1).float()
-        gx = gw = None
-        if dx is not None:   # one elementwise pass: fp32 factor, fp32 product, one rounding on store, no fp32 copy of dx
-            gx = torch.mul(dx, go, out=torch.empty_like(dx)).reshape(xshape)
-        if dw is not None:
-            gw = torch.mul(dw, go, out=torch.empty(dw.shape, dtype=wdtype, device=dw.device))
-        return gx, gw, None, None, None, None, None
+        return _scale_head_grads(ctx, grad_loss) + (None,) * 5
 
 
 @torch.compiler.disable
@@ -1441,7 +1426,7 @@ def plain_head_loss(x: torch.Tensor, weight: torch.Tensor, targets: torch.Tensor
     check_status() reports the kept overflow; the first max_kept rows are never scored alone."""
     max_kept = _max_kept_arg("plain_head_loss", max_kept)
     if not torch.is_grad_enabled() or not (x.requires_grad or weight.requires_grad):
-        x2, w, t = _plain_head_operands(x, weight, targets)
+        x2, w, t = _wide_head_operands("plain_head_loss", x, weight, targets)
         return _plain_head_call(x2, w, t, norm_in, ignore_index, chunk_rows, None, None, max_kept)
     return _PlainHeadFn.apply(x, weight, targets, bool(norm_in), int(ignore_index), chunk_rows, max_kept)
 
@@ -1460,7 +1445,7 @@ def plain_head_eval(x: torch.Tensor, weight: torch.Tensor, targets: torch.Tensor
     are never formed, so its pred is -1 (row_loss 0 and rank -1 as before).  The counts keep their definition, HeadEval.loss has the
     bits of plain_head_loss(..., max_kept=max_kept) under no_grad."""
     max_kept = _max_kept_arg("plain_head_eval", max_kept)
-    x2, w, t = _plain_head_operands(x, weight, targets)
+    x2, w, t = _wide_head_operands("plain_head_loss", x, weight, targets)
     d, dev = _plain_head_desc(x2, w, t, norm_in, ignore_index, chunk_rows, group_rows)
     n_counts = 3 if group_rows else 2
     if max_kept is None:
