@@ -485,6 +485,63 @@ size_t mot_char_swa_workspace_bytes(const MotCharSwaDesc *desc /* host */);
 int mot_char_swa_fwd(const MotCharSwaDesc *desc /* host */, mot_stream_t stream);
 
 /*
+ * One decode step of the character mixer: row t of what mot_char_swa_fwd computes for a sequence, from the newest token alone and a
+ * device-side state, for n_rows <= 16 sequences at once (the generation loop of inference/inference.py:411-489 with a KV cache in
+ * the trunk needs only the newest row).  Rotary cancels (mot_swa.hip), so row t depends on the token at t, on the character ids of
+ * the tokens t-window+1 .. t and on how many of those lie in front of the row's start.
+ *   state   ring [n_rows, window, c_v] int32: the characters of source position s sit in slot s % window;
+ *           pos  [n_rows] int64: the tokens of the row seen so far.
+ *   call    t = pos[b]; the new token's characters (row tokens[b] of tok_chars, or char_ids_new[b]) go to slot t % window; the query
+ *           attends over the window (a slot whose source position is < 0 is a padding key: score 0, a place in the softmax, zero
+ *           value, as in mot_char_swa_fwd); pos[b] = t + 1.
+ * `kv_tables` are the fp32 key / value tables that mot_char_swa_fwd fills (the prefill call): the step never builds them.
+ * Three launches on `stream`; no allocation, sync, memset or memcpy node; nothing is read on the host, `tokens` is device memory
+ * (mot_next_token's `token` is read in place).  Every sum has a fixed order: the same bits on every run.
+ * dtype MOT_F32: fp32 tables and weights.  MOT_BF16: tok_table, char_table, wq and wo are bf16 and read in place, `out` is bf16;
+ * the rounding points are those of mot_char_swa_fwd with matmul_dtype = io_dtype = MOT_BF16 (xn, q, k, v, y and the output of wo
+ * are bf16 tensors; softmax and sums in fp32; the residuals are added to the bf16 output of wo in fp32, one rounding).
+ * A token outside [0, tok_rows) raises MOT_STATUS_TOKEN_OOR and is treated as row 0 (mot_next_token's -1 included); a character id
+ * outside [0, char_rows) raises MOT_STATUS_BYTE_OOR and is treated as id 0.
+ */
+typedef struct MotCharSwaStepDesc {
+    uint32_t struct_size;         /* sizeof(MotCharSwaStepDesc) */
+    int32_t dtype;                /* MOT_F32 or MOT_BF16 */
+    int32_t n_rows;               /* B, 1 .. 16 (more: MOT_EUNSUPPORTED, use mot_char_swa_fwd) */
+    int32_t c_v;                  /* characters per token */
+    int32_t window;               /* window * c_v <= 64 */
+    int32_t n_heads;
+    int32_t head_dim;             /* 64 or 128 */
+    int32_t dim;                  /* multiple of 4 (8 in bf16) */
+    int32_t version;              /* MotSwaVersion */
+    int32_t char_rows;
+    const int64_t *tokens;        /* [n_rows] device */
+    const int32_t *tok_chars;     /* [tok_rows, c_v] token -> character ids, or NULL */
+    const int64_t *char_ids_new;  /* [n_rows, c_v] the new tokens' character ids, or NULL: exactly one of the two */
+    const void *tok_table;        /* [tok_rows, dim] */
+    int64_t tok_rows;
+    const void *char_table;       /* [char_rows, dim] */
+    const float *attn_norm_w;     /* [dim] fp32 in both modes */
+    const void *wq;               /* [n_heads * head_dim, dim] */
+    const void *wo;               /* [dim, n_heads * head_dim] */
+    const float *lambda_tok;      /* fp32 device scalars (two_residual); NULL = 1 */
+    const float *lambda_char;
+    const float *kv_tables;       /* [2, char_rows, n_heads * head_dim] fp32, as mot_char_swa_fwd left them; required */
+    int32_t *ring;                /* [n_rows, window, c_v] state, updated */
+    int64_t *pos;                 /* [n_rows] state, updated */
+    void *out;                    /* [n_rows, dim] */
+    uint32_t *status;             /* optional */
+    void *workspace;              /* mot_char_swa_step_workspace_bytes(desc) */
+    size_t workspace_bytes;
+    float norm_eps;               /* <= 0 -> 1e-5 */
+    int32_t reserved0;            /* must be 0 */
+    int64_t reserved1;            /* must be 0 */
+} MotCharSwaStepDesc;
+
+size_t mot_char_swa_step_desc_size(void);
+size_t mot_char_swa_step_workspace_bytes(const MotCharSwaStepDesc *desc /* host */);   /* 0 for a descriptor the call would refuse */
+int mot_char_swa_step(const MotCharSwaStepDesc *desc /* host */, mot_stream_t stream);
+
+/*
  * Byte output head of a mixout run with identity ByteSelfAttn layers (use_byte_self_attn off), forward: replaces
  *   ByteMixoutCopy / ByteMixoutSplit.forward          scaled-pre-train/train_gpt.py:483-527 (ByteSelfAttn identity, 382-419)
  *   and the head of GPT.forward                       :618-623  (x = byte_mixout(x); norm; lm_head; 30 sigmoid(l / 7.5); cross_entropy)

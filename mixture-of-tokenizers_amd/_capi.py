@@ -56,6 +56,7 @@ EXPORTS = (
     "mot_cross_attn_desc_size", "mot_cross_attn_workspace_bytes", "mot_cross_attn_fwd",
     "mot_cross_attn_bwd_workspace_bytes", "mot_cross_attn_bwd",
     "mot_char_swa_desc_size", "mot_char_swa_workspace_bytes", "mot_char_swa_fwd",
+    "mot_char_swa_step_desc_size", "mot_char_swa_step_workspace_bytes", "mot_char_swa_step",
     "mot_byte_head_desc_size", "mot_byte_head_workspace_bytes", "mot_byte_head_fwd", "mot_byte_head_bwd",
     "mot_byte_head_step_workspace_bytes", "mot_byte_head_step",
     "mot_token_head_desc_size", "mot_token_head_workspace_bytes", "mot_token_head_fwd",
@@ -151,6 +152,19 @@ class MotCharSwaDesc(C.Structure):
         ("lambda_tok", C.c_void_p), ("lambda_char", C.c_void_p), ("out", C.c_void_p), ("status", C.c_void_p),
         ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("matmul_dtype", C.c_int32), ("kv_tables_ready", C.c_int32),
         ("kv_tables", C.c_void_p), ("io_dtype", C.c_int32), ("reserved1", C.c_int32),
+    ]
+
+
+class MotCharSwaStepDesc(C.Structure):
+    """Mirror of struct MotCharSwaStepDesc (include/mot.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("dtype", C.c_int32), ("n_rows", C.c_int32), ("c_v", C.c_int32), ("window", C.c_int32),
+        ("n_heads", C.c_int32), ("head_dim", C.c_int32), ("dim", C.c_int32), ("version", C.c_int32), ("char_rows", C.c_int32),
+        ("tokens", C.c_void_p), ("tok_chars", C.c_void_p), ("char_ids_new", C.c_void_p), ("tok_table", C.c_void_p), ("tok_rows", C.c_int64),
+        ("char_table", C.c_void_p), ("attn_norm_w", C.c_void_p), ("wq", C.c_void_p), ("wo", C.c_void_p),
+        ("lambda_tok", C.c_void_p), ("lambda_char", C.c_void_p), ("kv_tables", C.c_void_p), ("ring", C.c_void_p), ("pos", C.c_void_p),
+        ("out", C.c_void_p), ("status", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+        ("norm_eps", C.c_float), ("reserved0", C.c_int32), ("reserved1", C.c_int64),
     ]
 
 
@@ -388,6 +402,11 @@ def _load() -> C.CDLL:
     lib.mot_char_swa_workspace_bytes.argtypes = [C.POINTER(MotCharSwaDesc)]
     lib.mot_char_swa_fwd.argtypes = [C.POINTER(MotCharSwaDesc), vp]
     lib.mot_char_swa_fwd.restype = C.c_int
+    lib.mot_char_swa_step_desc_size.restype = C.c_size_t
+    lib.mot_char_swa_step_workspace_bytes.restype = C.c_size_t
+    lib.mot_char_swa_step_workspace_bytes.argtypes = [C.POINTER(MotCharSwaStepDesc)]
+    lib.mot_char_swa_step.argtypes = [C.POINTER(MotCharSwaStepDesc), vp]
+    lib.mot_char_swa_step.restype = C.c_int
     lib.mot_byte_head_desc_size.restype = C.c_size_t
     lib.mot_byte_head_workspace_bytes.restype = C.c_size_t
     lib.mot_byte_head_workspace_bytes.argtypes = [C.POINTER(MotByteHeadDesc)]
@@ -487,6 +506,8 @@ def _load() -> C.CDLL:
         raise ImportError("MotEmbedMixDesc layout mismatch between include/mot.h and _capi.py")
     if lib.mot_char_swa_desc_size() != C.sizeof(MotCharSwaDesc):
         raise ImportError("MotCharSwaDesc layout mismatch between include/mot.h and _capi.py")
+    if lib.mot_char_swa_step_desc_size() != C.sizeof(MotCharSwaStepDesc):
+        raise ImportError("MotCharSwaStepDesc layout mismatch between include/mot.h and _capi.py")
     if lib.mot_cross_attn_desc_size() != C.sizeof(MotCrossAttnDesc):
         raise ImportError("MotCrossAttnDesc layout mismatch between include/mot.h and _capi.py")
     if lib.mot_byte_head_desc_size() != C.sizeof(MotByteHeadDesc):

@@ -161,6 +161,21 @@ class CharTokenizer:
             return 130
         return 131
 
+    def token_char_table(self, token_strings) -> torch.Tensor:
+        """The token -> character-row table of the decode step (functional.char_swa_step): row v is what
+        ``create_char_matrix([[chr_tokenize(c) for c in token_strings[v]]], seq_len=1)`` gives (inference.py:79-96) -- the
+        characters truncated to max_char, 130 behind the last one if there is room, fill 2.  ``token_strings`` =
+        ``tokenizer.convert_ids_to_tokens(range(vocab))``; None or empty entries give [130, 2, 2, ...].  Host only: (vocab, max_char)
+        int32 on the CPU, built once per tokenizer."""
+        import numpy as np
+        tab = np.full((len(token_strings), self.max_char), 2, dtype=np.int32)
+        for v, s in enumerate(token_strings):
+            ids = [self.chr_tokenize(ch) for ch in (s or "")][:self.max_char]
+            tab[v, :len(ids)] = ids
+            if len(ids) < self.max_char:
+                tab[v, len(ids)] = 130
+        return torch.from_numpy(tab)
+
     def _launch(self, codes, tok_off, seq_off, n_seqs, seq_len, device) -> torch.Tensor:
         dev = torch.device(device)
         c = torch.tensor(codes if len(codes) else [0], dtype=torch.int32).to(dev)

@@ -1043,6 +1043,120 @@ def char_swa(tokens: torch.Tensor, char_ids: torch.Tensor, tok_table: torch.Tens
     return out.to(torch.bfloat16) if bf else out
 
 
+class CharSwaState(NamedTuple):
+    """The device-side state of char_swa_step: ring (B, window, c_v) int32, the characters of source position s in slot
+    s % window; pos (B,) int64, the tokens of each row seen so far.  Both are updated in place by every step."""
+    ring: torch.Tensor
+    pos: torch.Tensor
+
+
+def char_swa_state(char_ids: torch.Tensor | None = None, *, n_rows: int | None = None, window: int = 8, c_v: int = 8,
+                   device=None) -> CharSwaState:
+    """The state after a prompt whose character matrix is char_ids (B, T, c_v), or the empty state of n_rows rows (char_ids None).
+    Plain torch indexing on `device` (default: char_ids' device): no library call, so it also runs on the host."""
+    window = int(window)
+    if char_ids is None:
+        if n_rows is None:
+            raise ValueError("char_swa_state: give char_ids (B, T, c_v) or n_rows")
+        return CharSwaState(torch.zeros((int(n_rows), window, int(c_v)), dtype=torch.int32, device=device),
+                            torch.zeros(int(n_rows), dtype=torch.int64, device=device))
+    if char_ids.ndim == 2:
+        char_ids = char_ids[None]
+    if char_ids.ndim != 3 or (n_rows is not None and char_ids.shape[0] != n_rows):
+        raise ValueError(f"char_swa_state: char_ids must be (B, T, c_v), got {tuple(char_ids.shape)}")
+    dev = char_ids.device if device is None else torch.device(device)
+    B, T, cv = char_ids.shape
+    ring = torch.zeros((B, window, cv), dtype=torch.int32, device=dev)
+    src = torch.arange(max(0, T - window), T, device=dev)          # the last `window` positions: one per slot
+    ring[:, src % window] = char_ids.to(dev)[:, src].to(torch.int32)
+    return CharSwaState(ring, torch.full((B,), T, dtype=torch.int64, device=dev))
+
+
+@torch.compiler.disable
+@torch.no_grad()
+def char_swa_step(tokens: torch.Tensor, state: CharSwaState, tok_table: torch.Tensor, char_table: torch.Tensor, *,
+                  tok_chars: torch.Tensor | None = None, char_ids_new: torch.Tensor | None = None,
+                  attn_norm_w: torch.Tensor, char_norm_w: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, wv: torch.Tensor, wo: torch.Tensor,
+                  n_heads: int, head_dim: int, window: int = 8, norm_eps: float = 1e-5, version: str = "two_residual",
+                  lambda_tok: torch.Tensor | None = None, lambda_char: torch.Tensor | None = None, matmul: str | None = None,
+                  kv_cache: dict) -> torch.Tensor:
+    """One decode step of the character mixer (mot_char_swa_step): tokens (B,) int64 on the device (NextToken.token is read in
+    place), B <= 16 -> (B, dim), row t = state.pos of what char_swa computes for each sequence; state is updated in place.  The new
+    tokens' characters come from tok_chars (vocab, c_v) int32 (CharTokenizer.token_char_table) or from char_ids_new (B, c_v).
+    `kv_cache` must hold the key / value tables a char_swa call (the prefill) built for these parameters.  bf16 tables: the tables,
+    wq and wo are read in place as bf16, the result is bf16, the rounding points are char_swa's.  Nothing is read on the host, so
+    the call captures into a hipGraph.  Forms no gradients."""
+    if matmul not in (None, "fp32", "bf16"):
+        raise ValueError(f"char_swa_step: matmul must be None, 'fp32' or 'bf16' (got {matmul!r})")
+    bf = tok_table.dtype == torch.bfloat16
+    if (bf and matmul == "fp32") or (not bf and matmul == "bf16"):
+        raise NotImplementedError("char_swa_step: the step runs in the tables' dtype (bf16 tables on the bf16 path, fp32 tables in fp32); "
+                                  "use char_swa for the other combinations")
+    params = (tok_table, char_table, attn_norm_w, char_norm_w, wq, wk, wv, wo, lambda_tok, lambda_char)
+    dev = capi.require_device(tokens, state.ring, state.pos, tok_chars, char_ids_new, *params)
+    tdt = torch.bfloat16 if bf else torch.float32
+    if (tok_chars is None) == (char_ids_new is None):
+        raise ValueError("char_swa_step: give exactly one of tok_chars and char_ids_new")
+    kv_key = tuple((t.data_ptr(), t._version) for t in (char_table, char_norm_w, wk, wv)) + (float(norm_eps), str(char_table.dtype), str(dev))
+    D, hdim, char_rows = tok_table.shape[1], int(n_heads) * int(head_dim), char_table.shape[0]
+    buf = None if kv_cache is None else kv_cache.get("buf")
+    if buf is None or kv_cache.get("key") != kv_key or buf.numel() != 2 * char_rows * hdim or buf.device != dev:
+        raise RuntimeError("char_swa_step: kv_cache holds no current key / value tables for these parameters; run char_swa (the prefill) "
+                           "with this kv_cache first")
+    ring, pos = state
+    if ring.dtype != torch.int32 or pos.dtype != torch.int64 or ring.ndim != 3 or not ring.is_contiguous() or not pos.is_contiguous() \
+            or pos.shape != (ring.shape[0],) or ring.shape[1] != int(window):
+        raise ValueError("char_swa_step: state must be char_swa_state's (ring (B, window, c_v) int32, pos (B,) int64), contiguous")
+    B, _, c_v = ring.shape
+    if tokens.dtype not in (torch.int64, torch.int32):
+        raise TypeError(f"char_swa_step: tokens must be int64 (NextToken.token) or int32, got {tokens.dtype}")
+    tok = _contig(tokens.detach().reshape(-1).to(torch.int64), torch.int64, "tokens")
+    if tok.numel() != B:
+        raise ValueError(f"char_swa_step: {tok.numel()} tokens for a state of {B} rows")
+    if char_table.dtype != tdt or char_table.shape[1] != D:
+        raise TypeError("char_swa_step: char_table must have tok_table's dtype and number of columns")
+    tt, ct = _contig(tok_table.detach(), tdt, "tok_table"), _contig(char_table.detach(), tdt, "char_table")
+    wq_, wo_ = _contig(wq.detach(), tdt, "wq"), _contig(wo.detach(), tdt, "wo")
+    if attn_norm_w.shape != (D,) or wq_.shape != (hdim, D) or wo_.shape != (D, hdim):
+        raise ValueError(f"char_swa_step: weight shapes do not fit dim {D}, heads {n_heads} x {head_dim}")
+    # the norm weight and the lambdas are fp32 device memory in both modes: with bf16 parameters their widened copies are kept in
+    # kv_cache beside char_swa's, while the originals are unchanged
+    wide_cache = kv_cache.setdefault("widened", {})
+
+    def f32_of(t, shape):
+        if t is None:
+            return None
+        if t.dtype == torch.float32:
+            return _contig(t.detach().reshape(shape), torch.float32, "parameter")
+        key = (t.data_ptr(), t._version, tuple(t.shape), str(t.dtype))
+        hit = wide_cache.get(id(t))
+        if hit is None or hit[0] != key:
+            hit = wide_cache[id(t)] = (key, t.detach().to(torch.bfloat16).float(), t)
+        return hit[1].reshape(shape)
+    anw, lt, lc = f32_of(attn_norm_w, (D,)), f32_of(lambda_tok, (1,)), f32_of(lambda_char, (1,))
+    d = capi.MotCharSwaStepDesc()
+    d.struct_size = C.sizeof(capi.MotCharSwaStepDesc)
+    d.dtype, d.n_rows, d.c_v, d.window, d.n_heads, d.head_dim, d.dim = capi.dtype_code(tdt), B, c_v, int(window), int(n_heads), int(head_dim), D
+    d.version, d.char_rows, d.tok_rows, d.norm_eps = _SWA_VERSIONS[version], char_rows, tt.shape[0], float(norm_eps)
+    keep = [tok]
+    if tok_chars is not None:
+        if tok_chars.dtype != torch.int32 or tok_chars.shape != (tt.shape[0], c_v) or not tok_chars.is_contiguous():
+            raise ValueError(f"char_swa_step: tok_chars must be the contiguous int32 ({tt.shape[0]}, {c_v}) table of token_char_table")
+        d.tok_chars = capi.ptr(tok_chars)
+    else:
+        cn = _contig(char_ids_new.detach().reshape(-1, c_v), torch.int64, "char_ids_new")
+        if cn.shape[0] != B:
+            raise ValueError(f"char_swa_step: char_ids_new must be ({B}, {c_v})")
+        keep.append(cn)
+        d.char_ids_new = capi.ptr(cn)
+    d.tokens, d.tok_table, d.char_table, d.attn_norm_w, d.wq, d.wo = capi.ptr(tok), capi.ptr(tt), capi.ptr(ct), capi.ptr(anw), capi.ptr(wq_), capi.ptr(wo_)
+    d.lambda_tok, d.lambda_char, d.kv_tables, d.ring, d.pos = capi.ptr(lt), capi.ptr(lc), capi.ptr(buf), capi.ptr(ring), capi.ptr(pos)
+    out = torch.empty((B, D), dtype=tdt, device=dev)
+    d.out = capi.ptr(out)
+    _launch(dev, d, capi.lib.mot_char_swa_step, ws_bytes=capi.lib.mot_char_swa_step_workspace_bytes)
+    return out
+
+
 # ----------------------------------------------------------------------------------------------
 # byte output head: mixout (identity layers) + norm + lm_head + softcap + cross-entropy, train_gpt.py:618-623
 # ----------------------------------------------------------------------------------------------

@@ -1044,6 +1044,39 @@ class CharMixerFrontEnd(nn.Module):
         self.char_embeddings = LazyEmbedding(char_vocab_size, model_args.dim, "bytes", max_char)
         self.max_char = max_char
         self.char_token_mixer = TokenMixByCharBMMBlock(model_args)
+        self.register_buffer("token_chars", None, persistent=False)   # set_token_chars: token id -> character ids, for step()
 
     def forward(self, input_ids: Tensor, char_ids: Tensor) -> Tensor:
         return self.char_token_mixer(self.embed_tokens(input_ids), self.char_embeddings(char_ids), None)
+
+    # ---- decoding one token at a time: forward() over the prompt (it fills the mixer's key / value tables), decode_state() of the
+    # prompt, then step() per new token -- nothing is read on the host, so a step captures into a hipGraph
+    def set_token_chars(self, table: Tensor) -> None:
+        """``table`` = CharTokenizer.token_char_table(tokenizer.convert_ids_to_tokens(range(vocab))): (vocab, max_char) int32."""
+        if table.ndim != 2 or table.shape != (self.embed_tokens.num_embeddings, self.max_char):
+            raise ValueError(f"token_chars must be ({self.embed_tokens.num_embeddings}, {self.max_char}), got {tuple(table.shape)}")
+        self.token_chars = table.to(device=self.embed_tokens.weight.device, dtype=torch.int32).contiguous()
+
+    def decode_state(self, input_ids: Tensor, char_ids: Tensor) -> "F_mot.CharSwaState":
+        """The step's state after the prompt (input_ids (B, T), char_ids (B, T, max_char)) that forward() was given."""
+        if input_ids.ndim == 1:
+            input_ids = input_ids[None]
+        blk = self.char_token_mixer
+        return F_mot.char_swa_state(char_ids.reshape(input_ids.shape[0], input_ids.shape[1], -1), window=blk.tok_attention.window_size,
+                                    c_v=self.max_char, device=self.embed_tokens.weight.device)
+
+    @torch.no_grad()
+    def step(self, state: "F_mot.CharSwaState", token: Tensor, char_ids_new: Tensor | None = None) -> Tensor:
+        """``mixed_embeddings`` of the newest position alone: token (B,) on the device (NextToken.token) -> (B, 1, dim); the state
+        moves on by one token.  The characters come from set_token_chars' table unless char_ids_new (B, max_char) is given."""
+        blk, ta = self.char_token_mixer, self.char_token_mixer.tok_attention
+        if char_ids_new is None and self.token_chars is None:
+            raise RuntimeError("CharMixerFrontEnd.step: call set_token_chars(table) first, or pass char_ids_new")
+        two = blk.version == "two_residual"
+        h = F_mot.char_swa_step(token, state, self.embed_tokens.weight, self.char_embeddings.weight,
+                                tok_chars=None if char_ids_new is not None else self.token_chars, char_ids_new=char_ids_new,
+                                attn_norm_w=blk.attention_norm.weight, char_norm_w=blk.char_norm.weight, wq=ta.wq.weight, wk=ta.wk.weight,
+                                wv=ta.wv.weight, wo=ta.wo.weight, n_heads=ta.n_heads, head_dim=ta.head_dim, window=ta.window_size,
+                                norm_eps=blk.attention_norm.eps, version=blk.version, lambda_tok=blk.lambda_tok if two else None,
+                                lambda_char=blk.lambda_char if two else None, kv_cache=blk._kv_cache)
+        return (h + blk.feed_forward.forward(blk.ffn_norm(h)))[:, None, :]
