@@ -542,6 +542,49 @@ size_t mot_char_swa_step_workspace_bytes(const MotCharSwaStepDesc *desc /* host 
 int mot_char_swa_step(const MotCharSwaStepDesc *desc /* host */, mot_stream_t stream);
 
 /*
+ * The feed-forward that closes the character mixer's block, on the rows of a decode step (inference/inference.py:269, 121-144):
+ *   out[r] = h[r] + w2 (silu(w1 xn[r]) * w3 xn[r]),   xn[r] = (h[r] * rs) * norm_w,  rs = 1 / sqrt(mean(h[r]^2) + norm_eps)
+ * for n_rows <= 16 rows, h = the output of mot_char_swa_step.  Three launches on `stream` (gate-up: both of w1 and w3 in one pass
+ * over the rows staged in LDS; down: w2 against slices of 1024 elements of inter, one workgroup per 16 columns and slice; the sum
+ * of the slices' shares in slice order plus the residual); no allocation, sync, memset or memcpy node; nothing is read on the host;
+ * no atomics.  Every sum has a fixed order that does not depend on n_rows: the same bits on every run, and for a row whatever rows
+ * stand beside it.  silu(a) = a / (1 + exp(-a)) is finite for every finite a.
+ * dtype MOT_F32: everything fp32.  MOT_BF16: h, w1, w2, w3 and out are bf16 and read in place (norm_w stays fp32); xn, a = w1 xn,
+ * silu(a), b = w3 xn, silu(a) * b and the output of w2 are rounded to bf16, all sums are fp32, the residual is added to the widened
+ * output of w2 in fp32 and rounded once.
+ * Refused before any HIP call, by the size query too (it then returns 0): a wrong struct_size, an unknown dtype, non-zero reserved
+ * fields (MOT_EINVAL); n_rows outside 1..16 (MOT_EUNSUPPORTED: use the torch path); dim or inter not a multiple of 4, inter above
+ * 2^24 (MOT_ESHAPE), not a multiple of 8 in bf16 (MOT_EUNSUPPORTED) -- the slices need nothing more, the last one may be short;
+ * staged rows R * dim * sizeof(element) above 128 KiB, R = n_rows rounded up to 1, 2, 4, 8 or 16 (MOT_EUNSUPPORTED); a NULL h,
+ * norm_w, w1, w3, w2 or out (MOT_EINVAL); one of them not 16-byte aligned (MOT_EUNSUPPORTED); out overlapping h (MOT_EINVAL).
+ * Workspace: align256(n_rows * inter * sizeof(element)) + align256(ceil(inter / 1024) * n_rows * dim * 4) bytes.
+ */
+typedef struct MotFfnStepDesc {
+    uint32_t struct_size;         /* sizeof(MotFfnStepDesc) */
+    int32_t dtype;                /* MOT_F32 or MOT_BF16 */
+    int32_t n_rows;               /* 1 .. 16 */
+    int32_t dim;                  /* multiple of 4 (8 in bf16) */
+    int32_t inter;                /* multiple of 4 (8 in bf16) */
+    int32_t reserved0;            /* must be 0 */
+    const void *h;                /* [n_rows, dim] */
+    const float *norm_w;          /* [dim] fp32 in both modes */
+    const void *w1;               /* [inter, dim] */
+    const void *w3;               /* [inter, dim] */
+    const void *w2;               /* [dim, inter] */
+    void *out;                    /* [n_rows, dim]; must not overlap h */
+    uint32_t *status;             /* optional; reserved, the call raises no flag */
+    void *workspace;              /* mot_ffn_step_workspace_bytes(desc) */
+    size_t workspace_bytes;
+    float norm_eps;               /* <= 0 -> 1e-5 */
+    int32_t reserved1;            /* must be 0 */
+    int64_t reserved2;            /* must be 0 */
+} MotFfnStepDesc;
+
+size_t mot_ffn_step_desc_size(void);
+size_t mot_ffn_step_workspace_bytes(const MotFfnStepDesc *desc /* host */);   /* 0 for a descriptor the call would refuse */
+int mot_ffn_step(const MotFfnStepDesc *desc /* host */, mot_stream_t stream);
+
+/*
  * Byte output head of a mixout run with identity ByteSelfAttn layers (use_byte_self_attn off), forward: replaces
  *   ByteMixoutCopy / ByteMixoutSplit.forward          scaled-pre-train/train_gpt.py:483-527 (ByteSelfAttn identity, 382-419)
  *   and the head of GPT.forward                       :618-623  (x = byte_mixout(x); norm; lm_head; 30 sigmoid(l / 7.5); cross_entropy)

@@ -57,6 +57,7 @@ EXPORTS = (
     "mot_cross_attn_bwd_workspace_bytes", "mot_cross_attn_bwd",
     "mot_char_swa_desc_size", "mot_char_swa_workspace_bytes", "mot_char_swa_fwd",
     "mot_char_swa_step_desc_size", "mot_char_swa_step_workspace_bytes", "mot_char_swa_step",
+    "mot_ffn_step_desc_size", "mot_ffn_step_workspace_bytes", "mot_ffn_step",
     "mot_byte_head_desc_size", "mot_byte_head_workspace_bytes", "mot_byte_head_fwd", "mot_byte_head_bwd",
     "mot_byte_head_step_workspace_bytes", "mot_byte_head_step",
     "mot_token_head_desc_size", "mot_token_head_workspace_bytes", "mot_token_head_fwd",
@@ -165,6 +166,16 @@ class MotCharSwaStepDesc(C.Structure):
         ("lambda_tok", C.c_void_p), ("lambda_char", C.c_void_p), ("kv_tables", C.c_void_p), ("ring", C.c_void_p), ("pos", C.c_void_p),
         ("out", C.c_void_p), ("status", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
         ("norm_eps", C.c_float), ("reserved0", C.c_int32), ("reserved1", C.c_int64),
+    ]
+
+
+class MotFfnStepDesc(C.Structure):
+    """Mirror of struct MotFfnStepDesc (include/mot.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("dtype", C.c_int32), ("n_rows", C.c_int32), ("dim", C.c_int32), ("inter", C.c_int32),
+        ("reserved0", C.c_int32), ("h", C.c_void_p), ("norm_w", C.c_void_p), ("w1", C.c_void_p), ("w3", C.c_void_p), ("w2", C.c_void_p),
+        ("out", C.c_void_p), ("status", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+        ("norm_eps", C.c_float), ("reserved1", C.c_int32), ("reserved2", C.c_int64),
     ]
 
 
@@ -407,6 +418,11 @@ def _load() -> C.CDLL:
     lib.mot_char_swa_step_workspace_bytes.argtypes = [C.POINTER(MotCharSwaStepDesc)]
     lib.mot_char_swa_step.argtypes = [C.POINTER(MotCharSwaStepDesc), vp]
     lib.mot_char_swa_step.restype = C.c_int
+    lib.mot_ffn_step_desc_size.restype = C.c_size_t
+    lib.mot_ffn_step_workspace_bytes.restype = C.c_size_t
+    lib.mot_ffn_step_workspace_bytes.argtypes = [C.POINTER(MotFfnStepDesc)]
+    lib.mot_ffn_step.argtypes = [C.POINTER(MotFfnStepDesc), vp]
+    lib.mot_ffn_step.restype = C.c_int
     lib.mot_byte_head_desc_size.restype = C.c_size_t
     lib.mot_byte_head_workspace_bytes.restype = C.c_size_t
     lib.mot_byte_head_workspace_bytes.argtypes = [C.POINTER(MotByteHeadDesc)]
@@ -508,6 +524,8 @@ def _load() -> C.CDLL:
         raise ImportError("MotCharSwaDesc layout mismatch between include/mot.h and _capi.py")
     if lib.mot_char_swa_step_desc_size() != C.sizeof(MotCharSwaStepDesc):
         raise ImportError("MotCharSwaStepDesc layout mismatch between include/mot.h and _capi.py")
+    if lib.mot_ffn_step_desc_size() != C.sizeof(MotFfnStepDesc):
+        raise ImportError("MotFfnStepDesc layout mismatch between include/mot.h and _capi.py")
     if lib.mot_cross_attn_desc_size() != C.sizeof(MotCrossAttnDesc):
         raise ImportError("MotCrossAttnDesc layout mismatch between include/mot.h and _capi.py")
     if lib.mot_byte_head_desc_size() != C.sizeof(MotByteHeadDesc):

@@ -292,6 +292,9 @@ int mot_char_swa_fwd(const MotCharSwaDesc *desc, mot_stream_t stream) {
 size_t mot_char_swa_step_desc_size(void) { return sizeof(MotCharSwaStepDesc); }
 size_t mot_char_swa_step_workspace_bytes(const MotCharSwaStepDesc *desc) { return char_swa_step_workspace_bytes(desc); }
 int mot_char_swa_step(const MotCharSwaStepDesc *desc, mot_stream_t stream) { return launch_char_swa_step(desc, (hipStream_t)stream); }
+size_t mot_ffn_step_desc_size(void) { return sizeof(MotFfnStepDesc); }
+size_t mot_ffn_step_workspace_bytes(const MotFfnStepDesc *desc) { return ffn_step_workspace_bytes(desc); }
+int mot_ffn_step(const MotFfnStepDesc *desc, mot_stream_t stream) { return launch_ffn_step(desc, (hipStream_t)stream); }
 
 size_t mot_cross_attn_desc_size(void) { return sizeof(MotCrossAttnDesc); }
 

@@ -129,6 +129,9 @@ int launch_char_swa(const MotCharSwaDesc &d, hipStream_t stream);
 // one decode step of the character mixer (mot_swa_step.hip): its own validation, every refusal before any HIP call
 size_t char_swa_step_workspace_bytes(const MotCharSwaStepDesc *d);   // 0 for a descriptor the call would refuse
 int launch_char_swa_step(const MotCharSwaStepDesc *d, hipStream_t stream);
+// the feed-forward behind that step (mot_ffn_step.hip): likewise
+size_t ffn_step_workspace_bytes(const MotFfnStepDesc *d);   // 0 for a descriptor the call would refuse
+int launch_ffn_step(const MotFfnStepDesc *d, hipStream_t stream);
 size_t cross_attn_workspace_bytes(const MotCrossAttnDesc &d);
 int launch_cross_attn(const MotCrossAttnDesc &d, hipStream_t stream);
 // the byte output head (mot_head.hip): validation before any HIP call, then the launches

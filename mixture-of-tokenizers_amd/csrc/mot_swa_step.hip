@@ -20,30 +20,10 @@
 // MOT_BF16: the tables, wq and wo are bf16 and read in place; xn, q, k, v, y and the output of wo are rounded to bf16 where
 // launch_char_swa (matmul_dtype = io_dtype = MOT_BF16) rounds them, softmax and sums stay fp32, the residuals are added to the
 // widened bf16 output of wo in fp32 with one rounding (swa_residual_bf16_kernel).
-#include "mot_mix.hpp"
+#include "mot_step.hpp"
 
 namespace mot {
 namespace {
-
-constexpr int kStepMaxRows = 16;
-constexpr int kStepThreads = 256, kStepWaves = kStepThreads / 64;   // the two product kernels (512 threads, same session: 110 -> 93 us at B 16 in fp32, 24 -> 27 us replayed at B 1 in bf16)
-constexpr int kStepCls = 4;                     // rows of the weight matrix a wave holds in flight
-constexpr size_t kStepMaxLds = 128u << 10;      // the staged rows: R * dim (R * hdim) elements
-
-template <typename T> struct StepVec;           // one 16-byte lane load of a weight row / of the staged rows
-template <> struct StepVec<float> {
-    static constexpr int N = 4;
-    float4v q;
-    __device__ __forceinline__ float get(int e) const { return q[e]; }
-};
-template <> struct StepVec<__bf16> {
-    static constexpr int N = 8;
-    bf16x8v q;
-    __device__ __forceinline__ float get(int e) const { return (float)q[e]; }
-};
-
-template <typename T> __device__ __forceinline__ float step_round(float v) { return v; }          // a value of a tensor of type T
-template <> __device__ __forceinline__ float step_round<__bf16>(float v) { return (float)(__bf16)v; }
 
 struct StepArgs {
     int n_rows, c_v, window, n_heads, dim, hdim, version, char_rows;
@@ -63,42 +43,6 @@ struct StepArgs {
 __device__ __forceinline__ int64_t step_token(const StepArgs &A, int r) {   // clamped; the state workgroup raises the flag
     const int64_t id = A.tokens[r];
     return (uint64_t)id < (uint64_t)A.tok_rows ? id : 0;
-}
-
-// S[r][c] for r < n_rows, c in [c0, c0 + 4): sum_k xs[r][k] W[c][k], fp32 fused multiply-adds over the lane's slices in k order,
-// then the wave's DPP sum; f(r, c, value) is called by lane c - c0 < 4.
-template <typename T, int R, class F>
-__device__ __forceinline__ void step_products(const T *__restrict__ xs, const T *__restrict__ W, int K, int c0, int n_rows, F &&f) {
-    typedef StepVec<T> Vec;
-    const int lane = threadIdx.x & 63, kvec = K / Vec::N;
-    float acc[kStepCls][R];
-#pragma unroll
-    for (int c = 0; c < kStepCls; ++c)
-#pragma unroll
-        for (int r = 0; r < R; ++r) acc[c][r] = 0.f;
-#pragma unroll 2
-    for (int kv = lane; kv < kvec; kv += 64) {
-        Vec w[kStepCls];
-#pragma unroll
-        for (int c = 0; c < kStepCls; ++c) w[c] = ((const Vec *)(W + (int64_t)(c0 + c) * K))[kv];
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const Vec xv = ((const Vec *)(xs + r * K))[kv];
-#pragma unroll
-            for (int e = 0; e < Vec::N; ++e) {
-                const float xe = xv.get(e);
-#pragma unroll
-                for (int c = 0; c < kStepCls; ++c) acc[c][r] = __builtin_fmaf(w[c].get(e), xe, acc[c][r]);
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        float s[kStepCls];
-#pragma unroll
-        for (int c = 0; c < kStepCls; ++c) s[c] = wave_sum(acc[c][r]);
-        if (lane < kStepCls && r < n_rows) f(r, c0 + lane, lane == 0 ? s[0] : lane == 1 ? s[1] : lane == 2 ? s[2] : s[3]);
-    }
 }
 
 template <typename T, int R>

@@ -1157,6 +1157,49 @@ def char_swa_step(tokens: torch.Tensor, state: CharSwaState, tok_table: torch.Te
     return out
 
 
+@torch.compiler.disable
+@torch.no_grad()
+def char_ffn_step(h: torch.Tensor, norm_w: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, w3: torch.Tensor, *, norm_eps: float = 1e-5,
+                  cache: dict | None = None) -> torch.Tensor:
+    """The feed-forward that closes the character mixer's block on the rows of a decode step (mot_ffn_step): h (B, dim), B <= 16,
+    char_swa_step's result -> ``h + w2(silu(w1 n) * w3 n)``, ``n = RMSNorm(h) * norm_w``; w1 and w3 (inter, dim), w2 (dim, inter),
+    FeedForward's weights, used in place.  h and the three matrices share one dtype, fp32 or bf16 (then the rounding points are
+    those of the module in a bf16 cast); norm_w is fp32 device memory in the call: the widened copy of a bf16 norm weight is kept
+    in `cache` (as char_swa_step keeps its own in kv_cache) while the weight is unchanged.  Nothing is read on the host, so the call
+    captures into a hipGraph.  Forms no gradients."""
+    dev = capi.require_device(h, norm_w, w1, w2, w3)
+    tdt = h.dtype
+    capi.dtype_code(tdt)
+    if h.ndim != 2:
+        raise ValueError(f"char_ffn_step: h must be (B, dim), got {tuple(h.shape)}")
+    B, D = h.shape
+    if B > 16:
+        raise NotImplementedError(f"char_ffn_step: {B} rows, the step is built for at most 16: use FeedForward (h + feed_forward(ffn_norm(h)))")
+    h_ = _contig(h.detach(), tdt, "h")
+    w1_, w2_, w3_ = _contig(w1.detach(), tdt, "w1"), _contig(w2.detach(), tdt, "w2"), _contig(w3.detach(), tdt, "w3")
+    inter = w1_.shape[0]
+    if norm_w.shape != (D,) or w1_.shape != (inter, D) or w3_.shape != (inter, D) or w2_.shape != (D, inter):
+        raise ValueError(f"char_ffn_step: weight shapes do not fit h {tuple(h.shape)}: norm_w ({D},), w1 and w3 (inter, {D}), w2 ({D}, inter)")
+    if norm_w.dtype == torch.float32:
+        nw = _contig(norm_w.detach(), torch.float32, "norm_w")
+    else:
+        key = (norm_w.data_ptr(), norm_w._version, str(norm_w.dtype), str(dev))
+        hit = None if cache is None else cache.get("norm_w")
+        if hit is None or hit[0] != key:
+            hit = (key, norm_w.detach().to(torch.bfloat16).float().contiguous(), norm_w)
+            if cache is not None:
+                cache["norm_w"] = hit
+        nw = hit[1]
+    d = capi.MotFfnStepDesc()
+    d.struct_size = C.sizeof(capi.MotFfnStepDesc)
+    d.dtype, d.n_rows, d.dim, d.inter, d.norm_eps = capi.dtype_code(tdt), B, D, inter, float(norm_eps)
+    d.h, d.norm_w, d.w1, d.w3, d.w2 = capi.ptr(h_), capi.ptr(nw), capi.ptr(w1_), capi.ptr(w3_), capi.ptr(w2_)
+    out = torch.empty((B, D), dtype=tdt, device=dev)
+    d.out = capi.ptr(out)
+    _launch(dev, d, capi.lib.mot_ffn_step, ws_bytes=capi.lib.mot_ffn_step_workspace_bytes)
+    return out
+
+
 # ----------------------------------------------------------------------------------------------
 # byte output head: mixout (identity layers) + norm + lm_head + softcap + cross-entropy, train_gpt.py:618-623
 # ----------------------------------------------------------------------------------------------

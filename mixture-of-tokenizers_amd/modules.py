@@ -956,7 +956,7 @@ class RMSNorm(nn.Module):  # inference.py:119-132 (a plain torch module: the tru
         return self._norm(x.float()).type_as(x) * self.weight
 
 
-class FeedForward(nn.Module):  # inference.py:135-144, SwiGLU: plain dense layers, outside the embedding path (torch ops)
+class FeedForward(nn.Module):  # inference.py:135-144, SwiGLU: plain dense layers (torch ops); on the rows of a decode step the block can run it fused (ffn_step)
     def __init__(self, args: ModelArgs):
         super().__init__()
         self.w1 = nn.Linear(args.dim, args.intermediate_dim, bias=False)
@@ -1032,6 +1032,13 @@ class TokenMixByCharBMMBlock(nn.Module):
         h = self.mix(toks, chars)
         return h + self.feed_forward.forward(self.ffn_norm(h))          # line 269: plain torch
 
+    def ffn_step(self, h: Tensor) -> Tensor:
+        """Line 269 on the rows of a decode step, h (B, dim) with B <= 16, in one library call (functional.char_ffn_step):
+        the block's own ffn_norm and feed_forward parameters, read in place."""
+        ff = self.feed_forward
+        return F_mot.char_ffn_step(h, self.ffn_norm.weight, ff.w1.weight, ff.w2.weight, ff.w3.weight, norm_eps=self.ffn_norm.eps,
+                                   cache=self._kv_cache.setdefault("ffn_step", {}))
+
 
 class CharMixerFrontEnd(nn.Module):
     """The embedding front of CustomLlamaModel (inference.py:273-335): ``embed_tokens`` (the Llama table), ``char_embeddings``
@@ -1066,9 +1073,10 @@ class CharMixerFrontEnd(nn.Module):
                                     c_v=self.max_char, device=self.embed_tokens.weight.device)
 
     @torch.no_grad()
-    def step(self, state: "F_mot.CharSwaState", token: Tensor, char_ids_new: Tensor | None = None) -> Tensor:
+    def step(self, state: "F_mot.CharSwaState", token: Tensor, char_ids_new: Tensor | None = None, *, fused_ffn: bool = False) -> Tensor:
         """``mixed_embeddings`` of the newest position alone: token (B,) on the device (NextToken.token) -> (B, 1, dim); the state
-        moves on by one token.  The characters come from set_token_chars' table unless char_ids_new (B, max_char) is given."""
+        moves on by one token.  The characters come from set_token_chars' table unless char_ids_new (B, max_char) is given.
+        ``fused_ffn``: the block's feed-forward line runs as one library call (TokenMixByCharBMMBlock.ffn_step) instead of torch ops."""
         blk, ta = self.char_token_mixer, self.char_token_mixer.tok_attention
         if char_ids_new is None and self.token_chars is None:
             raise RuntimeError("CharMixerFrontEnd.step: call set_token_chars(table) first, or pass char_ids_new")
@@ -1079,4 +1087,6 @@ class CharMixerFrontEnd(nn.Module):
                                 wv=ta.wv.weight, wo=ta.wo.weight, n_heads=ta.n_heads, head_dim=ta.head_dim, window=ta.window_size,
                                 norm_eps=blk.attention_norm.eps, version=blk.version, lambda_tok=blk.lambda_tok if two else None,
                                 lambda_char=blk.lambda_char if two else None, kv_cache=blk._kv_cache)
+        if fused_ffn:
+            return blk.ffn_step(h)[:, None, :]
         return (h + blk.feed_forward.forward(blk.ffn_norm(h)))[:, None, :]
